@@ -10,7 +10,12 @@ with SGD(momentum 0.9, nesterov, wd 1e-4, torch's default lr 1e-3), CosineAnneal
 class-weighted CE ([1, 3]) -- all on hand-written gfx950 kernels (libiswm_hip.so).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model resnet101|resnet50]
-                    [--batch B] [--size S] [--no-cpu-baseline]
+                    [--batch B] [--size S] [--dump-outputs DIR]
+                    [--full [--no-kernel-timing] [--no-alt] [--no-cpu-baseline] [--torch-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints the headline; --full adds the per-kernel warm-up
+profile and the roofline of the dominant conv kernel, the host's enqueue time on an idle queue, the same step in
+the other conv arithmetics and the CPU baseline (each of these can be left out with its --no-* switch).
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -78,14 +83,22 @@ def parse():
     ap.add_argument("--output-stride", type=int, default=16, choices=[8, 16])
     ap.add_argument("--batch", type=int, default=16, help="images per GPU")
     ap.add_argument("--size", type=int, default=513)
+    ap.add_argument("--full", action="store_true",
+                    help="also take the figures beyond the headline: kernel timing and roofline, idle-queue host "
+                         "time, the other conv arithmetics, the CPU baseline")
     ap.add_argument("--torch-baseline", action="store_true",
-                    help="also time the same step on stock PyTorch-ROCm ops (MIOpen) on this GPU (adds ~2 min)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+                    help="with --full: also time the same step on stock PyTorch-ROCm ops (MIOpen) on this GPU (adds ~2 min)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the kernel timing and roofline")
     ap.add_argument("--conv-math", default=None, choices=["f32", "bf16x6", "bf16"],
                     help="convolution arithmetic (default: library default = bf16x6, or $ISWM_CONV_MATH)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra exact-fp32-MFMA measurement")
-    return ap.parse_args()
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the steps in the other conv arithmetics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.torch_baseline and not args.full:
+        ap.error("--torch-baseline is part of --full")
+    return args
 
 
 def host_cores():
@@ -197,6 +210,53 @@ def torch_rocm_baseline(model_name, output_stride, size, batch, dev):
                     torch.__version__}
 
 
+# --dump-outputs: the logits whole up to DUMP_LOGITS_MAX elements (16 x 2 x 513 x 513 = 8.4 M), else a sample of that
+# many; samples of DUMP_SAMPLE elements of the parameter / gradient arenas (59 M for ResNet-101) and of the BatchNorm
+# running statistics.  At most 10 M + 3 x 2 M floats and the loss: under DUMP_LIMIT_BYTES.
+DUMP_LOGITS_MAX = 10_000_000
+DUMP_SAMPLE = 2_000_000
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _sample(flat, k, seed):
+    """the 1-D tensor `flat` whole if it has at most k elements, else k of them at positions fixed by `seed` and its size"""
+    import numpy as np
+    import torch
+    n = flat.numel()
+    if n <= k:
+        return flat
+    idx = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)]
+
+
+def dump_outputs(path, loss, logits, model, opt):
+    """What the last timed step handed its caller, as float32 DIR/<name>.npy: the loss, the logits, and the state the
+    step left behind -- parameters and gradients (the optimizer's flat arenas, sampled at the same positions) and the
+    BatchNorm running statistics.  Same arguments -> same inputs and the same sample positions from run to run."""
+    import numpy as np
+    import torch
+    logits = logits.detach()
+    if logits.numel() > DUMP_LOGITS_MAX:
+        logits = _sample(logits.reshape(-1), DUMP_LOGITS_MAX, 0)
+    bn = [t.detach().reshape(-1) for m in model.modules() if isinstance(m, torch.nn.BatchNorm2d)
+          for t in (m.running_mean, m.running_var) if t is not None]
+    arrays = {
+        "loss": loss.detach().reshape(()),
+        "logits": logits,
+        "params_sample": _sample(opt.arena.data, DUMP_SAMPLE, 1),
+        "grads_sample": _sample(opt.arena.grad, DUMP_SAMPLE, 1),
+        "bn_running_stats_sample": _sample(torch.cat(bn), DUMP_SAMPLE, 2),
+    }
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    nbytes = sum(a.nbytes for a in arrays.values())
+    assert nbytes <= DUMP_LIMIT_BYTES, nbytes
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    print("[bench] dump-outputs: %d arrays, %.1f MB -> %s" % (len(arrays), nbytes / 1e6, path), file=sys.stderr,
+          flush=True)
+
+
 def main():
     args = parse()
     import torch
@@ -260,25 +320,27 @@ def main():
         loss.backward()
         opt.step()
         sched.step()
-        return loss
+        return loss, logits
 
-    # warm-up; its last step is profiled per conv kernel to find the dominant one, so that the timed region
+    # warm-up; with --full its last step is profiled per conv kernel to find the dominant one, so that the timed region
     # only brackets THAT kernel's launches with events (bracketing all ~350 conv launches costs ~3 % of a step)
+    kernel_timing = args.full and not args.no_kernel_timing
     kprof, warm_summary, head_fwd = None, None, None
-    head = model.classifier
-    head_fwd_orig = head.fwd
+    if kernel_timing:
+        head = model.classifier
+        head_fwd_orig = head.fwd
 
-    def head_fwd_scoped(*a, **k):          # stamps the ASPP + decoder forward convs of the profiled warm-up step
-        if ops.KPROF is not None:
-            ops.KPROF.scope = "head_fwd"
-        try:
-            return head_fwd_orig(*a, **k)
-        finally:
+        def head_fwd_scoped(*a, **k):          # stamps the ASPP + decoder forward convs of the profiled warm-up step
             if ops.KPROF is not None:
-                ops.KPROF.scope = None
-    head.fwd = head_fwd_scoped
+                ops.KPROF.scope = "head_fwd"
+            try:
+                return head_fwd_orig(*a, **k)
+            finally:
+                if ops.KPROF is not None:
+                    ops.KPROF.scope = None
+        head.fwd = head_fwd_scoped
     for i in range(args.warmup):
-        if i == args.warmup - 1 and not args.no_kernel_timing:
+        if i == args.warmup - 1 and kernel_timing:
             torch.cuda.synchronize()
             ops.KPROF = ops.KernelProfile()
         step()
@@ -289,7 +351,7 @@ def main():
         ops.KPROF = None
         dominant = max(warm_summary.items(), key=lambda kv: kv[1]["ms"])[0]
         kprof = ops.KernelProfile(only=dominant)
-    elif not args.no_kernel_timing:
+    elif kernel_timing:
         kprof = ops.KernelProfile()
     if world > 1:
         dist.barrier()
@@ -297,7 +359,7 @@ def main():
     ops.KPROF = kprof
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, logits = step()
     t_enqueued = time.perf_counter() - t0          # host time to enqueue the work (GPU still running)
     if world > 1:
         dist.barrier()
@@ -321,13 +383,17 @@ def main():
                 "exposed_wait_ms_per_step": round(st["exposed_wait_ms"] / nsteps, 3),
                 "note": "rank 0's view; exposed_wait = compute stream stalled in finish_grad_sync (includes warm-up steps)"}
     final_loss = float(loss.detach())
-    # host cost of enqueuing ONE step into an idle queue (the timed loop's enqueue time is back-pressure: the host runs
-    # into the launch queue limit and then advances at the GPU's pace)
-    torch.cuda.synchronize()
-    th = time.perf_counter()
-    step()
-    host_idle_ms = (time.perf_counter() - th) * 1e3
-    torch.cuda.synchronize()
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, loss, logits, model, opt)
+    host_idle_ms = None
+    if args.full:
+        # host cost of enqueuing ONE step into an idle queue (the timed loop's enqueue time is back-pressure: the host
+        # runs into the launch queue limit and then advances at the GPU's pace)
+        torch.cuda.synchronize()
+        th = time.perf_counter()
+        step()
+        host_idle_ms = (time.perf_counter() - th) * 1e3
+        torch.cuda.synchronize()
 
     if rank == 0:
         ms = dt / args.steps * 1e3
@@ -361,9 +427,10 @@ def main():
                 "parallelism": "dp%d" % world,
             },
             "final_loss": round(final_loss, 6),
-            "host_enqueue_ms_idle": round(host_idle_ms, 3),
             "host_enqueue_ms_backpressured": round(t_enqueued / args.steps * 1e3, 3),
         }
+        if host_idle_ms is not None:
+            out["host_enqueue_ms_idle"] = round(host_idle_ms, 3)
         if comm is not None:
             out["comm"] = comm
         if kprof is not None:
@@ -400,7 +467,7 @@ def main():
                     "launches": head_fwd["launches"], "ms": round(head_fwd["ms"], 3), "tflops": round(tf, 2),
                     "frac_of_fp32_mfma_peak": round(tf / FP32_MFMA_PEAK_TFLOPS, 4),
                     "frac_of_bf16x6_peak": round(tf / X6_PEAK_TFLOPS, 4) if math_name == "bf16x6" else None}
-        if world == 1 and math_name == "bf16x6" and not args.no_alt:
+        if args.full and world == 1 and math_name == "bf16x6" and not args.no_alt:
             # same step with the exact-fp32 MFMA kernels, for reference (outside the timed region above)
             lib.iswm_set_conv_math(0)
             for _ in range(2):
@@ -433,13 +500,13 @@ def main():
                                                  "product, fp32 accumulation / BatchNorm statistics / master weights / loss.  "
                                                  "Reduced precision: NOT the headline arithmetic; parity unpinned (the reference "
                                                  "has no such mode; checked against a same-rounding oracle)"}
-        if world == 1 and args.torch_baseline:
+        if args.full and world == 1 and args.torch_baseline:
             del model, net, opt, images, labels          # free the product's activations / arenas first
             torch.cuda.empty_cache()
             tb = torch_rocm_baseline(args.model, args.output_stride, S, B, dev)
             tb["speedup_of_this_path"] = round(out["value"] / tb["value"], 3)
             out["torch_rocm_baseline"] = tb
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.model, args.output_stride, S)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -5,8 +5,8 @@ tag=${1:-r03}
 out=gpurun_out/profiles_$tag
 mkdir -p $out/pmc
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-python3 bench.py --steps 20 --warmup 5 --torch-baseline > $out/bench.json 2> $out/bench.err
-rocprofv3 --kernel-trace --stats -d $out/kt -o kt -- python3 bench.py --steps 10 --warmup 3 --no-alt --no-cpu-baseline --no-kernel-timing > $out/bench_rocprof.json 2> $out/bench_rocprof.err
+python3 bench.py --full --steps 20 --warmup 5 --torch-baseline > $out/bench.json 2> $out/bench.err
+rocprofv3 --kernel-trace --stats -d $out/kt -o kt -- python3 bench.py --full --steps 10 --warmup 3 --no-alt --no-cpu-baseline --no-kernel-timing > $out/bench_rocprof.json 2> $out/bench_rocprof.err
 python3 tools/prof_summary.py $out/kt/kt_results.db 14 $out/bench_kernel_stats.txt > /dev/null
 python3 tools/prof_sequence.py $out/kt/kt_results.db 2 $out/step_sequence.txt > /dev/null
 python3 tools/conv_table.py resnet101 16 > $out/conv_table.txt 2>&1
