@@ -143,9 +143,6 @@ int iswm_gap_fwd_pl(const void* x, int64_t x_ps, int N, int HW, int C, int ldx, 
 int iswm_bcast_fwd_pl(const float* v, int N, int HW, int C, void* y, int ldy, int64_t y_ps, iswm_stream_t stream);
 int iswm_bilinear_fwd_pl(const float* x, int N, int Hi, int Wi, int C, int ldx, void* y, int64_t y_ps, int Ho, int Wo,
                          int ldy, iswm_stream_t stream);
-/* diagnostics: per-stage shader-clock stamps of workgroup 0 of the planes conv kernels into a device buffer of >= 512 uint64
- * (NULL = off, the default; tools/pl2_timeline.py) */
-int iswm_set_debug_buffer(void* buf);
 /* second-generation planes kernels: (16*rbw) x 128 tiles, weights packed for the 16x16x32 MFMA (own packing) */
 size_t iswm_conv2d_pl2_weight_bytes(const iswm_conv_desc* d, int kind);
 int iswm_conv2d_pl2_pack_weights(const iswm_conv_desc* d, int kind, const float* w, void* packed, iswm_stream_t stream);

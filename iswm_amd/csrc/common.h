@@ -37,6 +37,17 @@ inline int stream_grid(int64_t work_items, int block) {
     return (int)g;
 }
 
+// compute units of the device current at the first call (256 on MI355X); thread-safe (function-local static)
+inline int device_cus() {
+    static const int ncu = [] {
+        int dev = 0, n = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
+        return n > 0 ? n : 256;
+    }();
+    return ncu;
+}
+
 // Blocks b and b+8 share an XCD (and its L2) under round-robin dispatch; give each
 // XCD a contiguous run of logical tile ids so neighbouring tiles hit one L2.
 // Bijective for any grid size.  Placement affects speed only, never results.

@@ -27,6 +27,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
+
 #include "conv_common.h"
 
 namespace iswm {
@@ -782,15 +784,20 @@ static WgradPlan plan_wgrad(const iswm_conv_desc* d, bool x6) {
 
 using namespace iswm;
 
-// 0: exact-fp32 MFMA (v_mfma_f32_32x32x2_f32);  1 (default): bf16x6 split on the bf16 matrix cores
-static int g_conv_math = -1;
+// 0: exact-fp32 MFMA (v_mfma_f32_32x32x2_f32);  1 (default): bf16x6 split on the bf16 matrix cores;  2: bf16.
+// -1 until the first read, which takes ISWM_CONV_MATH unless iswm_set_conv_math got there first.
+static std::atomic<int> g_conv_math{-1};
 static int conv_math() {
-    if (g_conv_math < 0) {
+    int m = g_conv_math.load();
+    if (m < 0) {
         const char* e = getenv("ISWM_CONV_MATH");
-        g_conv_math = (e && (!strcmp(e, "f32") || !strcmp(e, "0"))) ? 0
-                      : (e && (!strcmp(e, "bf16") || !strcmp(e, "2"))) ? 2 : 1;   // default: bf16x6
+        const int env = (e && (!strcmp(e, "f32") || !strcmp(e, "0"))) ? 0
+                        : (e && (!strcmp(e, "bf16") || !strcmp(e, "2"))) ? 2 : 1;   // default: bf16x6
+        int unset = -1;
+        g_conv_math.compare_exchange_strong(unset, env);      // a mode stored meanwhile by another thread stands
+        m = g_conv_math.load();
     }
-    return g_conv_math;
+    return m;
 }
 extern "C" int iswm_set_conv_math(int mode) {
     ISWM_REQUIRE(mode >= 0 && mode <= 2, "set_conv_math: mode must be 0 (f32), 1 (bf16x6) or 2 (bf16)");
@@ -801,14 +808,9 @@ extern "C" int iswm_get_conv_math(void) { return conv_math(); }
 // bf16 planes per operand of the packed / weight-gradient kernels under the current math: 3 (bf16x6) or 1 (bf16)
 static int math_planes() { return conv_math() == 2 ? 1 : 3; }
 
-// Halo-patch kernel applicability (stride-1 KxK, bf16x6, packed weights); ISWM_X6_PATCH=0 disables it.
-static int g_x6_patch = -1;
+// Halo-patch kernel applicability (stride-1 KxK, bf16x6, packed weights)
 static bool patch_plan(const iswm_conv_desc* d, bool dgrad, int* PH, int* PW) {
-    if (g_x6_patch < 0) {
-        const char* e = getenv("ISWM_X6_PATCH");
-        g_x6_patch = (e && e[0] == '0') ? 0 : 1;
-    }
-    if (!g_x6_patch || d->stride != 1 || d->KH * d->KW <= 1) return false;
+    if (d->stride != 1 || d->KH * d->KW <= 1) return false;
     return dgrad ? conv_patch_plan(d->H, d->W, d->KH, d->KW, d->dil, PH, PW)
                  : conv_patch_plan(d->Ho, d->Wo, d->KH, d->KW, d->dil, PH, PW);
 }
@@ -843,7 +845,7 @@ extern "C" int iswm_conv2d_kernel_name(const iswm_conv_desc* d, int kind, char* 
     ISWM_REQUIRE(d && buf && buflen > 0 && kind >= 0 && kind <= 7, "kernel_name: bad argument");
     if (kind == 7) {   // iswm_conv2d_wgrad_planes
         const int kk = wgrad_pl_kernel_kind(d);
-        snprintf(buf, buflen, kk == 2 ? "k_wgrad_pls<%d, 0, 4>" : kk == 1 ? "k_wgrad_plw<%d, false, 0>" : "k_wgrad_pl<%d>", math_planes());
+        snprintf(buf, buflen, kk == 2 ? "k_wgrad_pls<%d>" : kk == 1 ? "k_wgrad_plw<%d>" : "k_wgrad_pl<%d>", math_planes());
         return 0;
     }
     if (kind >= 5) {   // 5 / 6: iswm_conv2d_fwd_pl2 / iswm_conv2d_dgrad_pl2
@@ -852,8 +854,8 @@ extern "C" int iswm_conv2d_kernel_name(const iswm_conv_desc* d, int kind, char* 
         int rbw, wide;
         conv_pl2_plan(dg ? (int64_t)d->N * d->H * d->W : (int64_t)d->N * d->Ho * d->Wo, cols, pl2_K(d, dg), pl2_wide_ok(d, dg), &rbw, &wide);
         if (wide) snprintf(buf, buflen, "k_conv_pl2w<%d, %d, %s>", rbw, math_planes(), dg ? "true" : "false");
-        else if (cols <= 64) snprintf(buf, buflen, "k_conv_pl2<%d, 2, %d, %s, false, 0>", rbw / 2, math_planes(), dg ? "true" : "false");
-        else snprintf(buf, buflen, "k_conv_pl2<%d, 1, %d, %s, false, 0>", rbw, math_planes(), dg ? "true" : "false");
+        else if (cols <= 64) snprintf(buf, buflen, "k_conv_pl2<%d, 2, %d, %s>", rbw / 2, math_planes(), dg ? "true" : "false");
+        else snprintf(buf, buflen, "k_conv_pl2<%d, 1, %d, %s>", rbw, math_planes(), dg ? "true" : "false");
         return 0;
     }
     if (kind >= 3) {   // 3 / 4: iswm_conv2d_fwd_packed / iswm_conv2d_dgrad_packed
@@ -1131,14 +1133,6 @@ extern "C" int iswm_join_planes(const void* planes, int ldp, int64_t plane_strid
     return check_launch("join_planes");
 }
 
-namespace iswm { extern unsigned long long* g_conv_dbg; }
-/* diagnostics: a device buffer of >= 512 uint64 that workgroup 0 of the planes conv kernels fills with per-stage shader-clock
- * stamps (tools/pl2_timeline.py); NULL (the default) switches the stamps off */
-extern "C" int iswm_set_debug_buffer(void* buf) {
-    iswm::g_conv_dbg = reinterpret_cast<unsigned long long*>(buf);
-    return 0;
-}
-
 /* second-generation planes kernels (conv_mfma_pl2.hip): kind 0 forward, 1 data gradient */
 extern "C" size_t iswm_conv2d_pl2_weight_bytes(const iswm_conv_desc* d, int kind) {
     if (!d || conv_math() < 1 || (kind != 0 && kind != 1)) return 0;
@@ -1255,10 +1249,7 @@ extern "C" int iswm_conv2d_dgrad_pl2_bn(const iswm_conv_desc* d, const void* dyp
 
 extern "C" size_t iswm_conv2d_wgrad_workspace(const iswm_conv_desc* d) {
     if (!d) return 0;
-    if (conv_math() == 1 && stem_geometry(base_args(d))) {
-        const size_t stem = stem_wgrad_workspace(base_args(d));          // 0: the stem's own weight gradient is switched off
-        if (stem > 0) return stem;
-    }
+    if (conv_math() == 1 && stem_geometry(base_args(d))) return stem_wgrad_workspace(base_args(d));
     WgradPlan p = plan_wgrad(d, conv_math() >= 1);
     if (p.nsplit <= 1) return 0;
     return (size_t)p.nsplit * d->Cout * d->KH * d->KW * d->Cin * sizeof(float);

@@ -42,15 +42,14 @@ __device__ __forceinline__ f32x4 mfma16(uint4 a, uint4 b, f32x4 c) {
 }
 
 constexpr int PL2_RBWMAX = 10;     // tile height up to 160 rows
-
-unsigned long long* g_conv_dbg = nullptr;        // iswm_set_debug_buffer
+constexpr double PL2W_EFF = 0.85;   // time per MFMA of the 256-column tiles relative to the 128-column ones
 
 // a.x = plane 0 of the gathered operand (bf16), a.ldx = its pixel pitch in bf16 elements, a.xps = plane stride (bytes)
 // a.w = weights packed by k_pack_weights_pl2;  a.MT, a.NT tile counts;  a.psplit != 0: row-major rows for strided dgrad.
 // Tile = (16 * RBW * WM) rows x (128 / WM) columns; wave (wm, wn) owns rows [wm*16*RBW, +16*RBW) and columns 16*wn..+15.
 // PERSISTENT: the grid is min(tiles, CUs) workgroups; a workgroup walks tiles  it * gridDim + xcd_remap(blockIdx)  and its
 // stage pipeline runs across tile boundaries, so a tile's epilogue overlaps the DMA of the next tile's first stage.
-template <int RBW, int WM, int NP, bool DGRAD, bool DBG = false, int ABL = 0>
+template <int RBW, int WM, int NP, bool DGRAD>
 __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
     const int GC = DGRAD ? a.Cout : a.Cin;     // channels of the gathered operand (per tap)
     const int NC = DGRAD ? a.Cin : a.Cout;     // output columns
@@ -214,7 +213,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
         // fragments of row block i+1 are read while block i is multiplied; the scheduling fences keep hipcc from
         // hoisting all 2 * RBW * NP fragment reads of a stage to its top (216 VGPRs for RBW = 9)
         auto aload = [&](AFrag& f, int idx) __attribute__((always_inline)) {          // idx = half * RBW + rb
-            if (ABL & 8) return;                    // ablation: multiply whatever the registers hold
             const int half = idx / RBW, rb = idx - half * RBW;
             const unsigned char* p = smem + st * STAGE + (fbase ^ (half * 64)) + rb * 2048;
 #pragma unroll
@@ -251,13 +249,11 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
         }
         auto slot = [&](int sidx) __attribute__((always_inline)) {
             if (sidx < NB_SLOTS) {
-                if (!(ABL & 1)) bn.v[sidx / NP][sidx % NP] = wn_[sidx * 64];
+                bn.v[sidx / NP][sidx % NP] = wn_[sidx * 64];
             } else if (sidx < NSLOTS) {
                 const int i = (sidx - NB_SLOTS) / NP, pp = (sidx - NB_SLOTS) % NP;
-                if (!(ABL & 2)) {
-                    if (8 * i + 8 <= RG || wave + 8 * i < RG)
-                        glds16b(asrc[i] + pp * apl[i], lds_base + (st ^ 1) * STAGE + pp * PLANE + (wave + 8 * i) * 1024);
-                }
+                if (8 * i + 8 <= RG || wave + 8 * i < RG)
+                    glds16b(asrc[i] + pp * apl[i], lds_base + (st ^ 1) * STAGE + pp * PLANE + (wave + 8 * i) * 1024);
                 if (pp == NP - 1) aptr[i] += astep[i];          // this row group's pointer moves on to the stage after
             }
         };
@@ -265,12 +261,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
         // of a block's three reads behind the 4th MFMA of the previous block and waits for them (lgkmcnt(0)) two MFMAs
         // later -- 32 cycles of cover for a ~100-cycle LDS round trip, at every row block
         AFrag f[3];
-        if (ABL & 8) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) f[i].v[pl] = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
-        }
         aload(f[0], 0);
         if (2 * RBW > 1) aload(f[1], 1);
 #pragma unroll
@@ -518,12 +508,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
             epilogue(i_tile, i_m0, i_n0, true);
         }
     };
-    // diagnostic build: shader clock and 100 MHz reference clock at both ends of workgroup 0 -> the clock the chip actually
-    // held while this kernel ran (tools/pl2_timeline.py; the chip lowers it under matrix load, MI355X_MICROARCH.md 'DVFS')
-    if (DBG && a.dbg != nullptr && blockIdx.x == 0 && t == 0) {
-        a.dbg[500] = __builtin_amdgcn_s_memtime();
-        a.dbg[501] = __builtin_amdgcn_s_memrealtime();
-    }
     {
         BFrag bc, bn;
         bool have = next_in_tile();
@@ -539,53 +523,29 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
         int st = 0;
         // one step per stage: publish stage `st`, start the loads of the following stage (possibly of the next tile),
         // multiply stage `st`, and run the epilogue when it was the last stage of its tile
-        int dbg_n = 0;
-        // stamps exist only in the diagnostic instantiation (DBG): even as untaken branches they sit between the barrier
-        // and the first MFMA of every stage, where nothing overlaps them (tools/mfma_rate.hip)
-        const bool dbg = DBG && a.dbg != nullptr && blockIdx.x == 0 && (wave == 0 || wave == 4);
-        auto stamp = [&](int k) __attribute__((always_inline)) {
-            if constexpr (DBG) {
-                if (dbg && dbg_n < 40 && lane == 0) a.dbg[(wave ? 256 : 0) + dbg_n * 6 + k] = __builtin_amdgcn_s_memtime();
-            }
-        };
         while (have) {
-            stamp(0);
             __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): this wave's DMA pieces and weight fragments landed
-            stamp(1);
-            if (!(ABL & 4)) __builtin_amdgcn_s_barrier();                // ... everyone's did; the other stage buffer is free
+            __builtin_amdgcn_s_barrier();                // ... everyone's did; the other stage buffer is free
             asm volatile("" ::: "memory");
-            stamp(2);
             bool more = next_in_tile();
             const bool last = !more;                      // the stage in hand is the last of its tile
             if (last) more = next_tile_stage();
-            stamp(3);
             compute(st, bc, more, bn, more ? tap * (GC >> 5) + 2 * cc : 0);
-            stamp(4);
             if (last) {
                 epilogue(c_tile, c_m0, c_n0, false);
                 c_tile = i_tile; c_m0 = i_m0; c_n0 = i_n0;
             }
             st ^= 1;
             bc = bn;
-            stamp(5);
-            ++dbg_n;
             have = more;
         }
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): the idle loads of the last stage
-    if (DBG && a.dbg != nullptr && blockIdx.x == 0 && t == 0) {
-        a.dbg[502] = __builtin_amdgcn_s_memtime();
-        a.dbg[503] = __builtin_amdgcn_s_memrealtime();
-    }
 }
 
 // Tile height for a GEMM of M rows x cols columns on 256 CUs (one 128-column workgroup per CU at a time):
 // rbw 16-row blocks, chosen to minimise  rounds x (rows per tile + fixed per-tile cost in row equivalents).
 int conv_pl2_pick_rbw(int64_t M, int cols) {
-    if (const char* e = getenv("ISWM_PL2_RBW")) {
-        const int v = atoi(e);
-        if (v >= 8 && v <= PL2_RBWMAX && !(cols <= 64 && v == 9)) return v;      // 64-column tiles have no 9-block form
-    }
     const int64_t NT = cols <= 64 ? 1 : (cols + 127) / 128;
     int best = PL2_RBWMAX;
     double bestc = 1e300;
@@ -605,28 +565,17 @@ int conv_pl2_pick_rbw(int64_t M, int cols) {
 // Tile plan: height (rbw 16-row blocks) and width.  256-column tiles (k_conv_pl2w: two column blocks per wave, ~15 % less
 // time per MFMA) are taken where the tile count still covers the chip:  cost = rounds x (rows + fixed) x (2 x 0.85 if wide).
 void conv_pl2_plan(int64_t M, int cols, int K, bool wide_ok, int* rbw_out, int* wide_out) {
-    static int force = -2;
-    static double eff = 0.85;
-    if (force == -2) {
-        force = getenv("ISWM_PL2_WIDE") ? atoi(getenv("ISWM_PL2_WIDE")) : -1;        // 0: never, 1: wherever possible
-        if (const char* e = getenv("ISWM_PL2W_EFF")) eff = atof(e) > 0 ? atof(e) : eff;
-    }
     *rbw_out = conv_pl2_pick_rbw(M, cols);
     *wide_out = 0;
     // short K: a tile is a few stages and then an epilogue of twice the size -- measured slower below 4 stages (forward)
     // / 8 stages (data gradient, whose accumulating epilogue also reads) [profiles/r03_pl2w_ab.txt]
-    if (!wide_ok || cols < 256 || force == 0 || (force != 1 && K < 256)) return;
+    if (!wide_ok || cols < 256 || K < 256) return;
     const int64_t NT = (cols + 127) / 128, NTW = (cols + 255) / 256;
-    double best = 1e300;
-    {
-        const int rbw = *rbw_out;
-        const int64_t MT = (M + rbw * 16 - 1) / (rbw * 16);
-        best = (double)((MT * NT + 255) / 256) * (rbw * 16 + 24.0);
-        if (force == 1) best = 1e300;
-    }
+    const int64_t MT0 = (M + *rbw_out * 16 - 1) / (*rbw_out * 16);
+    double best = (double)((MT0 * NT + 255) / 256) * (*rbw_out * 16 + 24.0);
     for (int rbw = 8; rbw <= PL2_RBWMAX; ++rbw) {
         const int64_t MT = (M + rbw * 16 - 1) / (rbw * 16);
-        const double c = (double)((MT * NTW + 255) / 256) * (rbw * 16 + 24.0) * 2.0 * eff;
+        const double c = (double)((MT * NTW + 255) / 256) * (rbw * 16 + 24.0) * 2.0 * PL2W_EFF;
         if (c < best - 1e-9) {
             best = c;
             *rbw_out = rbw;
@@ -637,17 +586,7 @@ void conv_pl2_plan(int64_t M, int cols, int K, bool wide_ok, int* rbw_out, int* 
 
 // rbw = 16-row blocks per tile (8..10 instantiated for 128-column tiles; 2 x 4/5 for 64-column tiles)
 bool launch_conv_pl2(ConvArgs a, hipStream_t s, bool dgrad, int planes, int rbw) {
-    static int parity = -1, ncu = 0;
-    if (parity < 0) {
-        const char* e = getenv("ISWM_X6_PARITY");
-        parity = (e && e[0] == '0') ? 0 : 1;
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-        if (ncu <= 0) ncu = 256;
-        if (const char* g = getenv("ISWM_PL2_GRID")) ncu = atoi(g) > 0 ? atoi(g) : ncu;
-    }
-    a.psplit = parity ? 0 : 1;
+    a.psplit = 0;           // strided data gradient: parity-sorted rows
     {   // quarters of the parity-sorted rows, heaviest first (class k = 2 * (row parity) + column parity)
         int wgt[4], ord[4] = {0, 1, 2, 3};
         for (int k = 0; k < 4; ++k) {
@@ -661,15 +600,11 @@ bool launch_conv_pl2(ConvArgs a, hipStream_t s, bool dgrad, int planes, int rbw)
                 if (wgt[ord[j]] > wgt[ord[i]]) { const int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
         a.porder = ord[0] | (ord[1] << 2) | (ord[2] << 4) | (ord[3] << 6);
     }
-    a.dbg = g_conv_dbg;
-    static int abl = -1;
-    if (abl < 0) abl = getenv("ISWM_PL2_ABL") ? atoi(getenv("ISWM_PL2_ABL")) : 0;
-    a.abl = abl;
     const int nc = dgrad ? a.Cin : a.Cout;
     const bool narrow = nc <= 64;
     a.MT = (a.M + rbw * 16 - 1) / (rbw * 16);
     a.NT = narrow ? 1 : (nc + 127) / 128;
-    const int tiles = a.MT * a.NT;
+    const int tiles = a.MT * a.NT, ncu = device_cus();
     dim3 grid(tiles < ncu ? tiles : ncu), blk(512);
     if (planes == 1) {          // ONE bf16 plane per operand (conv math "bf16": activations stored rounded, one MFMA per product)
 #define PL2_LAUNCH1(R, W)                                                                      \
@@ -702,23 +637,7 @@ bool launch_conv_pl2(ConvArgs a, hipStream_t s, bool dgrad, int planes, int rbw)
         else return false;
     } else {
         if (rbw == 8) PL2_LAUNCH(8, 1);
-        else if (rbw == 9 && a.abl != 0) {               // ISWM_PL2_ABL: timing ablations are compile-time variants
-#define PL2_ABL_LAUNCH(A)                                                                                        \
-    do {                                                                                                         \
-        if (dgrad) hipLaunchKernelGGL((k_conv_pl2<9, 1, 3, true, false, A>), grid, blk, 0, s, a);                 \
-        else hipLaunchKernelGGL((k_conv_pl2<9, 1, 3, false, false, A>), grid, blk, 0, s, a);                      \
-    } while (0)
-            if (a.abl == 1) PL2_ABL_LAUNCH(1);
-            else if (a.abl == 2) PL2_ABL_LAUNCH(2);
-            else if (a.abl == 3) PL2_ABL_LAUNCH(3);
-            else if (a.abl == 7) PL2_ABL_LAUNCH(7);
-            else if (a.abl == 15) PL2_ABL_LAUNCH(15);
-            else return false;
-#undef PL2_ABL_LAUNCH
-        } else if (rbw == 9 && a.dbg != nullptr) {          // iswm_set_debug_buffer: the stamped instantiation
-            if (dgrad) hipLaunchKernelGGL((k_conv_pl2<9, 1, 3, true, true>), grid, blk, 0, s, a);
-            else hipLaunchKernelGGL((k_conv_pl2<9, 1, 3, false, true>), grid, blk, 0, s, a);
-        } else if (rbw == 9) PL2_LAUNCH(9, 1);
+        else if (rbw == 9) PL2_LAUNCH(9, 1);
         else if (rbw == 10) PL2_LAUNCH(10, 1);
         else return false;
     }

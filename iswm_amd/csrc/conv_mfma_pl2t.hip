@@ -521,17 +521,6 @@ static int aspp_build_plan(const iswm_conv_desc* d, int nbranch, const int* ksiz
     return 0;
 }
 
-static int device_cus() {
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-        if (ncu <= 0) ncu = 256;
-    }
-    return ncu;
-}
-
 }  // namespace iswm
 
 using namespace iswm;

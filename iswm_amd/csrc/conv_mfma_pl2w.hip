@@ -476,19 +476,12 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
 
 // launch the 256-column kernel; rbw in {8, 9, 10}.  Returns false when there is no instantiation.
 bool launch_conv_pl2w(ConvArgs a, hipStream_t s, bool dgrad, int planes, int rbw) {
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-        if (ncu <= 0) ncu = 256;
-    }
     if (planes != 3 || (dgrad && a.stride != 1)) return false;
     const int nc = dgrad ? a.Cin : a.Cout;
     a.MT = (a.M + rbw * 16 - 1) / (rbw * 16);
     a.NT = (nc + 255) / 256;
     a.psplit = 1;
-    const int tiles = a.MT * a.NT;
+    const int tiles = a.MT * a.NT, ncu = device_cus();
     dim3 grid(tiles < ncu ? tiles : ncu), blk(512);
 #define PL2W_LAUNCH(R)                                                                     \
     do {                                                                                   \

@@ -401,14 +401,6 @@ struct TilePick {
 };
 
 static TilePick pick_tile(int64_t M, int cols) {
-    if (const char* e = getenv("ISWM_TILE")) {          // tuning override: "128x128" | "128x64" | "64x64"
-        int bm = 0, bn = 0;
-        if (sscanf(e, "%dx%d", &bm, &bn) == 2 && (bm == 128 || bm == 64) && (bn == 128 || bn == 64) &&
-            !(bm == 64 && bn == 128)) {
-            if (bn == 128 && (cols <= 64 || (cols % 128 != 0 && cols % 128 <= 64))) bn = 64;
-            return TilePick{bm, bn};
-        }
-    }
     struct Cand {
         int bm, bn;
         double eff;

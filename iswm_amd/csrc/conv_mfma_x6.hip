@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256, (BM == 128 && BN == 128) ? 2 : (BM == 128 ? 3 
     // row -> pixel of the tensor the rows live in (fwd: output Ho x Wo; dgrad: input H x W)
     const int RH = DGRAD ? a.H : a.Ho, RW = DGRAD ? a.W : a.Wo;
     const int GH = DGRAD ? a.Ho : a.H, GW = DGRAD ? a.Wo : a.W;     // gathered tensor dims
-    const bool par = DGRAD && a.stride == 2 && a.nsplit == 0;     // a.nsplit != 0: tuning switch, row-major rows
+    const bool par = DGRAD && a.stride == 2 && a.nsplit == 0;     // a.nsplit != 0: row-major rows
     __shared__ int rowpix[DGRAD ? BM : 1];       // parity order: output pixel of each tile row
     if (DGRAD && par && t < BM) {
         const int m = m0 + t;
@@ -340,14 +340,6 @@ __global__ __launch_bounds__(256, (BM == 128 && BN == 128) ? 2 : (BM == 128 ? 3 
 // 128x64 tiles to give every CU three, and for write-dominated 1x1 data gradients (small K, wide
 // output); 128x128 (2 blocks per CU) only pays for very large M.
 void conv_pick_tile_x6(int64_t M, int cols, int K, bool dgrad, bool pointwise, int* bm, int* bn) {
-    if (const char* e = getenv("ISWM_TILE")) {          // tuning override: "128x128" | "128x64" | "64x64"
-        int m = 0, n = 0;
-        if (sscanf(e, "%dx%d", &m, &n) == 2 && (m == 128 || m == 64) && (n == 128 || n == 64) && !(m == 64 && n == 128)) {
-            if (n == 128 && (cols <= 64 || (cols % 128 != 0 && cols % 128 <= 64))) n = 64;
-            *bm = m; *bn = n;
-            return;
-        }
-    }
     const int64_t mt128 = (M + 127) / 128;
     const int64_t tiles64 = mt128 * ((cols + 63) / 64);
     if (tiles64 < 384 || (dgrad && pointwise && 2 * K <= cols)) {
@@ -372,12 +364,7 @@ bool launch_conv_fwd_x6(ConvArgs a, hipStream_t s, int bm, int bn) {
 
 // packed-weight ("B direct") launchers: a.w = k_pack_weights_x6 output.  Tiles: 128x64 or 64x64.
 bool launch_conv_x6_pk(ConvArgs a, hipStream_t s, bool dgrad, int bm, int planes) {
-    static int parity = -1;
-    if (parity < 0) {
-        const char* e = getenv("ISWM_X6_PARITY");
-        parity = (e && e[0] == '0') ? 0 : 1;
-    }
-    a.nsplit = parity ? 0 : 1;
+    a.nsplit = 0;           // strided data gradient: parity-sorted rows
     const int nc = dgrad ? a.Cin : a.Cout;
     a.MT = (a.M + bm - 1) / bm;
     a.NT = (nc + 63) / 64;

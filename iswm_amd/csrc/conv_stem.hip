@@ -364,9 +364,7 @@ __global__ __launch_bounds__(256) void k_stem_wgrad_reduce(const float* __restri
 
 // the geometry this file covers (conv math bf16x6 only: the exact-fp32 mode keeps the fp32 MFMA kernels)
 bool stem_geometry(const ConvArgs& a) {
-    static int on = -1;
-    if (on < 0) on = (getenv("ISWM_STEM") && getenv("ISWM_STEM")[0] == '0') ? 0 : 1;       // tuning switch: 0 = the generic kernels
-    return on && a.Cin == 4 && a.Cout == 64 && a.KH == 7 && a.KW == 7 && a.stride == 2 && a.pad == 3 && a.dil == 1 && a.ldx == 4 &&
+    return a.Cin == 4 && a.Cout == 64 && a.KH == 7 && a.KW == 7 && a.stride == 2 && a.pad == 3 && a.dil == 1 && a.ldx == 4 &&
            a.ldy % 4 == 0 && a.ldy >= 64 && (long long)a.N * a.H * a.W < (1ll << 29) && a.Ho == (a.H - 1) / 2 + 1 &&
            a.Wo == (a.W - 1) / 2 + 1 && a.Wo > 16;
 }
@@ -374,28 +372,15 @@ bool stem_geometry(const ConvArgs& a) {
 int stem_tile_rows() { return STEM_TILE; }
 
 bool launch_stem_fwd(ConvArgs a, hipStream_t s) {
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-        if (ncu <= 0) ncu = 256;
-    }
     if (!stem_geometry(a)) return false;
     a.MT = (a.M + STEM_TILE - 1) / STEM_TILE;
-    const int wgs = (a.MT + 7) / 8;
+    const int wgs = (a.MT + 7) / 8, ncu = device_cus();
     hipLaunchKernelGGL((k_stem_fwd<STEM_RB>), dim3(wgs < ncu ? wgs : ncu), dim3(512), 0, s, a);
     return true;
 }
 
 static int stem_wgrad_grid(const ConvArgs& a, int* per) {
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-        if (ncu <= 0) ncu = 256;
-    }
+    const int ncu = device_cus();
     const long long M = (long long)a.N * a.Ho * a.Wo;
     int grid = (int)((M + SW_KS - 1) / SW_KS < ncu ? (M + SW_KS - 1) / SW_KS : ncu);
     if (grid < 1) grid = 1;
@@ -403,21 +388,14 @@ static int stem_wgrad_grid(const ConvArgs& a, int* per) {
     return (int)((M + *per - 1) / *per);
 }
 
-static bool stem_wgrad_on() {
-    static int on = -1;
-    if (on < 0) on = (getenv("ISWM_STEM_WG") && getenv("ISWM_STEM_WG")[0] == '0') ? 0 : 1;      // tuning switch
-    return on != 0;
-}
-
 size_t stem_wgrad_workspace(const ConvArgs& a) {
-    if (!stem_wgrad_on()) return 0;          // 0: the generic weight gradient runs (and sizes its own workspace)
     int per;
     return (size_t)stem_wgrad_grid(a, &per) * 64 * 224 * sizeof(float);
 }
 
 // a.x: NHWC4 fp32 image, a.y: dy [M][ldy] fp32; dw: OHWI [64][7][7][4]; workspace >= stem_wgrad_workspace
 bool launch_stem_wgrad(ConvArgs a, float* dw, float* workspace, hipStream_t s) {
-    if (!stem_geometry(a) || !stem_wgrad_on()) return false;
+    if (!stem_geometry(a)) return false;
     int per;
     const int grid = stem_wgrad_grid(a, &per);
     a.M = a.N * a.Ho * a.Wo;

@@ -20,8 +20,6 @@
 
 namespace iswm {
 
-extern unsigned long long* g_conv_dbg;
-
 static __device__ __attribute__((aligned(256))) unsigned short g_zero_row_wg[128];   // 256 B of zeros
 
 typedef __attribute__((address_space(3))) void* lds_vptr3;
@@ -39,9 +37,7 @@ struct WgArgs {
     long long dyps, xps;        // plane strides in BYTES
     int N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, dil, ldx, ldy;
     int P, Ktot, MT, NT, nsplit, psplit;
-    int abl;                    // timing ablations (ISWM_WG_ABL): 1 no DMA, 2 no multiply
     int always;                 // 1: every gathered pixel is in bounds (1x1 stride-1 pad-0): no per-step culling vote
-    unsigned long long* dbg;    // iswm_set_debug_buffer: per-step shader-clock stamps of workgroup 0 (tools/wgrad_timeline.py)
     int vote;                   // 1: skip 32-pixel steps whose gathered pixels are ALL padding (workgroup-wide vote, one more
                                 // barrier per step: only worth it when the filter reaches far -- ASPP rates)
     // k_wgrad_pls, deep padding: every 256-column tile lies inside ONE filter tap (Cin % 256 == 0), and a tap (dh, dw) only
@@ -150,7 +146,6 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pl(const WgArgs a) {
         }
     };
     auto issue = [&](int st) __attribute__((always_inline)) {
-        if (a.abl & 1) return;
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl) glds16w(asrc + pl * apst, lds_base + st * STAGE + pl * PLANE + wave * 1024);
 #pragma unroll
@@ -236,7 +231,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pl(const WgArgs a) {
             __builtin_amdgcn_s_barrier();        // everyone's pieces landed; the buffer multiplied last time is free
             asm volatile("" ::: "memory");
             if (advance()) post();
-            if (!(a.abl & 2)) compute(rd);
+            compute(rd);
             rd = rd == NST - 1 ? 0 : rd + 1;
             --nissued;
         }
@@ -279,10 +274,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pl(const WgArgs a) {
 // and fetches 72 KB for it (23 B/clk at full matrix rate instead of 31; a single workgroup per CU is fed ~30 B/clk,
 // profiles/r02_ta_bw.txt).  Eight waves as 2 x 4, each a 64 x 64 block over the whole step: no k-half split, so no LDS
 // combine at the end.  Two stage buffers of [A | B0 | B1] images (144 KB).
-// DBG: per-step stamps and the in-kernel clock (tools/wgrad_timeline.py); ABL: timing ablations (1 no DMA, 2 no multiply).
-// Both are compile-time: an untaken scalar branch between the barrier and the first MFMA of a step is not free
-// (tools/mfma_rate.hip), and the production instantiation carries none of them.
-template <int NP, bool DBG = false, int ABL = 0>
+template <int NP>
 __global__ __launch_bounds__(512, 2) void k_wgrad_plw(const WgArgs a) {
     constexpr int PLANE = 32 * 256;            // bytes of one plane of one 128-channel image of one stage
     constexpr int IMG = NP * PLANE;
@@ -393,7 +385,6 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_plw(const WgArgs a) {
         else glds16w(bsrc[img - 1] + pl * bpst[img - 1], dst);
     };
     auto issue = [&](int st) __attribute__((always_inline)) {
-        if (ABL & 1) return;
 #pragma unroll
         for (int i = 0; i < 3 * NP; ++i) dma(i, st);
     };
@@ -463,42 +454,20 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_plw(const WgArgs a) {
 #undef ISWM_SB
     };
 
-    if (DBG && a.dbg != nullptr && blockIdx.x == 0 && t == 0) {          // in-kernel clock
-        a.dbg[500] = __builtin_amdgcn_s_memtime();
-        a.dbg[501] = __builtin_amdgcn_s_memrealtime();
-    }
     {
-        int dbg_n = 0;
-        const bool dbg = DBG && a.dbg != nullptr && blockIdx.x == 0 && (wave == 0 || wave == 4);
-        auto stamp = [&](int k) __attribute__((always_inline)) {
-            if constexpr (DBG) {
-                if (dbg && dbg_n < 40 && lane == 0) a.dbg[(wave ? 256 : 0) + dbg_n * 6 + k] = __builtin_amdgcn_s_memtime();
-            }
-        };
         bool have = next();
         if (have) issue(0);
         int st = 0;
         while (have) {
-            stamp(0);
             __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): this wave's pieces of the step have landed
-            stamp(1);
             __builtin_amdgcn_s_barrier();            // everyone's have; the other buffer is free again
             asm volatile("" ::: "memory");
-            stamp(2);
             const bool more = next();
             if (more) issue(st ^ 1);
-            stamp(3);
-            if (!(ABL & 2)) compute(st);
-            stamp(4);
+            compute(st);
             st ^= 1;
             have = more;
-            ++dbg_n;
         }
-        stamp(0);
-    }
-    if (DBG && a.dbg != nullptr && blockIdx.x == 0 && t == 0) {
-        a.dbg[502] = __builtin_amdgcn_s_memtime();
-        a.dbg[503] = __builtin_amdgcn_s_memrealtime();
     }
 
     if (a.nsplit > 1) {
@@ -545,9 +514,9 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_plw(const WgArgs a) {
 // the gaps; between two barriers a multiplier executes nothing but reads and MFMAs.
 // Stages whose gathered pixels are all padding are not skipped (no workgroup-wide vote: it would put the multipliers back
 // in the loaders' lockstep) -- the deep-padding ASPP shapes stay on k_wgrad_plw.
-// MW: multiplier waves -- 4 (one per SIMD, 64 x 128 each) or 8 (two per SIMD, 64 x 64 each; 12 waves per workgroup)
-template <int NP, int ABL = 0, int MW = 4>
-__global__ __launch_bounds__(64 * (MW + 4), (MW + 4) / 4) void k_wgrad_pls(const WgArgs a) {
+template <int NP>
+__global__ __launch_bounds__(512, 2) void k_wgrad_pls(const WgArgs a) {
+    constexpr int MW = 4;                      // multiplier waves
     constexpr int KS = 16;                     // pixels per stage
     constexpr int PLANE = KS * 256;            // bytes of one plane of one 128-channel image of one stage
     constexpr int IMG = NP * PLANE;
@@ -670,7 +639,6 @@ __global__ __launch_bounds__(64 * (MW + 4), (MW + 4) / 4) void k_wgrad_pls(const
                     bpst[i] = v ? a.xps : 0;
                 }
                 const unsigned dstr = lds_base + (kc & 3) * STAGE + rg * 1024;
-                if constexpr (ABL & 1) return;
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) glds16w(asrc + pl * apst, dstr + pl * PLANE);
 #pragma unroll
@@ -714,7 +682,6 @@ __global__ __launch_bounds__(64 * (MW + 4), (MW + 4) / 4) void k_wgrad_pls(const
                 }
             }
             const unsigned dst = lds_base + (kc & 3) * STAGE + rg * 1024;
-            if constexpr (ABL & 1) return;              // timing ablation: no DMA
 #pragma unroll
             for (int pl = 0; pl < NP; ++pl) glds16w(asrc + pl * apst, dst + pl * PLANE);
 #pragma unroll
@@ -744,9 +711,9 @@ __global__ __launch_bounds__(64 * (MW + 4), (MW + 4) / 4) void k_wgrad_pls(const
     }
 
     // ================= multiplier =================
-    constexpr int NBW = MW == 4 ? 4 : 2;               // 32-column blocks per multiplier
-    const int wm = MW == 4 ? wave >> 1 : wave >> 2;    // rows 64 wm ..
-    const int wn4 = MW == 4 ? 2 * (wave & 1) : (wave & 3);        // first 64-column group of this wave (of 4)
+    constexpr int NBW = 4;                             // 32-column blocks per multiplier
+    const int wm = wave >> 1;                          // rows 64 wm ..
+    const int wn4 = 2 * (wave & 1);                    // first 64-column group of this wave (of 4)
     const int tg = lane >> 4, ti = lane & 15, tq = ti >> 2, tp = ti & 3;
     const int th = tg >> 1, tc = (tg & 1) * 16 + tp * 4;
     typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -778,11 +745,6 @@ __global__ __launch_bounds__(64 * (MW + 4), (MW + 4) / 4) void k_wgrad_pls(const
     };
     auto mm = [&](int mb, int nb) __attribute__((always_inline)) {
         f32x16 c = acc[mb][nb];
-        if constexpr (ABL & 2) {                        // timing ablation: one MFMA per block instead of six
-            c = mfma_bf16(FA[mb][0] ^ FA[mb][1] ^ FA[mb][2], FB[nb][0] ^ FB[nb][1] ^ FB[nb][2], c);
-            acc[mb][nb] = c;
-            return;
-        }
         if constexpr (NP == 3) {
             c = mfma_bf16(FA[mb][2], FB[nb][0], c);     // smallest terms first
             c = mfma_bf16(FA[mb][0], FB[nb][2], c);
@@ -800,21 +762,14 @@ __global__ __launch_bounds__(64 * (MW + 4), (MW + 4) / 4) void k_wgrad_pls(const
         const int slot = s2 & 3;
         // blocks of 6 MFMAs; every fragment group is read one block before the block that needs it
         ldA(slot, 0); ldB(slot, 0);
-        if constexpr (NBW == 4) {
-            ISWM_SB(); ldB(slot, 1); ISWM_SB(); mm(0, 0); ISWM_SB();
-            ISWM_SB(); ldB(slot, 2); ISWM_SB(); mm(0, 1); ISWM_SB();
-            ISWM_SB(); ldB(slot, 3); ISWM_SB(); mm(0, 2); ISWM_SB();
-            ISWM_SB(); ldA(slot, 1); ISWM_SB(); mm(0, 3); ISWM_SB();
-            ISWM_SB(); mm(1, 3); ISWM_SB();
-            ISWM_SB(); mm(1, 2); ISWM_SB();
-            ISWM_SB(); mm(1, 1); ISWM_SB();
-            ISWM_SB(); mm(1, 0); ISWM_SB();
-        } else {
-            ISWM_SB(); ldB(slot, 1); ISWM_SB(); mm(0, 0); ISWM_SB();
-            ISWM_SB(); ldA(slot, 1); ISWM_SB(); mm(0, 1); ISWM_SB();
-            ISWM_SB(); mm(1, 1); ISWM_SB();
-            ISWM_SB(); mm(1, 0); ISWM_SB();
-        }
+        ISWM_SB(); ldB(slot, 1); ISWM_SB(); mm(0, 0); ISWM_SB();
+        ISWM_SB(); ldB(slot, 2); ISWM_SB(); mm(0, 1); ISWM_SB();
+        ISWM_SB(); ldB(slot, 3); ISWM_SB(); mm(0, 2); ISWM_SB();
+        ISWM_SB(); ldA(slot, 1); ISWM_SB(); mm(0, 3); ISWM_SB();
+        ISWM_SB(); mm(1, 3); ISWM_SB();
+        ISWM_SB(); mm(1, 2); ISWM_SB();
+        ISWM_SB(); mm(1, 1); ISWM_SB();
+        ISWM_SB(); mm(1, 0); ISWM_SB();
         // all reads of the stage were waited for by the MFMAs that consumed them: the next barrier may free its buffer
     }
 #undef ISWM_SB
@@ -889,9 +844,6 @@ __global__ __launch_bounds__(256) void k_reduce_slabs_frag(const float4* __restr
 
 // tile width along the (tap, ci) axis: 256 when that wastes little
 static int wgrad_pl_wide(int Ktot, int taps, int64_t P) {
-    static int force = -2;
-    if (force == -2) force = getenv("ISWM_WG_WIDE") ? atoi(getenv("ISWM_WG_WIDE")) : -1;
-    if (force >= 0) return force && Ktot > 128;
     if (Ktot <= 128) return 0;
     // the slabs of a launch are ~256 workgroups x one tile whatever the shape: 32 MB instead of 16 MB.  K x K filters and
     // the 33 x 33 maps have the work per launch to pay for that (measured 1.05-1.4x); a 1 x 1 on a large map splits
@@ -914,15 +866,6 @@ void plan_wgrad_pl(int Cout, int Ktot, int taps, int64_t P, int* nsplit, int* ps
     const double slab_us = (double)Cout * Ktot * 8.0 / 4.0e6;     // one slab written + read at ~4 TB/s
     int64_t maxs = (P + 255) / 256;
     if (maxs > 256) maxs = 256;
-    if (const char* e = getenv("ISWM_WGPL_SPLIT")) {
-        const int64_t v = atoi(e);
-        if (v >= 1 && v <= maxs) {
-            const int64_t ps = ((P + v - 1) / v + 31) / 32 * 32;
-            *psplit = (int)ps;
-            *nsplit = (int)((P + ps - 1) / ps);
-            return;
-        }
-    }
     double best = 1e300;
     *psplit = (int)((P + 31) / 32 * 32);
     *nsplit = 1;
@@ -941,26 +884,11 @@ void plan_wgrad_pl(int Cout, int Ktot, int taps, int64_t P, int* nsplit, int* ps
 
 void launch_wgrad_pl(const WgArgs& a, int planes, int wide, hipStream_t s) {
     dim3 grid(a.MT * a.NT * a.nsplit), blk(512);
-    static int spec = -1;
-    if (spec < 0) spec = getenv("ISWM_WG_SPEC") ? atoi(getenv("ISWM_WG_SPEC")) : 1;
-    if (wide && spec && !a.vote && a.abl == 0 && a.dbg == nullptr) {
-        static int sabl = -1;
-        if (sabl < 0) sabl = getenv("ISWM_WGS_ABL") ? atoi(getenv("ISWM_WGS_ABL")) : 0;
+    if (wide && !a.vote) {
         if (planes == 1) hipLaunchKernelGGL(k_wgrad_pls<1>, grid, blk, 0, s, a);
-        else if (sabl == 1) hipLaunchKernelGGL((k_wgrad_pls<3, 1>), grid, blk, 0, s, a);
-        else if (sabl == 2) hipLaunchKernelGGL((k_wgrad_pls<3, 2>), grid, blk, 0, s, a);
-        else if (sabl == 3) hipLaunchKernelGGL((k_wgrad_pls<3, 3>), grid, blk, 0, s, a);
-        else if (sabl == 8) hipLaunchKernelGGL((k_wgrad_pls<3, 0, 8>), grid, dim3(768), 0, s, a);
-        else if (sabl == 9) hipLaunchKernelGGL((k_wgrad_pls<3, 1, 8>), grid, dim3(768), 0, s, a);
         else hipLaunchKernelGGL(k_wgrad_pls<3>, grid, blk, 0, s, a);
-        return;
-    }
-    if (wide) {
+    } else if (wide) {
         if (planes == 1) hipLaunchKernelGGL(k_wgrad_plw<1>, grid, blk, 0, s, a);
-        else if (a.abl == 1) hipLaunchKernelGGL((k_wgrad_plw<3, false, 1>), grid, blk, 0, s, a);
-        else if (a.abl == 2) hipLaunchKernelGGL((k_wgrad_plw<3, false, 2>), grid, blk, 0, s, a);
-        else if (a.abl == 3) hipLaunchKernelGGL((k_wgrad_plw<3, false, 3>), grid, blk, 0, s, a);
-        else if (a.dbg != nullptr) hipLaunchKernelGGL((k_wgrad_plw<3, true, 0>), grid, blk, 0, s, a);
         else hipLaunchKernelGGL(k_wgrad_plw<3>, grid, blk, 0, s, a);
     } else {
         if (planes == 1) hipLaunchKernelGGL(k_wgrad_pl<1>, grid, blk, 0, s, a);
@@ -1006,10 +934,8 @@ extern "C" int iswm_conv2d_wgrad_planes_ok(const iswm_conv_desc* d) {
 // Tap-rectangle mode of k_wgrad_pls (WgArgs::rect): deep padding, stride 1, whole taps per 256-column tile.  Returns the mean
 // number of pixels a tile walks (what the split planner balances) and fills the taps by descending rectangle size.
 static bool wgrad_rect_mode(const iswm_conv_desc* d, int64_t* p_eff, unsigned char* order, bool* similar = nullptr) {
-    static int on = -1;
-    if (on < 0) on = getenv("ISWM_WG_RECT") ? atoi(getenv("ISWM_WG_RECT")) : 1;
     const int taps = d->KH * d->KW;
-    if (!on || d->pad < 4 || d->stride != 1 || d->Cin % 256 != 0 || taps <= 1 || taps > 32 || iswm_get_conv_math() != 1) return false;
+    if (d->pad < 4 || d->stride != 1 || d->Cin % 256 != 0 || taps <= 1 || taps > 32 || iswm_get_conv_math() != 1) return false;
     int64_t area[32], sum = 0;
     for (int t = 0; t < taps; ++t) {
         const int dh = (t / d->KW) * d->dil - d->pad, dw = (t % d->KW) * d->dil - d->pad;
@@ -1041,11 +967,9 @@ static bool wgrad_rect_mode(const iswm_conv_desc* d, int64_t* p_eff, unsigned ch
 namespace iswm {
 int wgrad_pl_kernel_kind(const iswm_conv_desc* d) {
     if (!wgrad_pl_is_wide(d)) return 0;
-    static int spec = -1;
-    if (spec < 0) spec = getenv("ISWM_WG_SPEC") ? atoi(getenv("ISWM_WG_SPEC")) : 1;
     const bool rect = wgrad_rect_mode(d, nullptr, nullptr);
     const bool vote = d->pad >= 4 && !rect;
-    return (spec && !vote) ? 2 : 1;
+    return vote ? 1 : 2;
 }
 }  // namespace iswm
 
@@ -1085,21 +1009,11 @@ extern "C" int iswm_conv2d_wgrad_planes(const iswm_conv_desc* d, const void* xp,
         // one column block per XCD (k_wgrad_pls) where the taps walk their rectangles at a similar pace (rates 6 and 12 on the
         // 33 x 33 map: fabric fetch -43 % / -27 %, kernel -4.6 % / -2.2 %; at rate 18 the corner taps are a fifth of the centre
         // tap, the XCD's taps drift apart by images and the order only unbalances the rounds: +3 %) -- profiles/r03_rect_xcd.txt
-        static int rx = -2;
-        if (rx == -2) rx = getenv("ISWM_WG_RECT_XCD") ? atoi(getenv("ISWM_WG_RECT_XCD")) : -1;    // tuning switch: 0 never, 1 always
-        if (a.rect && (d->Cin >> 8) == 8 && (rx == 1 || (rx < 0 && similar))) a.rect = 2;
+        if (a.rect && (d->Cin >> 8) == 8 && similar) a.rect = 2;
     }
     plan_wgrad_pl(d->Cout, a.Ktot, d->KH * d->KW, p_plan, &a.nsplit, &a.psplit);
-    static int abl = -1;
-    if (abl < 0) abl = getenv("ISWM_WG_ABL") ? atoi(getenv("ISWM_WG_ABL")) : 0;
-    a.abl = abl;
-    a.dbg = g_conv_dbg;
-    {
-        static int fv = -2;
-        if (fv == -2) fv = getenv("ISWM_WG_VOTE") ? atoi(getenv("ISWM_WG_VOTE")) : -1;
-        a.vote = fv >= 0 ? fv : (d->pad >= 4 ? 1 : 0);
-        if (a.rect) a.vote = 0;                       // nothing to vote on: the tile walks in-bounds pixels only
-    }
+    // rect: nothing to vote on, the tile walks in-bounds pixels only
+    a.vote = (d->pad >= 4 && !a.rect) ? 1 : 0;
     a.always = (d->KH == 1 && d->KW == 1 && d->pad == 0 && d->stride == 1) ? 1 : 0;
     const size_t need = iswm_conv2d_wgrad_planes_workspace(d);
     ISWM_REQUIRE(workspace_bytes >= need && (need == 0 || (workspace && aligned16(workspace))),

@@ -13,7 +13,6 @@ and the whole model is ONE node in torch's autograd graph (``_Bridge``), so
 ``loss.backward()`` / ``optimizer.step()`` in train.py work unchanged while no
 torch op ever touches an activation.  All compute is libiswm_hip.so kernels.
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -386,7 +385,7 @@ def _cba_finish(conv, bn, relu, x, y, g, partials, tiles, training, save, residu
     return o, ctx
 
 
-_BN3_FUSE = os.environ.get("ISWM_BN3_FUSE", "1") != "0"      # tuning switch: 0 = residual stages reduce themselves
+_BN3_FUSE = True      # False: residual stages reduce themselves (tests compare both paths)
 
 
 def _bn_stats_request(up):
@@ -394,7 +393,7 @@ def _bn_stats_request(up):
     stage returns: the planes data gradient then takes that backward's reduction pass in its epilogue (ops.BnStats)."""
     if up is None or not ops.planes_on() or up.get("bn_stats") is not None:
         return None
-    if ops._relu_code(up["relu"]) not in (0, 1) or not ops._BN_MASK_FROM_Y:
+    if ops._relu_code(up["relu"]) not in (0, 1):
         return None
     if up.get("res"):
         # a residual stage (bn3 + identity + ReLU): the pattern is read from its saved output planes and the data gradient
@@ -476,9 +475,6 @@ def fuse_batch_counters(root):
     return flat
 
 
-_BATCH_PACK = os.environ.get("ISWM_BATCH_PACK", "1") != "0"     # 0: every conv call packs its own weight (tuning switch)
-
-
 class WeightPacker(object):
     """Packs the weights of every (unpadded) Conv2d under `root` for the bf16x6 kernels in ONE launch per forward
     pass -- the exact 3-way split in MFMA fragment order, csrc/conv_mfma_x6.hip k_pack_weights_batch -- instead of
@@ -537,7 +533,7 @@ class WeightPacker(object):
     def begin(self):
         from .. import _lib
         math = _lib.load().iswm_get_conv_math()
-        if math < 1 or not ops._USE_PACKED or not self.convs or not _BATCH_PACK:
+        if math < 1 or not ops._USE_PACKED or not self.convs:
             return
         key = (math, ops.planes_on()) + tuple(m.weight.data_ptr() for m in self.convs)      # bf16x6 packs 3 planes, bf16 one
         if key != self.key:
@@ -554,7 +550,7 @@ class WeightPacker(object):
             e["live"] = False
 
 
-_CLS_FUSE = os.environ.get("ISWM_CLS_FUSE", "1") != "0"      # tuning switch: 0 = the classifier as a conv of its own
+_CLS_FUSE = True      # False: the classifier as a conv of its own (tests compare both paths)
 
 
 def cls_fusable(conv, bn, relu, cls):

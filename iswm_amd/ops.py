@@ -10,7 +10,6 @@ contiguous and whose pixel pitch ``ld = t.stride(2)`` may exceed C (a channel
 slice of a wider buffer -- that is how torch.cat disappears from the graph).
 """
 import ctypes
-import os
 
 import torch
 
@@ -55,15 +54,12 @@ def new_act(n, h, w, c, device):
 
 
 # ---- "planes": activations stored pre-split for the bf16x6 convolution kernels (csrc/planes.h) -------------
-# ISWM_PLANES=0 keeps every activation fp32 (the round-1 data path); conv math f32 / bf16 do that too.
-_PLANES_ENV = os.environ.get("ISWM_PLANES", "1") != "0"
-_WGRAD_PLANES = os.environ.get("ISWM_WGRAD_PLANES", "1") != "0"     # tuning switch: 0 joins the planes and runs the fp32-input weight gradient
+# False keeps every activation fp32 (the round-1 data path, which tests compare against); conv math f32 does that too.
+_PLANES_ENV = True
 
 
 # conv math "bf16" (BASELINE configs[4], mixed precision): activations between convolutions are STORED as one bf16 plane
 # (round to nearest even) -- 2 bytes per element through every memory-bound pass instead of 4 (fp32) or 6 (bf16x6 planes).
-# ISWM_BF16_STORE=0 keeps them fp32 and rounds inside the conv kernels (the round-2 form of this mode).
-_BF16_STORE = os.environ.get("ISWM_BF16_STORE", "1") != "0"
 
 
 def nplanes():
@@ -71,7 +67,7 @@ def nplanes():
     math = _lib.load().iswm_get_conv_math()
     if not _PLANES_ENV:
         return 0
-    return 3 if math == 1 else (1 if (math == 2 and _BF16_STORE) else 0)
+    return 3 if math == 1 else (1 if math == 2 else 0)
 
 
 def planes_on():
@@ -389,7 +385,7 @@ def conv2d_fwd(x, w_ohwi, g, bias=None, out=None, want_stats=False, wpk=None, wp
     return out, partials, tiles
 
 
-_USE_PACKED = os.environ.get("ISWM_X6_PK", "1") != "0"
+_USE_PACKED = True      # False: the packed-weight kernels stay unused (tests compare both paths)
 
 
 def _packed_bytes(d, kind):
@@ -420,7 +416,7 @@ class BnStats(object):
         self.mask, self.masked = mask, False
 
 
-_BN_FUSE = os.environ.get("ISWM_BN_FUSE", "1") != "0"      # tuning switch: 0 = BatchNorm backward always reduces itself
+_BN_FUSE = True      # False: BatchNorm backward always reduces itself (tests compare both paths)
 
 
 def conv2d_dgrad(dy, w_ohwi, g, x_like_shape, dx=None, accumulate=False, wpk=None, wpk2=None, bn_stats=None):
@@ -496,7 +492,7 @@ def conv2d_wgrad(x, dy, g, dw_ohwi=None):
         dw_ohwi = torch.empty((g.cout, g.kh, g.kw, g.cin), dtype=torch.float32, device=x.device)
     _check_w(dw_ohwi, g)
     c8 = (g.cout + 7) // 8 * 8
-    if isinstance(x, Planes) and planes_on() and _WGRAD_PLANES and _wgrad_planes_ok(x, dy, g, c8):
+    if isinstance(x, Planes) and planes_on() and _wgrad_planes_ok(x, dy, g, c8):
         if not isinstance(dy, Planes) or c8 != g.cout:
             dyf = as_f32(dy)
             dy = new_planes(g.n, g.ho, g.wo, c8, x.device)
@@ -527,7 +523,7 @@ def conv2d_wgrad(x, dy, g, dw_ohwi=None):
 # ---- ASPP: the parallel branch convolutions as one launch (csrc/conv_mfma_pl2t.hip) ---------------------------------
 ASPP_TILE_ROWS = 144
 _ASPP_PLANS = {}
-_ASPP_FUSED = os.environ.get("ISWM_ASPP_FUSED", "1") != "0"      # tuning switch: 0 = one launch per branch
+_ASPP_FUSED = True      # False: one launch per branch (tests compare both paths)
 
 
 def _int_array(v):
@@ -734,9 +730,6 @@ def bn_apply(y, coef, relu, residual=None, out=None, planes=False):
     return out
 
 
-_BN_MASK_FROM_Y = os.environ.get("ISWM_BN_MASKY", "1") != "0"     # tuning switch
-
-
 def bn_backward(dout, out, y, coef, gamma, relu, training, dgamma, dbeta, want_dres=False, dy=None, dy_planes=False,
                 stats=None):
     """Returns (dy, dres|None); writes dgamma / dbeta (length-C fp32 tensors).  `out` (the saved activation, for the
@@ -755,7 +748,7 @@ def bn_backward(dout, out, y, coef, gamma, relu, training, dgamma, dbeta, want_d
     dres = torch.empty(y.shape, dtype=torch.float32, device=y.device) if want_dres else None
     # ReLU without a residual: hand over the forward's scale / shift so the sign pattern is recomputed from y and the
     # saved output is never read (a residual stage's pattern depends on the identity tensor: read `out` there)
-    masky = _relu_code(relu) == 1 and not want_dres and _BN_MASK_FROM_Y
+    masky = _relu_code(relu) == 1 and not want_dres
     if stats is not None and stats.partials is not None:
         call("iswm_bn_backward_stats_pl", _p(dout), ldd, _p(po), ldo, pso, _p(y), ldy, m, c, _p(coef[2]), _p(coef[3]), _p(gamma),
              _p(coef[0]) if masky else None, _p(coef[1]) if masky else None,

@@ -658,7 +658,7 @@ def test_bf16_store_is_round_to_nearest_even():
     try:
         lib.iswm_set_conv_math(2)
         if not ops.planes_on():
-            pytest.skip("ISWM_BF16_STORE=0")
+            pytest.skip("activation planes switched off (ops._PLANES_ENV)")
         g = torch.Generator().manual_seed(3)
         x = torch.randn(2, 9, 11, 128, generator=g)
         x[0, 0, 0, :6] = torch.tensor([1.00390625, 1.01171875, -1.00390625, 3.0e38, 1e-30, 0.0])     # exact ties (to even), range ends

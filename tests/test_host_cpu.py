@@ -135,7 +135,9 @@ def _ddp_worker(rank, world, port, q):
         ddp._on_ready(p)
     ddp.finish_grad_sync()
     ok = all(bool((p.grad == 3.0 * (i + 1)).all()) for i, p in enumerate(params))   # 1 + 2 summed
-    q.put((rank, ok, w0))
+    # by value: a tensor would travel as a handle to this process's shared memory, which is gone if the process exits
+    # before the parent has unpickled it (FileNotFoundError in the parent's q.get)
+    q.put((rank, ok, w0.numpy()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -152,7 +154,7 @@ def test_ddp_bucketed_allreduce_gloo_world2():
         p.join(60)
         assert p.exitcode == 0
     assert res[0][1] and res[1][1]
-    assert torch.equal(res[0][2], res[1][2])          # rank-0 parameters were broadcast
+    assert torch.equal(torch.from_numpy(res[0][2]), torch.from_numpy(res[1][2]))          # rank-0 parameters were broadcast
 
 
 def test_c_abi_argument_validation_without_a_gpu():
@@ -220,7 +222,8 @@ def _cw_worker(rank, world, port, q):
     g = torch.Generator().manual_seed(11)
     full = [(torch.rand(2, 16, 16, generator=g) < (0.05 + 0.1 * i)).to(torch.uint8) for i in range(6)]
     shard = full[rank::world]                                      # what a DistributedSampler hands this rank
-    q.put((rank, calculate_class_weights([(None, x) for x in shard]), calculate_class_weights.__module__))
+    w = calculate_class_weights([(None, x) for x in shard])
+    q.put((rank, w.numpy(), calculate_class_weights.__module__))           # by value (see _ddp_worker)
     dist.barrier()
     dist.destroy_process_group()
 
@@ -242,7 +245,8 @@ def test_class_weights_are_global_under_data_parallelism():
     g = torch.Generator().manual_seed(11)
     full = [(torch.rand(2, 16, 16, generator=g) < (0.05 + 0.1 * i)).to(torch.uint8) for i in range(6)]
     want = calculate_class_weights([(None, x) for x in full])
-    assert torch.equal(res[0][1], res[1][1]) and torch.equal(res[0][1], want)
+    w0, w1 = torch.from_numpy(res[0][1]), torch.from_numpy(res[1][1])
+    assert torch.equal(w0, w1) and torch.equal(w0, want)
 
 
 def _ddp_accum_worker(rank, world, port, q):

@@ -4,12 +4,15 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from tests.util import load, rel_err
+from iswm_amd import ops
 from iswm_amd.network import modeling
 from oracle.deeplab import OracleDeepLab
 from oracle.make_golden import model_input, model_state
 from oracle.synth import ArchCfg, synth_state_dict
 
-for tag, backbone, os_ in (("r50_os16", "resnet50", 16), ("r101_os8", "resnet101", 8)):
+for planes, (tag, backbone, os_) in [(p, c) for c in (("r50_os16", "resnet50", 16), ("r101_os8", "resnet101", 8))
+                                     for p in (True, False)]:
+    ops._PLANES_ENV = planes          # False: every activation fp32 (the round-1 data path)
     fx = load("model_%s.npz" % tag)
     cfg = ArchCfg("deeplabv3plus", backbone, 2, os_)
     sd = model_state(tag, cfg)
@@ -25,4 +28,4 @@ for tag, backbone, os_ in (("r50_os16", "resnet50", 16), ("r101_os8", "resnet101
     with torch.no_grad():
         lg = m(x.cuda())
     print("%s planes=%s: vs golden(fp32 cpu) %.3e   vs oracle fp64 %.3e   golden vs fp64 %.3e" %
-          (tag, os.environ.get("ISWM_PLANES", "1"), rel_err(lg, fx["train_logits"]), rel_err(lg, ref64), rel_err(fx["train_logits"], ref64)))
+          (tag, int(planes), rel_err(lg, fx["train_logits"]), rel_err(lg, ref64), rel_err(fx["train_logits"], ref64)))

@@ -1,6 +1,5 @@
 """Isolated kernel time of the planes forward / data-gradient kernels on the production shapes (median of N launches, HIP
-events on the launch stream).  One process = one setting of the env switches (ISWM_PL2_WIDE, ISWM_PL2W_PRIO, ...): run it
-once per setting in the same gpurun call for a same-box A/B.   usage: pl2_shapes.py [rounds] [case filter substring]"""
+events on the launch stream).   usage: pl2_shapes.py [rounds] [case filter substring]"""
 import os
 import sys
 
@@ -35,7 +34,6 @@ def med(fn):
     return ts[len(ts) // 2]
 
 
-print("env:", {k: v for k, v in os.environ.items() if k.startswith("ISWM_")})
 tot = totw = 0.0
 for c in CASES:
     n, h, w, cin, cout, k, s, p, d = c
