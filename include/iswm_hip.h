@@ -362,6 +362,37 @@ int iswm_confusion_matrix(const void* labels, int label_dtype, const void* preds
 int iswm_confusion_matrix_logits(const void* labels, int label_dtype, const float* logits, int B, int C, int64_t HW,
                                  int n_classes, int64_t* hist, iswm_stream_t stream);
 
+/* ---- sequence-validation metrics (mask_metrics.hip) ----------------------------------
+ * Batched [N, H, W] masks (1 <= H, W <= 2048), current stream, no host copies.  src dtype codes: 0 = uint8,
+ * 1 = int64; inputs are binarised with > 0.  Borders are neutral (cv2's default for morphology).
+ * morph: dst = dilate (dilate != 0) or erode of the mask by a (2*radius+1)^2 rectangle.
+ * ccl: 8-connected components of mask != 0; labels[i] = the smallest frame raster index (y*W+x) of the
+ *   pixel's component, -1 for background; areas[i] = the component's pixel count where i is that root, else 0.
+ * preprocess: MaskUtils.preprocess_mask (metrics/utils/mask_utils.py:7-50) -- close, open (3x3), largest
+ *   component of area >= 0.001*H*W (ties: smallest root) -> out (0/1), weight (1, max(0.4, 1-0.2*(n-1)), or 0
+ *   with an empty out), area.
+ * fronts: per row the leftmost column whose value (mask * weight; weight NULL = 1) equals 1, else -1;
+ *   stats[N][3] = count, sum of rows, sum of columns.
+ * front_error: FrontTrackingMetrics.calculate_error on front rows [N][H] of each (pred, gt) pair.
+ * pair_scores: MaskUtils.calculate_stability / calculate_motion of (current, previous) pairs.
+ * region_score: RegionMetrics.calculate_region_metrics; valid = 0 where either frame is empty. */
+int iswm_mask_morph(const void* src, int src_dtype, int N, int H, int W, int radius, int dilate, uint8_t* dst,
+                    iswm_stream_t stream);
+int iswm_ccl(const uint8_t* mask, int N, int H, int W, int32_t* labels, int32_t* areas, iswm_stream_t stream);
+size_t iswm_mask_preprocess_workspace(int N, int H, int W);
+int iswm_mask_preprocess(const void* src, int src_dtype, int N, int H, int W, uint8_t* out, double* weight,
+                         int64_t* area, void* workspace, size_t workspace_bytes, iswm_stream_t stream);
+int iswm_mask_fronts(const uint8_t* mask, const double* weight, int N, int H, int W, int32_t* fronts, int64_t* stats,
+                     iswm_stream_t stream);
+int iswm_front_error(const int32_t* pred_fronts, const int32_t* gt_fronts, int N, int H, double tau, double* out,
+                     iswm_stream_t stream);
+int iswm_mask_pair_scores(const int32_t* curr_fronts, const int64_t* curr_stats, const uint8_t* prev_mask,
+                          const double* prev_weight, const int64_t* prev_stats, int N, int H, int W, double* stability,
+                          double* motion, iswm_stream_t stream);
+size_t iswm_region_workspace(int N, int H, int W);
+int iswm_region_score(const void* pred, int pred_dtype, const void* gt, int gt_dtype, int N, int H, int W, double* score,
+                      int32_t* valid, void* workspace, size_t workspace_bytes, iswm_stream_t stream);
+
 /* ---- training-input pipeline -------------------------------------------------------
  * The reference's per-sample PIL chain ExtRandomScale -> ExtRandomCrop(pad_if_needed) -> ExtRandomHorizontalFlip ->
  * ExtToTensor -> ExtNormalize (train.py:355-362, utils/ext_transforms.py:94-115,212-396) for a whole batch in one

@@ -6,7 +6,7 @@ torch ops or the CPU oracle.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libiswm_hip.so")
@@ -118,6 +118,15 @@ _SIGS = {
     "iswm_augment_batch": (c_int, [P, P, P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P, P]),
     "iswm_confusion_matrix": (c_int, [P, c_int, P, c_int, c_int64, c_int, P, P]),
     "iswm_confusion_matrix_logits": (c_int, [P, c_int, P, c_int, c_int, c_int64, c_int, P, P]),
+    "iswm_mask_morph": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "iswm_ccl": (c_int, [P, c_int, c_int, c_int, P, P, P]),
+    "iswm_mask_preprocess_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "iswm_mask_preprocess": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
+    "iswm_mask_fronts": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
+    "iswm_front_error": (c_int, [P, P, c_int, c_int, c_double, P, P]),
+    "iswm_mask_pair_scores": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P, P]),
+    "iswm_region_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "iswm_region_score": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "iswm_sgd_step": (c_int, [P, P, P, c_int64, P, c_float, c_float, c_int, P]),
     "iswm_adam_step": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, c_int, P]),
 }

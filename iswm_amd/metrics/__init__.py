@@ -1,3 +1,4 @@
+from .sequence_metrics import FrontTrackingMetrics, RegionMetrics, TemporalMetrics
 from .stream_metrics import StreamMetrics
 
-__all__ = ["StreamMetrics"]
+__all__ = ["StreamMetrics", "TemporalMetrics", "RegionMetrics", "FrontTrackingMetrics"]

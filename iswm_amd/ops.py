@@ -995,6 +995,107 @@ def confusion_matrix_logits(labels, logits, n_classes, hist=None):
     return hist
 
 
+def _masks(t):
+    """[N, H, W] (or [H, W]) uint8 / int64 class map on the device, contiguous"""
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3:
+        raise ValueError("expected [N, H, W] masks, got %s" % (tuple(t.shape),))
+    return t.contiguous()
+
+
+def mask_morph(src, radius, dilate):
+    """dilate / erode (src > 0) by a (2*radius+1)^2 rectangle, neutral border -> uint8 [N, H, W]"""
+    src = _masks(src)
+    n, h, w = src.shape
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=src.device)
+    call("iswm_mask_morph", _p(src), _int_code(src), n, h, w, int(radius), int(bool(dilate)), _p(out), _stream())
+    return out
+
+
+def ccl(mask):
+    """8-connected components of a uint8 mask: (labels int32 [N, H, W], the component's smallest raster index or -1;
+    areas int32 [N, H, W], the component's size at that root, 0 elsewhere)"""
+    mask = _masks(mask)
+    if mask.dtype != torch.uint8:
+        raise TypeError("ccl takes a uint8 mask, got %s" % mask.dtype)
+    n, h, w = mask.shape
+    labels = torch.empty((n, h, w), dtype=torch.int32, device=mask.device)
+    areas = torch.empty_like(labels)
+    call("iswm_ccl", _p(mask), n, h, w, _p(labels), _p(areas), _stream())
+    return labels, areas
+
+
+def mask_preprocess(src):
+    """MaskUtils.preprocess_mask per frame: (mask uint8 [N, H, W], weight float64 [N], area int64 [N]); the
+    reference's result is mask * weight"""
+    src = _masks(src)
+    n, h, w = src.shape
+    dev = src.device
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+    weight = torch.empty(n, dtype=torch.float64, device=dev)
+    area = torch.empty(n, dtype=torch.int64, device=dev)
+    nbytes = _lib.load().iswm_mask_preprocess_workspace(n, h, w)
+    ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=dev)
+    call("iswm_mask_preprocess", _p(src), _int_code(src), n, h, w, _p(out), _p(weight), _p(area), _p(ws), nbytes,
+         _stream())
+    return out, weight, area
+
+
+def mask_fronts(mask, weight=None):
+    """leftmost column per row where mask * weight == 1 (-1: none): (fronts int32 [N, H], stats int64 [N, 3] =
+    count, sum of rows, sum of columns)"""
+    mask = _masks(mask)
+    if mask.dtype != torch.uint8:
+        raise TypeError("mask_fronts takes a uint8 mask, got %s" % mask.dtype)
+    n, h, w = mask.shape
+    fronts = torch.empty((n, h), dtype=torch.int32, device=mask.device)
+    stats = torch.empty((n, 3), dtype=torch.int64, device=mask.device)
+    weight = weight.contiguous() if weight is not None else None
+    call("iswm_mask_fronts", _p(mask), _p(weight), n, h, w, _p(fronts), _p(stats), _stream())
+    return fronts, stats
+
+
+def front_error(pred_fronts, gt_fronts, tau):
+    """FrontTrackingMetrics.calculate_error per (pred, gt) pair of front rows [N, H] -> float64 [N]"""
+    pred_fronts, gt_fronts = pred_fronts.contiguous(), gt_fronts.contiguous()
+    if pred_fronts.shape != gt_fronts.shape or pred_fronts.dtype != torch.int32 or gt_fronts.dtype != torch.int32:
+        raise ValueError("front rows must be two int32 [N, H] tensors of one shape")
+    n, h = pred_fronts.shape
+    out = torch.empty(n, dtype=torch.float64, device=pred_fronts.device)
+    call("iswm_front_error", _p(pred_fronts), _p(gt_fronts), n, h, float(tau), _p(out), _stream())
+    return out
+
+
+def mask_pair_scores(curr_fronts, curr_stats, prev_mask, prev_weight, prev_stats):
+    """MaskUtils.calculate_stability / calculate_motion of (current, previous) preprocessed frames, given the
+    current frames' fronts and the previous frames' masks -> (stability, motion) float64 [N]"""
+    prev_mask = _masks(prev_mask)
+    n, h, w = prev_mask.shape
+    if tuple(curr_fronts.shape) != (n, h):
+        raise ValueError("fronts %s do not match masks %s" % (tuple(curr_fronts.shape), tuple(prev_mask.shape)))
+    stab = torch.empty(n, dtype=torch.float64, device=prev_mask.device)
+    motion = torch.empty_like(stab)
+    call("iswm_mask_pair_scores", _p(curr_fronts.contiguous()), _p(curr_stats.contiguous()), _p(prev_mask),
+         _p(prev_weight.contiguous()), _p(prev_stats.contiguous()), n, h, w, _p(stab), _p(motion), _stream())
+    return stab, motion
+
+
+def region_score(pred, gt):
+    """RegionMetrics.calculate_region_metrics per frame -> (final_score float64 [N], valid int32 [N])"""
+    pred, gt = _masks(pred), _masks(gt)
+    if pred.shape != gt.shape:
+        raise ValueError("pred %s and gt %s differ in shape" % (tuple(pred.shape), tuple(gt.shape)))
+    n, h, w = pred.shape
+    score = torch.empty(n, dtype=torch.float64, device=pred.device)
+    valid = torch.empty(n, dtype=torch.int32, device=pred.device)
+    nbytes = _lib.load().iswm_region_workspace(n, h, w)
+    ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=pred.device)
+    call("iswm_region_score", _p(pred), _int_code(pred), _p(gt), _int_code(gt), n, h, w, _p(score), _p(valid), _p(ws),
+         nbytes, _stream())
+    return score, valid
+
+
 def sgd_step(p, g, buf, lr_dev, momentum, weight_decay, nesterov):
     call("iswm_sgd_step", _p(p), _p(g), _p(buf), p.numel(), _p(lr_dev), float(momentum), float(weight_decay),
          int(bool(nesterov)), _stream())

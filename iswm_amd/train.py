@@ -82,6 +82,11 @@ def get_argparser():
                         help="run the reference's train_transform (random scale / crop / flip / normalise, "
                              "train.py:355-362) as one HIP kernel per batch on uint8 tiles")
     parser.add_argument("--pretrained_backbone", action='store_true', default=False)
+    parser.add_argument("--val_metrics", type=str, default='confusion', choices=['confusion', 'sequence'],
+                        help="confusion: every validation frame counted into the confusion matrix, best checkpoint on "
+                             "0.5*FG-IoU + 0.5*FG-F1; sequence: the reference's validate_and_save (train.py:620-745) -- "
+                             "sliding windows of --sequence_length frames ordered by file name, the temporal / front / "
+                             "region evaluators, best checkpoint by is_best_score")
     return parser
 
 
@@ -197,6 +202,93 @@ def validate(model, loader, device, opts):
     return {k: float(v) for k, v in metrics.get_results().items()}
 
 
+METRIC_WEIGHTS = {"MIoU": 0.05, "Foreground IoU": 0.25, "Foreground F1": 0.25, "Front Tracking Error": 0.25,
+                  "Temporal Consistency": 0.10, "Region Continuity": 0.10}         # get_metric_weights, train.py:842-850
+
+
+def validate_sequence(model, loader, device, opts):
+    """the metric half of train.py:620-694: eval-mode argmax masks (kept on the device), ordered by
+    ``loader.dataset.images``, fed to StreamMetrics as sliding windows of ``--sequence_length`` frames; with fewer
+    frames than that nothing is counted"""
+    from .metrics import StreamMetrics
+    model.eval()
+    preds, gts = [], []
+    with torch.no_grad():
+        for images, labels in loader:
+            preds.append(ops.argmax_nchw(model(images.to(device, dtype=torch.float32))))
+            gts.append(labels.to(device))
+    model.train()
+    metrics = StreamMetrics(opts.num_classes, sequence_length=opts.sequence_length, device=device)
+    L = opts.sequence_length
+    if preds:
+        preds, gts = torch.cat(preds), torch.cat(gts)
+        names = loader.dataset.images
+        order = sorted(range(preds.shape[0]), key=lambda i: names[i])        # stable, as list.sort in the reference
+        idx = torch.tensor(order, dtype=torch.int64).to(device)
+        preds, gts = preds.index_select(0, idx), gts.index_select(0, idx)
+        for i in range(preds.shape[0] - L + 1):
+            metrics.update(gts[i:i + L], preds[i:i + L], sequence_data=True)
+    return {k: float(v) for k, v in metrics.get_results().items()}
+
+
+def initialize_best_score():
+    """train.py:747-758"""
+    inf = float('inf')
+    return {'MIoU': -inf, 'Foreground IoU': -inf, 'Foreground F1': -inf, 'Temporal Consistency': -inf,
+            'Front Tracking Error': inf, 'Region Continuity': -inf, 'Precision': -inf, 'Recall': -inf}
+
+
+def is_best_score(current, best, weights=METRIC_WEIGHTS):
+    """train.py:760-797 (without the prints)"""
+    if best is None:
+        return True
+    current_total = best_total = 0
+    for metric in ('MIoU', 'Foreground IoU', 'Foreground F1', 'Temporal Consistency', 'Region Continuity'):
+        if metric in weights and weights[metric] > 0:
+            v = float(current[metric])
+            if not np.isnan(v):
+                current_total += weights[metric] * v
+                best_total += weights[metric] * float(best.get(metric, 0.0))
+    if 'Front Tracking Error' in current:
+        w = abs(weights.get('Front Tracking Error', 0.03))
+        current_total += w * max(0, 1 - float(current['Front Tracking Error']) / 10.0)
+        best_total += w * max(0, 1 - float(best.get('Front Tracking Error', 10.0)) / 10.0)
+    return current_total > best_total
+
+
+def update_best_score(val_score):
+    """train.py:799-840 (without the prints)"""
+    best = {}
+    for metric in ('MIoU', 'Foreground IoU', 'Foreground F1', 'Region Continuity'):
+        v = val_score.get(metric)
+        best[metric] = float(v) if v is not None and not np.isnan(v) else 0.0
+    if 'Front Tracking Error' in val_score:
+        e = float(val_score['Front Tracking Error'])
+        best['Front Tracking Error'] = e if not np.isnan(e) else 10.0
+    if 'Temporal Consistency' in val_score:
+        v = val_score['Temporal Consistency']
+        best['Temporal Consistency'] = float(v) if v is not None and not np.isnan(v) else 0.0
+    for metric in ('Precision', 'Recall'):
+        if metric in val_score and not np.isnan(val_score[metric]):
+            best[metric] = float(val_score[metric])
+    return best
+
+
+def logged_weighted_score(val_score, weights=METRIC_WEIGHTS):
+    """MetricsLogger.get_weighted_score (train.py:128-167) over the values validate_and_save logs (:686-694): FG-IoU,
+    FG-F1 and region continuity, the front error as max(0, 1 - e/10), temporal consistency"""
+    score = 0.0
+    for metric in ('Foreground IoU', 'Foreground F1', 'Region Continuity'):
+        v = float(val_score.get(metric, 0))
+        if not np.isnan(v):
+            score += weights[metric] * v
+    score += abs(weights['Front Tracking Error']) * max(0, 1 - float(val_score.get('Front Tracking Error', 0)) / 10.0)
+    v = float(val_score.get('Temporal Consistency', 0))
+    if not np.isnan(v):
+        score += weights['Temporal Consistency'] * v
+    return score
+
+
 def save_best_model(model, optimizer, scheduler, opts, val_score, weighted_score, cur_itrs, best_score):
     """train.py:525-609 -- same payload keys, atomic replace, older best_*.pth removed"""
     os.makedirs(opts.checkpoints_dir, exist_ok=True)
@@ -284,8 +376,13 @@ def main(argv=None):
         optimizer.load_state_dict(ckpt["optimizer_state"])
         scheduler.load_state_dict(ckpt["scheduler_state"])
 
+    sequence_val = opts.val_metrics == 'sequence'
+    if sequence_val:
+        best_score = initialize_best_score()
+        if ckpt is not None and opts.continue_training and isinstance(ckpt.get("best_score"), dict):
+            best_score = ckpt["best_score"]
     if opts.test_only:
-        print(validate(model, val_loader, device, opts))
+        print((validate_sequence if sequence_val else validate)(model, val_loader, device, opts))
         return
     model.train()
     interval_loss = torch.zeros((), device=device)
@@ -324,13 +421,21 @@ def main(argv=None):
             if cur_itrs % opts.val_interval == 0 and world > 1:
                 dist.barrier()               # the other ranks wait HERE (not inside the next step's all-reduce) while rank 0 validates
             if cur_itrs % opts.val_interval == 0 and rank == 0:
-                score = validate(model, val_loader, device, opts)
-                weighted = 0.5 * score["Foreground IoU"] + 0.5 * score["Foreground F1"]
-                print("Validation @%d: %s" % (cur_itrs, score))
-                if weighted > best_score:
-                    best_score = weighted
-                    print("saved", save_best_model(model, optimizer, scheduler, opts, score, weighted, cur_itrs,
-                                                   best_score))
+                if sequence_val:                                # train.py:686-731
+                    score = validate_sequence(model, val_loader, device, opts)
+                    print("Validation @%d: %s" % (cur_itrs, score))
+                    if is_best_score(score, best_score):
+                        best_score = update_best_score(score)
+                        print("saved", save_best_model(model, optimizer, scheduler, opts, score,
+                                                       logged_weighted_score(score), cur_itrs, best_score))
+                else:
+                    score = validate(model, val_loader, device, opts)
+                    weighted = 0.5 * score["Foreground IoU"] + 0.5 * score["Foreground F1"]
+                    print("Validation @%d: %s" % (cur_itrs, score))
+                    if weighted > best_score:
+                        best_score = weighted
+                        print("saved", save_best_model(model, optimizer, scheduler, opts, score, weighted, cur_itrs,
+                                                       best_score))
             if cur_itrs % opts.val_interval == 0 and world > 1:
                 dist.barrier()
             scheduler.step()
