@@ -419,6 +419,21 @@ int iswm_augment_batch(const unsigned char* images, const unsigned char* labels,
                        const int* tables, int B, int crop_h, int crop_w, const float* mean3, const float* std3,
                        float* out_nchw, unsigned char* out_labels, iswm_stream_t stream);
 
+/* ---- inference outputs (predict.hip) ------------------------------------------------
+ * predict_normalize: uint8 [N][H][W][3] RGB -> fp32 NCHW [N][3][H][W], (v / 255.0f - mean) / std in IEEE fp32
+ * (ToTensor + Normalize, predict.py:93-97).
+ * predict_maps: low-resolution NHWC logits yl [N][Hi][Wi][ldx] (first C channels; ldx % 4 == 0, ldx >= pad4(C))
+ * -> per output pixel of [N][Ho][Wo]: bilinear sample (k_bilinear_to_nchw_fwd's arithmetic), p = softmax(l)[fg],
+ * pred = p > thr ? 255 : 0 (fp32 compare), conf = (uint8)(p * 255.0f), band = band_lo <= conf <= band_hi ? 255 : 0,
+ * prob = p (optional, NULL: not written); stats [N][5] = {min p, max p, sum p, count(p < thr), count(pred)} (fp64,
+ * fixed-order sums, bit-reproducible).  Output pointers 16-byte aligned; workspace: iswm_predict_maps_workspace. */
+int iswm_predict_normalize(const unsigned char* img, int N, int H, int W, const float* mean3, const float* std3,
+                           float* out_nchw, iswm_stream_t stream);
+size_t iswm_predict_maps_workspace(int N, int H, int W);
+int iswm_predict_maps(const float* yl, int N, int Hi, int Wi, int ldx, int C, int fg, int Ho, int Wo, float thr,
+                      int band_lo, int band_hi, unsigned char* pred, unsigned char* conf, unsigned char* band,
+                      float* prob, double* stats, void* workspace, size_t workspace_bytes, iswm_stream_t stream);
+
 /* ---- optimizers over a flat fp32 arena ------------------------------------------
  * torch.optim.SGD(momentum=0.9, nesterov=True, weight_decay) / Adam / AdamW as built
  * by setup_optimizer, train.py:421-444.  lr is read from device memory so that a

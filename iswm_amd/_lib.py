@@ -127,6 +127,10 @@ _SIGS = {
     "iswm_mask_pair_scores": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P, P]),
     "iswm_region_workspace": (c_size_t, [c_int, c_int, c_int]),
     "iswm_region_score": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "iswm_predict_normalize": (c_int, [P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P]),
+    "iswm_predict_maps_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "iswm_predict_maps": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P, P,
+                                  P, P, P, P, c_size_t, P]),
     "iswm_sgd_step": (c_int, [P, P, P, c_int64, P, c_float, c_float, c_int, P]),
     "iswm_adam_step": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, c_int, P]),
 }
@@ -148,6 +152,9 @@ def load():
         raise ImportError(
             "libiswm_hip.so is not built (%s). Run `python -m iswm_amd.build` (hipcc, gfx950). "
             "iswm_amd has no CPU or torch-op fallback." % LIB_PATH)
+    # torch first: its HIP runtime is then the one the library binds to.  Loaded the other way round, the process holds
+    # two runtimes and the library's launches on torch's streams fail ("no ROCm-capable device is detected").
+    import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in _SIGS.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing

@@ -1,0 +1,301 @@
+// Inference outputs on the device: the reference's predict.py per-image chain
+//   ToTensor -> Normalize (predict.py:93-97), model, softmax, prob[:, 1], `> threshold`, `* 255 -> uint8`,
+//   binarize_confidence_map (predict.py:214-290)
+// as two kernels around the model:
+//   * k_predict_normalize: uint8 HWC RGB -> normalised fp32 NCHW, (v / 255.0f - m) / s in IEEE fp32 as torch does
+//     on the CPU (the expression k_augment uses);
+//   * k_predict_maps: the classifier's low-resolution NHWC logits -> bilinear sample (the index and weight arithmetic
+//     of k_bilinear_to_nchw_fwd, bilinear.h) -> softmax over C classes -> p = prob[fg] -> pred / conf / band uint8
+//     maps (+ optional fp32 p) and per-workgroup statistics in a slab, summed by k_predict_stats in a fixed order.
+// Exactness: the threshold compare is fp32 (torch compares a float32 tensor with a Python float
+// in float32); conf truncates (numpy astype(uint8)); the band compares conf with integer bounds the host derived
+// from the reference's fp64 expression conf / 255.0 >= min_prob, <= max_prob; no float atomics anywhere.
+#include "bilinear.h"
+#include "rowmap.h"
+
+namespace iswm {
+
+constexpr int PM_BLOCK = 256;
+constexpr int PM_PIX = 16;           // consecutive raster pixels per thread: one 16-B store per uint8 map
+constexpr int PM_MAX_GROUPS = 4;     // logits kept in registers for C <= 16; larger C re-samples in a second pass
+
+struct PredictPartial {              // one workgroup's share of one image (32 B)
+    double sum;
+    float mn, mx;
+    long long n_low, n_pred;
+};
+
+__global__ __launch_bounds__(256) void k_predict_normalize(const unsigned char* __restrict__ img, int N, int64_t HW,
+                                                           float m0, float m1, float m2, float s0, float s1, float s2,
+                                                           float* __restrict__ out) {
+    const int64_t M = (int64_t)N * HW;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M; i += (int64_t)gridDim.x * 256) {
+        const int64_t n = i / HW, p = i - n * HW;
+        const unsigned char* s = img + i * 3;
+        float* o = out + n * 3 * HW + p;
+        o[0] = __fdiv_rn(__fdiv_rn((float)s[0], 255.0f) - m0, s0);
+        o[HW] = __fdiv_rn(__fdiv_rn((float)s[1], 255.0f) - m1, s1);
+        o[2 * HW] = __fdiv_rn(__fdiv_rn((float)s[2], 255.0f) - m2, s2);
+    }
+}
+
+// the four source taps of one output pixel, same expression as k_bilinear_to_nchw_fwd
+__device__ __forceinline__ float4 bilerp4(const float* pa, const float* pb, const float* pd, const float* pe,
+                                          const Lerp& lh, const Lerp& lw, int c0) {
+    float4 a = ld4(pa + c0), b = ld4(pb + c0), d = ld4(pd + c0), e = ld4(pe + c0);
+    float4 o;
+    o.x = lh.l0 * (lw.l0 * a.x + lw.l1 * b.x) + lh.l1 * (lw.l0 * d.x + lw.l1 * e.x);
+    o.y = lh.l0 * (lw.l0 * a.y + lw.l1 * b.y) + lh.l1 * (lw.l0 * d.y + lw.l1 * e.y);
+    o.z = lh.l0 * (lw.l0 * a.z + lw.l1 * b.z) + lh.l1 * (lw.l0 * d.z + lw.l1 * e.z);
+    o.w = lh.l0 * (lw.l0 * a.w + lw.l1 * b.w) + lh.l1 * (lw.l0 * d.w + lw.l1 * e.w);
+    return o;
+}
+
+__device__ __forceinline__ float comp(const float4& v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
+
+// p = softmax(l)[fg] with m = max_c l_c, e_c = expf(l_c - m), s summed in class order
+template <int G>
+__device__ __forceinline__ float fg_prob(const float* pa, const float* pb, const float* pd, const float* pe,
+                                         const Lerp& lh, const Lerp& lw, int C, int fg) {
+    if constexpr (G > 0) {
+        float4 v[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) v[g] = bilerp4(pa, pb, pd, pe, lh, lw, 4 * g);
+        float m = v[0].x;
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (4 * g + k < C) m = fmaxf(m, comp(v[g], k));
+        float s = 0.f, ef = 0.f;
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (4 * g + k < C) {
+                    const float e = expf(comp(v[g], k) - m);
+                    s += e;
+                    if (4 * g + k == fg) ef = e;
+                }
+        return __fdiv_rn(ef, s);
+    } else {                     // C > 16: sample twice (the same arithmetic gives the same logits)
+        float m = -INFINITY;
+        for (int c0 = 0; c0 < C; c0 += 4) {
+            const float4 v = bilerp4(pa, pb, pd, pe, lh, lw, c0);
+            for (int k = 0; k < 4 && c0 + k < C; ++k) m = fmaxf(m, comp(v, k));
+        }
+        float s = 0.f, ef = 0.f;
+        for (int c0 = 0; c0 < C; c0 += 4) {
+            const float4 v = bilerp4(pa, pb, pd, pe, lh, lw, c0);
+            for (int k = 0; k < 4 && c0 + k < C; ++k) {
+                const float e = expf(comp(v, k) - m);
+                s += e;
+                if (c0 + k == fg) ef = e;
+            }
+        }
+        return __fdiv_rn(ef, s);
+    }
+}
+
+// grid (blocks_per_image, N).  Image n owns the raster pixels [n*H*W, (n+1)*H*W) of the [N, H, W] outputs; a thread
+// takes the 16-pixel chunks k of the whole tensor (pixels [16k, 16k+16)) that overlap its image and produces the
+// pixels of the chunk inside it.  A chunk wholly inside the image is stored as one 16-B store per uint8 map; a chunk
+// shared by two images (at most one per image boundary) is written byte by byte by both.
+template <int G>
+__global__ __launch_bounds__(PM_BLOCK) void k_predict_maps(const float* __restrict__ yl, int Hi, int Wi, int ldx, int C,
+                                                           int fg, int Ho, int Wo, float sh, float sw, float thr, int lo,
+                                                           int hi, unsigned char* __restrict__ pred,
+                                                           unsigned char* __restrict__ conf,
+                                                           unsigned char* __restrict__ band, float* __restrict__ prob,
+                                                           PredictPartial* __restrict__ partials) {
+    const int n = blockIdx.y;
+    const int64_t HW = (int64_t)Ho * Wo;
+    const int64_t p_begin = (int64_t)n * HW, p_end = p_begin + HW;
+    const int64_t k_begin = p_begin / PM_PIX, k_end = (p_end + PM_PIX - 1) / PM_PIX;
+    const float* base = yl + (size_t)n * Hi * Wi * ldx;
+
+    double sum = 0.0;
+    float mn = INFINITY, mx = -INFINITY;
+    long long n_low = 0, n_pred = 0;
+    for (int64_t k = k_begin + (int64_t)blockIdx.x * PM_BLOCK + threadIdx.x; k < k_end;
+         k += (int64_t)gridDim.x * PM_BLOCK) {
+        const int64_t q0 = k * PM_PIX;
+        const int j0 = q0 < p_begin ? (int)(p_begin - q0) : 0;
+        const int j1 = q0 + PM_PIX > p_end ? (int)(p_end - q0) : PM_PIX;
+        int rem = (int)(q0 + j0 - p_begin);
+        int oh = rem / Wo, ow = rem - oh * Wo;
+        Lerp lh = src_index(sh, oh, Hi);
+        unsigned int wp[4] = {0u, 0u, 0u, 0u}, wc[4] = {0u, 0u, 0u, 0u}, wb[4] = {0u, 0u, 0u, 0u};
+        float pv[PM_PIX];
+#pragma unroll
+        for (int j = 0; j < PM_PIX; ++j) {
+            pv[j] = 0.f;
+            if (j < j0 || j >= j1) continue;
+            const Lerp lw = src_index(sw, ow, Wi);
+            const float* pa = base + ((size_t)lh.i0 * Wi + lw.i0) * ldx;
+            const float* pb = base + ((size_t)lh.i0 * Wi + lw.i1) * ldx;
+            const float* pd = base + ((size_t)lh.i1 * Wi + lw.i0) * ldx;
+            const float* pe = base + ((size_t)lh.i1 * Wi + lw.i1) * ldx;
+            const float p = fg_prob<G>(pa, pb, pd, pe, lh, lw, C, fg);
+            pv[j] = p;
+            const unsigned int vp = p > thr ? 255u : 0u;
+            const unsigned int vc = (unsigned int)(p * 255.0f);
+            const unsigned int vb = ((int)vc >= lo && (int)vc <= hi) ? 255u : 0u;
+            wp[j >> 2] |= vp << (8 * (j & 3));
+            wc[j >> 2] |= vc << (8 * (j & 3));
+            wb[j >> 2] |= vb << (8 * (j & 3));
+            sum += (double)p;
+            mn = fminf(mn, p);
+            mx = fmaxf(mx, p);
+            n_low += p < thr ? 1 : 0;
+            n_pred += vp ? 1 : 0;
+            if (++ow == Wo) {
+                ow = 0;
+                lh = src_index(sh, ++oh, Hi);
+            }
+        }
+        if (j0 == 0 && j1 == PM_PIX) {
+            *reinterpret_cast<uint4*>(pred + q0) = make_uint4(wp[0], wp[1], wp[2], wp[3]);
+            *reinterpret_cast<uint4*>(conf + q0) = make_uint4(wc[0], wc[1], wc[2], wc[3]);
+            *reinterpret_cast<uint4*>(band + q0) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
+            if (prob) {
+#pragma unroll
+                for (int j = 0; j < PM_PIX; j += 4)
+                    *reinterpret_cast<float4*>(prob + q0 + j) = make_float4(pv[j], pv[j + 1], pv[j + 2], pv[j + 3]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < PM_PIX; ++j) {
+                if (j < j0 || j >= j1) continue;
+                const int sh8 = 8 * (j & 3);
+                pred[q0 + j] = (unsigned char)(wp[j >> 2] >> sh8);
+                conf[q0 + j] = (unsigned char)(wc[j >> 2] >> sh8);
+                band[q0 + j] = (unsigned char)(wb[j >> 2] >> sh8);
+                if (prob) prob[q0 + j] = pv[j];
+            }
+        }
+    }
+
+    // workgroup reduction in a fixed order: wave shuffles, then wave 0 over the four wave results
+    __shared__ PredictPartial red[PM_BLOCK / 64];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_down(sum, off, 64);
+        mn = fminf(mn, __shfl_down(mn, off, 64));
+        mx = fmaxf(mx, __shfl_down(mx, off, 64));
+        n_low += __shfl_down(n_low, off, 64);
+        n_pred += __shfl_down(n_pred, off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = PredictPartial{sum, mn, mx, n_low, n_pred};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        PredictPartial r = red[0];
+        for (int w = 1; w < PM_BLOCK / 64; ++w) {
+            r.sum += red[w].sum;
+            r.mn = fminf(r.mn, red[w].mn);
+            r.mx = fmaxf(r.mx, red[w].mx);
+            r.n_low += red[w].n_low;
+            r.n_pred += red[w].n_pred;
+        }
+        partials[(size_t)n * gridDim.x + blockIdx.x] = r;
+    }
+}
+
+// stats[n] = {min p, max p, sum p, count(p < thr), count(pred)}: one wave per image; lane l takes the partials
+// l, l + 64, ... in order, then a shuffle tree -- a fixed order, so the result is bit-reproducible
+__global__ __launch_bounds__(64) void k_predict_stats(const PredictPartial* __restrict__ partials, int blocks,
+                                                      double* __restrict__ stats) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const PredictPartial* p = partials + (size_t)n * blocks;
+    double sum = 0.0;
+    float mn = INFINITY, mx = -INFINITY;
+    long long n_low = 0, n_pred = 0;
+    for (int b = lane; b < blocks; b += 64) {
+        sum += p[b].sum;
+        mn = fminf(mn, p[b].mn);
+        mx = fmaxf(mx, p[b].mx);
+        n_low += p[b].n_low;
+        n_pred += p[b].n_pred;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_down(sum, off, 64);
+        mn = fminf(mn, __shfl_down(mn, off, 64));
+        mx = fmaxf(mx, __shfl_down(mx, off, 64));
+        n_low += __shfl_down(n_low, off, 64);
+        n_pred += __shfl_down(n_pred, off, 64);
+    }
+    if (lane == 0) {
+        double* s = stats + (size_t)n * 5;
+        s[0] = (double)mn;
+        s[1] = (double)mx;
+        s[2] = sum;
+        s[3] = (double)n_low;
+        s[4] = (double)n_pred;
+    }
+}
+
+// workgroups per image: about one chunk per thread, at most ~2048 workgroups in all
+static int predict_blocks_per_image(int N, int H, int W) {
+    const int64_t chunks = ((int64_t)H * W + PM_PIX - 1) / PM_PIX + 1;
+    int64_t b = (chunks + PM_BLOCK - 1) / PM_BLOCK;
+    const int64_t cap = N >= 2048 ? 1 : 2048 / N;
+    if (b > cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+}  // namespace iswm
+
+using namespace iswm;
+
+extern "C" int iswm_predict_normalize(const unsigned char* img, int N, int H, int W, const float* mean3,
+                                      const float* std3, float* out_nchw, iswm_stream_t stream) {
+    ISWM_REQUIRE(img && mean3 && std3 && out_nchw, "predict_normalize: null pointer");
+    ISWM_REQUIRE(N > 0 && H > 0 && W > 0, "predict_normalize: bad size");
+    const int64_t HW = (int64_t)H * W;
+    hipLaunchKernelGGL(k_predict_normalize, dim3(stream_grid((int64_t)N * HW, 256)), dim3(256), 0,
+                       (hipStream_t)stream, img, N, HW, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2],
+                       out_nchw);
+    return check_launch("predict_normalize");
+}
+
+extern "C" size_t iswm_predict_maps_workspace(int N, int H, int W) {
+    if (N <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)N * predict_blocks_per_image(N, H, W) * sizeof(PredictPartial);
+}
+
+extern "C" int iswm_predict_maps(const float* yl, int N, int Hi, int Wi, int ldx, int C, int fg, int Ho, int Wo,
+                                 float thr, int band_lo, int band_hi, unsigned char* pred, unsigned char* conf,
+                                 unsigned char* band, float* prob, double* stats, void* workspace,
+                                 size_t workspace_bytes, iswm_stream_t stream) {
+    ISWM_REQUIRE(yl && pred && conf && band && stats && workspace, "predict_maps: null pointer");
+    ISWM_REQUIRE(N > 0 && N <= 65535 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "predict_maps: bad size");
+    ISWM_REQUIRE(C > 0 && ldx % 4 == 0 && ldx >= ((C + 3) / 4) * 4, "predict_maps: need ldx %% 4 == 0, ldx >= pad4(C)");
+    ISWM_REQUIRE(fg >= 0 && fg < C, "predict_maps: foreground class %d outside [0, %d)", fg, C);
+    ISWM_REQUIRE(aligned16(yl) && aligned16(pred) && aligned16(conf) && aligned16(band) && (!prob || aligned16(prob)),
+                 "predict_maps: pointers must be 16-byte aligned");
+    const int blocks = predict_blocks_per_image(N, Ho, Wo);
+    ISWM_REQUIRE(workspace_bytes >= (size_t)N * blocks * sizeof(PredictPartial),
+                 "predict_maps: workspace too small (see iswm_predict_maps_workspace)");
+    const dim3 grid(blocks, N);
+    const float sh = (float)Hi / (float)Ho, sw = (float)Wi / (float)Wo;
+    PredictPartial* part = (PredictPartial*)workspace;
+    const int groups = (C + 3) / 4;
+#define ISWM_PM(G)                                                                                                   \
+    hipLaunchKernelGGL(k_predict_maps<G>, grid, dim3(PM_BLOCK), 0, (hipStream_t)stream, yl, Hi, Wi, ldx, C, fg, Ho, \
+                       Wo, sh, sw, thr, band_lo, band_hi, pred, conf, band, prob, part)
+    switch (groups > PM_MAX_GROUPS ? 0 : groups) {
+        case 1: ISWM_PM(1); break;
+        case 2: ISWM_PM(2); break;
+        case 3: ISWM_PM(3); break;
+        case 4: ISWM_PM(4); break;
+        default: ISWM_PM(0); break;
+    }
+#undef ISWM_PM
+    int rc = check_launch("predict_maps");
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_predict_stats, dim3(N), dim3(64), 0, (hipStream_t)stream, part, blocks, stats);
+    return check_launch("predict_stats");
+}

@@ -1,31 +1,14 @@
 // Bilinear resize with align_corners=False (F.interpolate at network/_deeplab.py:58 and
 // network/utils.py:22), forward and backward, plus the NCHW <-> NHWC layout changes at the
-// model boundary.  Index/weight arithmetic restates ATen's area_pixel_compute_source_index:
-//   scale = in/out (float); src = scale*(dst+0.5)-0.5, clamped at 0; i0 = (int)src;
-//   i1 = i0 + (i0 < in-1); l1 = src - i0; l0 = 1 - l1.
+// model boundary.  Index/weight arithmetic (Lerp, src_index: bilinear.h) restates ATen's
+// area_pixel_compute_source_index.
 // Backward is a GATHER (each input pixel visits the output pixels that can reference it and
 // re-derives their weights with the same float formula), so it needs no atomics and is
 // bit-reproducible.  All kernels are HBM/L2-bound.
+#include "bilinear.h"
 #include "rowmap.h"
 
 namespace iswm {
-
-struct Lerp {
-    int i0, i1;
-    float l0, l1;
-};
-
-__device__ __forceinline__ Lerp src_index(float scale, int dst, int in_size) {
-    float src = scale * ((float)dst + 0.5f) - 0.5f;
-    if (src < 0.f) src = 0.f;
-    Lerp r;
-    r.i0 = (int)src;
-    if (r.i0 > in_size - 1) r.i0 = in_size - 1;
-    r.i1 = r.i0 + (r.i0 < in_size - 1 ? 1 : 0);
-    r.l1 = src - (float)r.i0;
-    r.l0 = 1.f - r.l1;
-    return r;
-}
 
 // candidate output range that can touch input index i (with one index of slack each side)
 __device__ __forceinline__ void out_range(float inv_scale, int i, int out_size, int& lo, int& hi) {

@@ -59,7 +59,15 @@ class _SimpleSegmentationModel(nn.Module):
         return pk
 
     def _fwd(self, x, save):
-        n, c, h, w = x.shape
+        h, w = x.shape[2:]
+        yl = self._fwd_lowres(x, save)
+        nc = self.classifier.num_classes
+        # bilinear upsample to the input size fused with NHWC -> NCHW (reference :22)
+        return ops.bilinear_to_nchw_fwd(yl, nc, h, w)
+
+    def _fwd_lowres(self, x, save):
+        """x NCHW -> the classifier's NHWC logits [B, hl, wl, pad4(num_classes)]"""
+        c = x.shape[1]
         if self.training:
             flat = self._counters()
             if flat is not None:
@@ -81,10 +89,8 @@ class _SimpleSegmentationModel(nn.Module):
             raise
         if not save:
             pk.end()                                           # no backward will follow: retire the packed weights
-        nc = self.classifier.num_classes
         self._saved = (tuple(yl.shape), c) if save else None
-        # bilinear upsample to the input size fused with NHWC -> NCHW (reference :22)
-        return ops.bilinear_to_nchw_fwd(yl, nc, h, w)
+        return yl
 
     def _bwd(self, dlogits, need_dx):
         (n, hl, wl, cp), cin = self._saved
@@ -108,6 +114,16 @@ class _SimpleSegmentationModel(nn.Module):
             if params or x.requires_grad:
                 return _SegBridge.apply(self, x, *params)
         return self._fwd(x, False)
+
+    def forward_lowres(self, x):
+        """The classifier's low-resolution NHWC logits [B, hl, wl, pad4(num_classes)] (fp32, channels past
+        num_classes are padding), without the final upsample: ops.bilinear_to_nchw_fwd(forward_lowres(x), nc, H, W)
+        is bit-identical to forward(x).  Inference only -- raises while autograd is recording."""
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+            raise ValueError("iswm_amd model takes a 4-D fp32 CUDA NCHW tensor (there is no CPU fallback)")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError("forward_lowres has no backward: call it under torch.no_grad()")
+        return ops.as_f32(self._fwd_lowres(x, False))
 
 
 class IntermediateLayerGetter(nn.ModuleDict):

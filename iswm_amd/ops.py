@@ -10,6 +10,7 @@ contiguous and whose pixel pitch ``ld = t.stride(2)`` may exceed C (a channel
 slice of a wider buffer -- that is how torch.cat disappears from the graph).
 """
 import ctypes
+import functools
 
 import torch
 
@@ -1094,6 +1095,81 @@ def region_score(pred, gt):
     call("iswm_region_score", _p(pred), _int_code(pred), _p(gt), _int_code(gt), n, h, w, _p(score), _p(valid), _p(ws),
          nbytes, _stream())
     return score, valid
+
+
+def predict_normalize(img, mean, std):
+    """uint8 [N, H, W, 3] RGB on the device -> normalised fp32 NCHW [N, 3, H, W]: (v / 255 - mean) / std in fp32,
+    bit-identical to ToTensor + Normalize on the CPU"""
+    if img.dim() == 3:
+        img = img.unsqueeze(0)
+    if img.dim() != 4 or img.shape[3] != 3 or img.dtype != torch.uint8 or not img.is_cuda:
+        raise ValueError("expected a uint8 CUDA [N, H, W, 3] image batch, got %s %s" % (tuple(img.shape), img.dtype))
+    img = img.contiguous()
+    n, h, w, _ = img.shape
+    out = torch.empty((n, 3, h, w), dtype=torch.float32, device=img.device)
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    call("iswm_predict_normalize", _p(img), n, h, w, m, s, _p(out), _stream())
+    return out
+
+
+@functools.lru_cache(maxsize=64)
+def band_bounds(min_prob, max_prob):
+    """(lo, hi) with lo <= k <= hi exactly for the confidence values k in 0..255 that binarize_confidence_map marks
+    (predict.py:229-234: k / 255.0 >= min_prob and k / 255.0 <= max_prob, fp64); an empty band gives (1, 0)"""
+    ks = [k for k in range(256) if k / 255.0 >= min_prob and k / 255.0 <= max_prob]
+    return (ks[0], ks[-1]) if ks else (1, 0)
+
+
+def _align16(v):
+    return (v + 15) // 16 * 16
+
+
+def predict_maps_layout(n, h, w):
+    """byte offsets of stats (fp64 [n, 5]), pred, conf, band (uint8 [n, h, w]) in predict_maps' packed buffer and its
+    size: a prefix up to the last map a caller needs can be copied to the host in one transfer"""
+    stats = 0
+    pred = _align16(40 * n)
+    conf = pred + _align16(n * h * w)
+    band = conf + _align16(n * h * w)
+    return {"stats": stats, "pred": pred, "conf": conf, "band": band, "end": band + _align16(n * h * w)}
+
+
+class PredictMaps(tuple):
+    """(pred, conf, band, prob, stats, packed): pred / conf / band uint8 [N, H, W], prob fp32 [N, H, W] or None,
+    stats fp64 [N, 5] = (min p, max p, sum p, count(p < thr), count(pred)); every tensor but prob is a view of the
+    uint8 buffer `packed` (predict_maps_layout)"""
+    __slots__ = ()
+    pred = property(lambda self: self[0])
+    conf = property(lambda self: self[1])
+    band = property(lambda self: self[2])
+    prob = property(lambda self: self[3])
+    stats = property(lambda self: self[4])
+    packed = property(lambda self: self[5])
+
+
+def predict_maps(yl, num_classes, fg, H, W, thr, min_prob, max_prob, want_prob=False):
+    """low-resolution NHWC logits (the model's forward_lowres) -> PredictMaps at [N, H, W]: the reference's
+    predict_mask / binarize_confidence_map maps in one pass (bilinear upsample, softmax, p = prob[fg], pred = p > thr,
+    conf = uint8(p * 255), band = min_prob <= conf / 255 <= max_prob).  Enqueues only; never synchronises."""
+    yl = as_f32(yl)
+    n, hl, wl, c, ld = geom(yl)
+    if ld % 4 or ld < (num_classes + 3) // 4 * 4 or num_classes > c:
+        raise ValueError("logits %s (pitch %d) do not hold %d classes" % (tuple(yl.shape), ld, num_classes))
+    if not 0 <= fg < num_classes:
+        raise ValueError("foreground class %d outside [0, %d)" % (fg, num_classes))
+    dev = yl.device
+    lay = predict_maps_layout(n, H, W)
+    packed = torch.empty(lay["end"], dtype=torch.uint8, device=dev)
+    stats = packed[:40 * n].view(torch.float64).view(n, 5)
+    pred, conf, band = (packed[lay[k]:lay[k] + n * H * W].view(n, H, W) for k in ("pred", "conf", "band"))
+    prob = torch.empty((n, H, W), dtype=torch.float32, device=dev) if want_prob else None
+    lo, hi = band_bounds(min_prob, max_prob)
+    nbytes = _lib.load().iswm_predict_maps_workspace(n, H, W)
+    ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=dev)
+    call("iswm_predict_maps", _p(yl), n, hl, wl, ld, int(num_classes), int(fg), int(H), int(W), float(thr),
+         lo, hi, _p(pred), _p(conf), _p(band), _p(prob), _p(stats), _p(ws), nbytes, _stream())
+    return PredictMaps((pred, conf, band, prob, stats, packed))
 
 
 def sgd_step(p, g, buf, lr_dev, momentum, weight_decay, nesterov):

@@ -1,0 +1,336 @@
+"""Inference entry point -- runnable counterpart of the reference's predict.py.
+
+    python -m iswm_amd.predict --input <dir> --ckpt <checkpoint> --save_val_results_to <out> \\
+        [--save_confidence] [--save_binary] [--batch_size B] [--workers W]
+
+Every subfolder of ``--input`` is walked (process_images, predict.py:292-368) and each frame gets
+``<out>/<subfolder>/<name>_predict.png`` (0/255 foreground mask), plus ``_confidence.png`` (uint8(p * 255), p = the
+softmax foreground probability) and ``_binary_mask.png`` (min_broken_prob <= conf / 255 <= max_broken_prob) when
+asked for.  Per batch, the uint8 frames are uploaded once; ops.predict_normalize, the model's forward_lowres and
+ops.predict_maps run on the device; one asynchronous copy brings the maps and the per-image statistics back; PNG
+decoding and encoding run in a thread pool, overlapping the device work.
+
+Same flags and defaults as the reference's get_argparser (predict.py:19-67).  Differences, all deliberate:
+  * ``--model`` takes this project's constructors (train.py's choices); the reference builds resnet50 only;
+  * models are built with ``pretrained_backbone=False`` -- the weights come from ``--ckpt`` (the reference's
+    pretrained backbone is a download);
+  * ``--save_val_results_to`` is required (the reference's default None crashes at os.makedirs);
+  * ``--gpu_id`` selects ``cuda:<id>`` among the visible devices; the process does not rewrite
+    CUDA_VISIBLE_DEVICES;
+  * new ``--batch_size`` (default 1): consecutive frames of one subfolder with the same size share a batch;
+  * new ``--workers`` (default 4): host threads for PNG decoding and encoding;
+  * ``--binary_threshold`` is accepted and unused, as in the reference (predict.py:223);
+  * ``--enable_wave_processing`` is refused: its synthetic "broken area" generator is random and draws with
+    OpenCV, which is not a dependency here.  Its flags still parse;
+  * ``_predict.png`` is mode L with values 0 / 255 (this project's decode_target); the colour map of the
+    reference's BinarySegmentation.decode_target is not in its tree and stays unpinned;
+  * subfolders and files are walked in sorted order (the reference uses os.listdir order);
+  * messages are in English.
+"""
+import argparse
+import os
+import sys
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+from PIL import Image
+
+IMAGE_EXTENSIONS = ('.png', '.jpg', '.jpeg', '.tif')
+MEAN = (0.485, 0.456, 0.406)        # predict.py:96
+STD = (0.229, 0.224, 0.225)
+WAVE_PROCESSING_REFUSED = ("--enable_wave_processing is not supported: the reference's synthetic broken-area "
+                           "generator is random and draws with OpenCV, which this project does not depend on")
+
+
+def _model_names():
+    from . import network
+    return sorted(name for name in network.modeling.__dict__ if name.islower() and
+                  not (name.startswith("__") or name.startswith('_')) and callable(network.modeling.__dict__[name]))
+
+
+def get_argparser():
+    parser = argparse.ArgumentParser()
+
+    # Dataset Options
+    parser.add_argument("--input", type=str, required=True,
+                        help="Directory whose subfolders hold the images")
+    parser.add_argument("--dataset", type=str, default='binary', choices=['binary'], help='Name of dataset')
+
+    # Model Options
+    parser.add_argument("--model", type=str, default='deeplabv3plus_resnet50', choices=_model_names(),
+                        help='Model name')
+    parser.add_argument("--ckpt", default=None, type=str, help="Path to trained model")
+    parser.add_argument("--gpu_id", type=str, default='0', help="GPU ID (index among the visible devices)")
+    parser.add_argument("--save_val_results_to", default=None, required=True,
+                        help="Directory to save segmentation results")
+
+    # Additional Parameters
+    parser.add_argument("--output_stride", type=int, default=16, help='Output stride for DeepLabV3+ (8 or 16)')
+
+    # Confidence Map & Binary Mask Options
+    parser.add_argument("--save_confidence", action='store_true', help="Save confidence maps")
+    parser.add_argument("--save_binary", action='store_true', help="Save binary masks")
+    parser.add_argument("--binary_threshold", type=int, default=200,
+                        help="Threshold for binarizing confidence map (unused, as in the reference)")
+    parser.add_argument("--pred_threshold", type=float, default=0.5,
+                        help="Threshold for predicting foreground (default: 0.5)")
+
+    # Internal-wave processing options (parsed; --enable_wave_processing is refused)
+    parser.add_argument("--internal_wave_area_threshold", type=float, default=0.01,
+                        help="Minimum foreground area ratio to consider image having internal waves")
+    parser.add_argument("--synthetic_broken_prob", type=float, default=0.8,
+                        help="Probability to generate synthetic broken areas for no-wave images")
+    parser.add_argument("--synthetic_broken_ratio", type=float, default=0.05,
+                        help="Ratio of image area to generate as synthetic broken areas")
+    parser.add_argument("--enable_wave_processing", action='store_true',
+                        help="Enable internal wave specific processing (not supported)")
+
+    parser.add_argument("--min_broken_prob", type=float, default=0.2,
+                        help="Minimum foreground probability to consider pixel as broken area (default: 0.2)")
+    parser.add_argument("--max_broken_prob", type=float, default=0.7,
+                        help="Maximum foreground probability to consider pixel as broken area (default: 0.7)")
+
+    # this project's additions
+    parser.add_argument("--batch_size", type=int, default=1,
+                        help="frames per device batch (consecutive frames of one subfolder with the same size)")
+    parser.add_argument("--workers", type=int, default=4, help="host threads for PNG decoding and encoding")
+    return parser
+
+
+def list_subdirs(input_base_path):
+    return sorted(d for d in os.listdir(input_base_path) if os.path.isdir(os.path.join(input_base_path, d)))
+
+
+def list_images(subdir_path):
+    return sorted(f for f in os.listdir(subdir_path) if f.lower().endswith(IMAGE_EXTENSIONS)
+                  and os.path.isfile(os.path.join(subdir_path, f)))
+
+
+def decode_image(path):
+    """uint8 [H, W, 3] RGB (predict.py:259)"""
+    with Image.open(path) as im:
+        return np.asarray(im.convert('RGB'))
+
+
+def _decoded(pool, paths, ahead):
+    """(path, array or exception) in order, keeping at most `ahead` decodes in flight"""
+    q = deque()
+    it = iter(paths)
+    for p in it:
+        q.append((p, pool.submit(decode_image, p)))
+        if len(q) >= ahead:
+            break
+    while q:
+        p, f = q.popleft()
+        try:
+            yield p, f.result()
+        except Exception as e:          # noqa: BLE001 -- reported per image, like the reference
+            yield p, e
+        nxt = next(it, None)
+        if nxt is not None:
+            q.append((nxt, pool.submit(decode_image, nxt)))
+
+
+def _batches(decoded, batch_size, on_error):
+    """consecutive decoded frames with the same size, at most batch_size each: lists of (path, array)"""
+    cur = []
+    for path, img in decoded:
+        if isinstance(img, Exception):
+            on_error(path, img)
+            continue
+        if cur and (len(cur) >= batch_size or cur[0][1].shape != img.shape):
+            yield cur
+            cur = []
+        cur.append((path, img))
+    if cur:
+        yield cur
+
+
+def _save_png(arr, path):
+    """uint8 [H, W] -> mode-L PNG"""
+    Image.fromarray(np.ascontiguousarray(arr)).save(path)
+
+
+def _stats_lines(st, npix, thr):
+    """the reference's per-image log (predict.py:271-272)"""
+    return ("Foreground probability: min=%.4f, max=%.4f, mean=%.4f\n"
+            "Pixels below prediction threshold %s: %.2f%%" %
+            (st[0], st[1], st[2] / npix, thr, 100.0 * st[3] / npix))
+
+
+def process_images(input_base_path, output_path, predict_batch, save_confidence, save_binary, pred_threshold=0.5,
+                   batch_size=1, workers=4, log=print, progress=True):
+    """Walk the subfolders of input_base_path (predict.py:292-368) and write the masks of every image.
+
+    predict_batch(uint8 [B, H, W, 3]) enqueues one batch and returns a callable; calling it waits for that batch and
+    returns {"pred", "conf", "band": uint8 [B, H, W] (conf / band may be None when not asked for), "stats": [B, 5]}.
+    Batch i+1 is enqueued before batch i is waited for, and the PNGs are encoded in the pool, so the device never
+    waits on host encoding.  An exception on one image is printed and that image skipped.  Returns the number of
+    images written."""
+    from tqdm import tqdm
+
+    os.makedirs(output_path, exist_ok=True)
+    subdirs = list_subdirs(input_base_path)
+    log("\nFound %d subfolders" % len(subdirs))
+    files = {d: list_images(os.path.join(input_base_path, d)) for d in subdirs}
+    total_images = sum(len(v) for v in files.values())
+    log("Found %d images in total" % total_images)
+
+    done = [0]
+    workers = max(1, int(workers))
+    batch_size = max(1, int(batch_size))
+
+    def report(path, e):
+        log("\nError while processing %s: %s" % (path, e))
+
+    with ThreadPoolExecutor(max_workers=workers) as pool, \
+            tqdm(total=total_images, desc="Total progress", disable=not progress) as pbar:
+        encodes = deque()
+
+        def drain(block):
+            while encodes and (block or encodes[0][1].done()):
+                path, f = encodes.popleft()
+                try:
+                    f.result()
+                    done[0] += 1
+                    pbar.update(1)
+                except Exception as e:      # noqa: BLE001
+                    report(path, e)
+
+        def encode_one(res, k, out_base):
+            _save_png(res["pred"][k], out_base + '_predict.png')
+            if save_confidence:
+                _save_png(res["conf"][k], out_base + '_confidence.png')
+            if save_binary:
+                _save_png(res["band"][k], out_base + '_binary_mask.png')
+
+        def finish(pending):
+            items, subdir, wait, last = pending
+            try:
+                res = wait()
+            except Exception as e:          # noqa: BLE001
+                for path, _ in items:
+                    report(path, e)
+                res = None
+            for k, (path, img) in enumerate(items if res is not None else ()):
+                log(_stats_lines(res["stats"][k], img.shape[0] * img.shape[1], pred_threshold))
+                base = os.path.splitext(os.path.basename(path))[0]
+                out_base = os.path.join(output_path, subdir, base)
+                encodes.append((path, pool.submit(encode_one, res, k, out_base)))
+            if last:
+                log("Finished folder %s" % subdir)
+            drain(False)
+
+        # one pipeline across folders: the next folder's first batch is enqueued before the previous folder's last
+        # batch is waited for, and nothing waits on the encodes until the end
+        pending = None
+        for subdir in subdirs:
+            subdir_path = os.path.join(input_base_path, subdir)
+            log("\nProcessing folder: %s" % subdir)
+            log("Found %d images in %s" % (len(files[subdir]), subdir))
+            os.makedirs(os.path.join(output_path, subdir), exist_ok=True)
+            paths = [os.path.join(subdir_path, f) for f in files[subdir]]
+            for items in _batches(_decoded(pool, paths, 2 * batch_size + workers), batch_size, report):
+                try:
+                    wait = predict_batch(np.stack([img for _, img in items]))
+                except Exception as e:      # noqa: BLE001
+                    for path, _ in items:
+                        report(path, e)
+                    continue
+                if pending is not None:
+                    finish(pending)
+                pending = [items, subdir, wait, False]
+            if pending is not None and pending[1] == subdir:
+                pending[3] = True           # the folder is finished once its last batch is
+            else:
+                log("Finished folder %s" % subdir)
+        if pending is not None:
+            finish(pending)
+        drain(True)
+
+    log("\nPrediction finished, results saved to: %s" % output_path)
+    return done[0]
+
+
+class DevicePredictor:
+    """predict_batch for process_images: upload -> predict_normalize -> forward_lowres -> predict_maps -> one copy of
+    stats + the requested maps into pinned host memory"""
+
+    def __init__(self, model, device, num_classes, fg, pred_threshold, min_prob, max_prob, want_conf, want_band):
+        self.model, self.device = model, device
+        self.num_classes, self.fg = num_classes, fg
+        self.thr, self.min_prob, self.max_prob = pred_threshold, min_prob, max_prob
+        self.want_conf, self.want_band = want_conf, want_band
+
+    def __call__(self, batch):
+        import torch
+        from . import ops
+        n, h, w, _ = batch.shape
+        pin = torch.from_numpy(np.ascontiguousarray(batch)).pin_memory()
+        with torch.cuda.device(self.device), torch.no_grad():
+            img = pin.to(self.device, non_blocking=True)
+            x = ops.predict_normalize(img, MEAN, STD)
+            yl = self.model.forward_lowres(x)
+            maps = ops.predict_maps(yl, self.num_classes, self.fg, h, w, self.thr, self.min_prob, self.max_prob)
+            lay = ops.predict_maps_layout(n, h, w)
+            end = lay["band"] + n * h * w if self.want_band else lay["conf"] + n * h * w if self.want_conf else \
+                lay["pred"] + n * h * w
+            host = torch.empty(end, dtype=torch.uint8, pin_memory=True)
+            host.copy_(maps.packed[:end], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+
+        def wait():
+            ev.synchronize()
+            a = host.numpy()
+            stats = a[:40 * n].view(np.float64).reshape(n, 5)
+            pick = (lambda k: a[lay[k]:lay[k] + n * h * w].reshape(n, h, w))
+            return {"pred": pick("pred"), "conf": pick("conf") if self.want_conf else None,
+                    "band": pick("band") if self.want_band else None, "stats": stats}
+        return wait
+
+
+def load_model(model, ckpt_path):
+    """predict.py:80-91 with the weights-only loader: {"model_state": ...} (this project's and the reference's
+    checkpoints) or a bare state dict, `module.` prefixes stripped, strict load.  No file: initial weights."""
+    if ckpt_path is not None and os.path.isfile(ckpt_path):
+        from .train import load_checkpoint
+        ck = load_checkpoint(ckpt_path)
+        state = ck["model_state"] if isinstance(ck, dict) and "model_state" in ck else ck
+        state = {(k[7:] if k.startswith("module.") else k): v for k, v in state.items()}
+        model.load_state_dict(state, strict=True)
+        print("Model loaded from %s" % ckpt_path)
+    else:
+        print("[!] No checkpoint found")
+    return model
+
+
+def main(argv=None):
+    opts = get_argparser().parse_args(argv)
+    if opts.enable_wave_processing:
+        get_argparser().error(WAVE_PROCESSING_REFUSED)
+    if opts.batch_size < 1 or opts.workers < 1:
+        get_argparser().error("--batch_size and --workers must be at least 1")
+
+    import torch
+    from . import network
+    if not torch.cuda.is_available():
+        raise RuntimeError("iswm_amd.predict needs a GPU (there is no CPU path)")
+    device = torch.device("cuda:%d" % int(opts.gpu_id))
+    print("Device: %s" % device)
+
+    num_classes, fg = 2, 1                       # --dataset binary: prob[:, 1] (predict.py:267)
+    model = network.modeling.__dict__[opts.model](num_classes=num_classes, output_stride=opts.output_stride,
+                                                  pretrained_backbone=False)
+    model = load_model(model, opts.ckpt).to(device)
+    model.eval()
+
+    predictor = DevicePredictor(model, device, num_classes, fg, opts.pred_threshold, opts.min_broken_prob,
+                                opts.max_broken_prob, opts.save_confidence, opts.save_binary)
+    return process_images(opts.input, opts.save_val_results_to, predictor, opts.save_confidence, opts.save_binary,
+                          pred_threshold=opts.pred_threshold, batch_size=opts.batch_size, workers=opts.workers)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
