@@ -434,6 +434,49 @@ int iswm_predict_maps(const float* yl, int N, int Hi, int Wi, int ldx, int C, in
                       int band_lo, int band_hi, unsigned char* pred, unsigned char* conf, unsigned char* band,
                       float* prob, double* stats, void* workspace, size_t workspace_bytes, iswm_stream_t stream);
 
+/* ---- INT8 post-training quantized inference (qconv.hip, quant.hip) ----------------------
+ * Activations are int8 NHWC with a pixel pitch in bytes; one symmetric scale s per tensor (value = q * s).
+ * qconv: implicit-GEMM convolution on v_mfma_i32_16x16x64_i8, forward only.  x int8 [N][H][W][ldx] (first Cin
+ * channels, Cin % 64 == 0, ldx % 16 == 0, 16-byte aligned), w int8 OHWI [Cout][KH][KW][Cin] (Cout % 16 == 0; rows past
+ * the real output channels are zero; iswm_qconv_weight_bytes), mul / add fp64 [Cout].  Per output element, in fp64
+ * without contraction: v = acc * mul[c] + add[c]; with res: v += res * s_res; with relu: v = max(v, 0); then int8
+ * q = clamp(rint(v * inv_s_out), lo, 127) or, out_f32, (float)v.  Channels c < cstore of y (pitch ldy) are written,
+ * nothing else.  res int8 [pixel][ldr] (int8 output only). */
+typedef struct {
+    int N, H, W, Cin;   /* input  [N,H,W,Cin] */
+    int Ho, Wo, Cout;   /* output [N,Ho,Wo,Cout] (Cout padded to 16) */
+    int KH, KW, stride, pad, dil;
+    int ldx;            /* pixel pitch of x (bytes) */
+    int ldy;            /* pixel pitch of y (bytes for int8, floats for fp32) */
+    int ldr;            /* pixel pitch of res (bytes) */
+    int relu;           /* 1: max(v, 0) before quantizing */
+    int lo;             /* int8 floor: 0 (ReLU output) or -127 */
+    int out_f32;        /* 1: fp32 output */
+    int cstore;         /* output channels written, <= Cout */
+} iswm_qconv_desc;
+size_t iswm_qconv_weight_bytes(const iswm_qconv_desc* d);
+int iswm_qconv_fwd(const iswm_qconv_desc* d, const signed char* x, const signed char* w, const double* mul,
+                   const double* add, const signed char* res, double s_res, double inv_s_out, void* y,
+                   iswm_stream_t stream);
+/* absmax: amax[0] = max(amax[0], max |x|) over rows x the first C channels of an fp32 (ps == 0) or planes (ps != 0,
+ * the iswm_*_pl convention) tensor of pitch ld; a per-workgroup slab (iswm_absmax_workspace bytes) then one finalize
+ * workgroup; no atomics, no sync. */
+size_t iswm_absmax_workspace(int64_t rows, int C);
+int iswm_absmax(const void* x, int64_t ps, int64_t rows, int C, int ld, float* slab, size_t slab_bytes, float* amax,
+                iswm_stream_t stream);
+/* quantize_i8: y[r][c] = clamp(rint(x * inv_s), lo, 127) for c < C, 0 for C <= c < ldy (fp64 product) */
+int iswm_quantize_i8(const void* x, int64_t ps, int64_t rows, int C, int ld, double inv_s, int lo, signed char* y,
+                     int ldy, iswm_stream_t stream);
+/* qgap: y[n][c] = clamp(rint((sum_p x[n][p][c] * s_in / HW) * inv_s_in)), the int32 sum exact */
+int iswm_qgap(const signed char* x, int N, int HW, int C, int ldx, double s_in, double inv_s_in, signed char* y,
+              int ldy, iswm_stream_t stream);
+/* qbcast: y[n][p][c] = v[n][c] (C % 4 == 0) */
+int iswm_qbcast(const signed char* v, int N, int HW, int C, int ldv, signed char* y, int ldy, iswm_stream_t stream);
+/* qbilinear: align_corners=False resize (bilinear.h's indices and fp32 weights); the four taps dequantized with s_in
+ * and combined in fp64 as h0 (w0 a + w1 b) + h1 (w0 d + w1 e), quantized with inv_s_out (C % 4 == 0) */
+int iswm_qbilinear(const signed char* x, int N, int Hi, int Wi, int C, int ldx, double s_in, int Ho, int Wo,
+                   double inv_s_out, signed char* y, int ldy, iswm_stream_t stream);
+
 /* ---- optimizers over a flat fp32 arena ------------------------------------------
  * torch.optim.SGD(momentum=0.9, nesterov=True, weight_decay) / Adam / AdamW as built
  * by setup_optimizer, train.py:421-444.  lr is read from device memory so that a

@@ -18,6 +18,12 @@ class ConvDesc(Structure):
                                      "dil", "ldx", "ldy")]
 
 
+class QConvDesc(Structure):
+    """iswm_qconv_desc"""
+    _fields_ = [(n, c_int) for n in ("N", "H", "W", "Cin", "Ho", "Wo", "Cout", "KH", "KW", "stride", "pad",
+                                     "dil", "ldx", "ldy", "ldr", "relu", "lo", "out_f32", "cstore")]
+
+
 P = c_void_p
 _SIGS = {
     # name: (restype, [argtypes])
@@ -131,6 +137,14 @@ _SIGS = {
     "iswm_predict_maps_workspace": (c_size_t, [c_int, c_int, c_int]),
     "iswm_predict_maps": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P, P,
                                   P, P, P, P, c_size_t, P]),
+    "iswm_qconv_weight_bytes": (c_size_t, [POINTER(QConvDesc)]),
+    "iswm_qconv_fwd": (c_int, [POINTER(QConvDesc), P, P, P, P, P, c_double, c_double, P, P]),
+    "iswm_absmax_workspace": (c_size_t, [c_int64, c_int]),
+    "iswm_absmax": (c_int, [P, c_int64, c_int64, c_int, c_int, P, c_size_t, P, P]),
+    "iswm_quantize_i8": (c_int, [P, c_int64, c_int64, c_int, c_int, c_double, c_int, P, c_int, P]),
+    "iswm_qgap": (c_int, [P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, P]),
+    "iswm_qbcast": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P]),
+    "iswm_qbilinear": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_double, P, c_int, P]),
     "iswm_sgd_step": (c_int, [P, P, P, c_int64, P, c_float, c_float, c_int, P]),
     "iswm_adam_step": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, c_int, P]),
 }

@@ -113,6 +113,8 @@ class ASPP(_hip.HipModule):
         for i, conv in enumerate(self.convs):
             if fused is None or i >= len(fused):
                 conv.fwd(x, save, out=cat[..., i * oc:(i + 1) * oc])
+        if _hip.CALIB_RECORDER is not None:
+            _hip.CALIB_RECORDER.record(self, cat)
         self._saved = (tuple(x.shape), oc, fused) if save else None
         return self.project.fwd(cat, save)
 
@@ -252,6 +254,8 @@ class DeepLabHeadV3Plus(_hip.HipModule):
         self.project.fwd(low, save, out=cat[..., :c_low])
         a = self.aspp.fwd(hi, save)
         ops.bilinear_fwd(a, hl, wl, out=cat[..., c_low:c_cat])
+        if _hip.CALIB_RECORDER is not None:
+            _hip.CALIB_RECORDER.record(self, cat, c_cat)
         self._saved = (tuple(a.shape), c_low, c_cat) if save else None
         return self.classifier.fwd(cat, save)
 

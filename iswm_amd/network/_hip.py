@@ -26,6 +26,10 @@ MASK_RECORDER = None
 # ... and {MaxPool2d module: uint8 NHWC tap index (kh * 3 + kw) chosen per output element}: two fp32 implementations pick different
 # elements of a near-tie, which re-routes that window's gradient (same kind of discontinuity as a flipped ReLU)
 POOL_RECORDER = None
+# Calibration hook (iswm_amd.quant.calibrating): when set, the output of every fused conv stage, the stem's max-pool and the
+# ASPP / decoder concat buffers report their max |x| to it (recorder.record(module, tensor[, channels])).  None, the default,
+# leaves the forward exactly as it is.
+CALIB_RECORDER = None
 
 
 def pad4(c):
@@ -379,6 +383,8 @@ def _cba_finish(conv, bn, relu, x, y, g, partials, tiles, training, save, residu
     if MASK_RECORDER is not None and relu:
         of = ops.as_f32(o)
         MASK_RECORDER[bn] = (of > 0) & (of < 6) if relu == 6 and relu is not True else (of > 0)
+    if CALIB_RECORDER is not None:
+        CALIB_RECORDER.record(conv, o)
     ctx = None
     if save:
         ctx = dict(x=x, y=y, out=o, coef=coef, g=g, relu=relu, training=training, res=residual is not None, sep=sep, dw=dw)
@@ -556,8 +562,9 @@ _CLS_FUSE = True      # False: the classifier as a conv of its own (tests compar
 def cls_fusable(conv, bn, relu, cls):
     """[Conv2d(.., 256, k) -> BatchNorm2d -> ReLU] followed by the 1x1 classifier Conv2d(256, num_classes <= 4, 1): the tail of both
     DeepLab heads (network/_deeplab.py:44-52, 84-90).  The classifier is then folded into the stage's BatchNorm passes
-    (csrc/bn_classify.hip).  Not while a test records ReLU patterns (it needs the stage's stored output)."""
-    return (_CLS_FUSE and MASK_RECORDER is None and relu is True and type(conv) is Conv2d and conv.out_channels == 256 and
+    (csrc/bn_classify.hip).  Not while a test records ReLU patterns or a calibration records ranges (both need the stage's
+    stored output)."""
+    return (_CLS_FUSE and MASK_RECORDER is None and CALIB_RECORDER is None and relu is True and type(conv) is Conv2d and conv.out_channels == 256 and
             conv.bias is None and type(cls) is Conv2d and cls.in_channels == 256 and cls.out_channels <= 4 and
             tuple(cls.kernel_size) == (1, 1) and tuple(cls.stride) == (1, 1) and tuple(cls.padding) == (0, 0) and
             bn.momentum is not None and bn.track_running_stats and bn.affine)

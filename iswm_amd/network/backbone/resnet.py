@@ -118,6 +118,8 @@ class MaxPool2d(_hip.HipModule, nn.MaxPool2d):
         y, idx = ops.maxpool_fwd(x, planes=ops.planes_on() and x.shape[3] % 64 == 0)
         if _hip.POOL_RECORDER is not None:
             _hip.POOL_RECORDER[self] = idx
+        if _hip.CALIB_RECORDER is not None:
+            _hip.CALIB_RECORDER.record(self, y)
         self._saved = (idx, tuple(x.shape)) if save else None
         return y
 

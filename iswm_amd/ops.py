@@ -1180,3 +1180,100 @@ def sgd_step(p, g, buf, lr_dev, momentum, weight_decay, nesterov):
 def adam_step(p, g, m, v, hyper_dev, beta1, beta2, eps, weight_decay, decoupled):
     call("iswm_adam_step", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper_dev), float(beta1), float(beta2),
          float(eps), float(weight_decay), int(bool(decoupled)), _stream())
+
+
+# ---- INT8 post-training quantized inference (csrc/qconv.hip, csrc/quant.hip; iswm_amd/quant.py) ---------------------
+# int8 activations are NHWC torch.int8 tensors (pitched views allowed, pitch in bytes); one symmetric scale per tensor.
+def i8geom(t):
+    return geom(t, torch.int8)
+
+
+def qconv_desc(x, cout, k, stride, pad, dil, ldy, cstore, relu, lo, out_f32, ldr=0):
+    n, h, w, cin, ldx = i8geom(x)
+    ho, wo = conv_out_size(h, k, stride, pad, dil), conv_out_size(w, k, stride, pad, dil)
+    return _lib.QConvDesc(n, h, w, cin, ho, wo, cout, k, k, stride, pad, dil, ldx, ldy, ldr, int(bool(relu)), int(lo),
+                          int(bool(out_f32)), cstore)
+
+
+def qconv_fwd(x, w, mul, add, k, stride, pad, dil, relu, lo, inv_s_out, out=None, res=None, s_res=0.0, out_f32=False,
+              cstore=None):
+    """int8 implicit-GEMM convolution: x int8 NHWC [N,H,W,Cin] (Cin % 64 == 0), w int8 [Cout_p, KH*KW*Cin] (OHWI,
+    Cout_p % 16 == 0), mul / add fp64 [Cout_p] -> `out` (int8, or fp32 when out_f32) of which the first `cstore`
+    channels are written (default Cout_p).  Epilogue: see iswm_qconv_fwd."""
+    cout = w.shape[0]
+    cstore = cout if cstore is None else cstore
+    if w.dtype != torch.int8 or not w.is_contiguous() or mul.dtype != torch.float64 or add.dtype != torch.float64:
+        raise ValueError("qconv: int8 contiguous weights and fp64 mul / add expected")
+    n, h, wd, cin, _ = i8geom(x)
+    ho, wo = conv_out_size(h, k, stride, pad, dil), conv_out_size(wd, k, stride, pad, dil)
+    if out is None:
+        out = torch.empty((n, ho, wo, cstore), dtype=torch.float32 if out_f32 else torch.int8, device=x.device)
+    on, oh, ow, oc, ldy = geom(out, torch.float32 if out_f32 else torch.int8)
+    if (on, oh, ow) != (n, ho, wo) or oc < cstore:
+        raise ValueError("qconv: out %s cannot hold [%d, %d, %d, %d]" % (tuple(out.shape), n, ho, wo, cstore))
+    ldr = 0
+    if res is not None:
+        rn, rh, rw, rc, ldr = i8geom(res)
+        if (rn, rh, rw) != (n, ho, wo) or rc < cstore:
+            raise ValueError("qconv: residual %s does not cover [%d, %d, %d, %d]" % (tuple(res.shape), n, ho, wo, cstore))
+    d = qconv_desc(x, cout, k, stride, pad, dil, ldy, cstore, relu, lo, out_f32, ldr)
+    if w.numel() != _lib.load().iswm_qconv_weight_bytes(ctypes.byref(d)):
+        raise ValueError("qconv: weights %s do not match the geometry" % (tuple(w.shape),))
+    call("iswm_qconv_fwd", ctypes.byref(d), _p(x), _p(w), _p(mul), _p(add), _p(res), float(s_res), float(inv_s_out),
+         _p(out), _stream())
+    return out
+
+
+def absmax(x, amax, c=None, slab=None):
+    """amax (a 1-element fp32 device tensor) = max(amax, max |x|) over the first c channels of an fp32 NHWC or
+    Planes tensor.  Enqueues only."""
+    px, n, h, w, cc, ld, ps = xgeom(x)
+    c = cc if c is None else c
+    rows = n * h * w
+    nbytes = _lib.load().iswm_absmax_workspace(rows, c)
+    if slab is None or slab.numel() * 4 < nbytes:
+        slab = torch.empty((max(1, nbytes // 4),), dtype=torch.float32, device=amax.device)
+    call("iswm_absmax", _p(px), ps, rows, c, ld, _p(slab), nbytes, _p(amax), _stream())
+    return amax
+
+
+def quantize_i8(x, inv_s, lo, ldy=None, c=None, out=None):
+    """fp32 NHWC / Planes -> int8 NHWC: clamp(rint(x * inv_s), lo, 127) for the first c channels, 0 up to ldy"""
+    px, n, h, w, cc, ld, ps = xgeom(x)
+    c = cc if c is None else c
+    if out is None:
+        out = torch.empty((n, h, w, ldy or (c + 63) // 64 * 64), dtype=torch.int8, device=px.device)
+    _, _, _, _, ldo = i8geom(out)
+    if out.shape[3] != ldo:
+        raise ValueError("quantize_i8 writes whole pixels: out must not be a channel slice")
+    call("iswm_quantize_i8", _p(px), ps, n * h * w, c, ld, float(inv_s), int(lo), _p(out), ldo, _stream())
+    return out
+
+
+def qgap(x, s_in, inv_s_in, ldy=None):
+    """int8 global average pool [N,H,W,C] -> int8 [N,1,1,ldy] re-quantized with the input's scale"""
+    n, h, w, c, ldx = i8geom(x)
+    ldy = ldy or c
+    y = torch.zeros((n, 1, 1, ldy), dtype=torch.int8, device=x.device)
+    call("iswm_qgap", _p(x), n, h * w, c, ldx, float(s_in), float(inv_s_in), _p(y), ldy, _stream())
+    return y
+
+
+def qbcast(v, out):
+    """int8 [N,1,1,C] -> every pixel of `out` (an int8 [N,H,W,C] channel slice)"""
+    n, h, w, c, ldy = i8geom(out)
+    _, _, _, cv, ldv = i8geom(v)
+    if cv < c:
+        raise ValueError("qbcast: %d source channels for a %d-wide slice" % (cv, c))
+    call("iswm_qbcast", _p(v), n, h * w, c, ldv, _p(out), ldy, _stream())
+    return out
+
+
+def qbilinear(x, s_in, inv_s_out, out):
+    """int8 bilinear resize (align_corners=False) of x into `out` (an int8 channel slice of the destination size)"""
+    n, hi, wi, c, ldx = i8geom(x)
+    no, ho, wo, co, ldy = i8geom(out)
+    if no != n or co != c:
+        raise ValueError("qbilinear: %s does not fit %s" % (tuple(x.shape), tuple(out.shape)))
+    call("iswm_qbilinear", _p(x), n, hi, wi, c, ldx, float(s_in), ho, wo, float(inv_s_out), _p(out), ldy, _stream())
+    return out

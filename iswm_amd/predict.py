@@ -25,7 +25,10 @@ Same flags and defaults as the reference's get_argparser (predict.py:19-67).  Di
   * ``_predict.png`` is mode L with values 0 / 255 (this project's decode_target); the colour map of the
     reference's BinarySegmentation.decode_target is not in its tree and stays unpinned;
   * subfolders and files are walked in sorted order (the reference uses os.listdir order);
-  * messages are in English.
+  * messages are in English;
+  * ``--ckpt`` may name an INT8 checkpoint written by iswm_amd.quant (detected by its format tag): the frames then
+    run through QuantizedSegmentationModel.forward_lowres, and ``--model`` / ``--output_stride`` are taken from the
+    checkpoint.
 """
 import argparse
 import os
@@ -291,12 +294,14 @@ class DevicePredictor:
         return wait
 
 
-def load_model(model, ckpt_path):
+def load_model(model, ckpt_path, ck=None):
     """predict.py:80-91 with the weights-only loader: {"model_state": ...} (this project's and the reference's
-    checkpoints) or a bare state dict, `module.` prefixes stripped, strict load.  No file: initial weights."""
+    checkpoints) or a bare state dict, `module.` prefixes stripped, strict load.  No file: initial weights.
+    `ck`: the file's contents when the caller has read it already."""
     if ckpt_path is not None and os.path.isfile(ckpt_path):
-        from .train import load_checkpoint
-        ck = load_checkpoint(ckpt_path)
+        if ck is None:
+            from .train import load_checkpoint
+            ck = load_checkpoint(ckpt_path)
         state = ck["model_state"] if isinstance(ck, dict) and "model_state" in ck else ck
         state = {(k[7:] if k.startswith("module.") else k): v for k, v in state.items()}
         model.load_state_dict(state, strict=True)
@@ -321,9 +326,16 @@ def main(argv=None):
     print("Device: %s" % device)
 
     num_classes, fg = 2, 1                       # --dataset binary: prob[:, 1] (predict.py:267)
-    model = network.modeling.__dict__[opts.model](num_classes=num_classes, output_stride=opts.output_stride,
-                                                  pretrained_backbone=False)
-    model = load_model(model, opts.ckpt).to(device)
+    from . import quant
+    q, ck = quant.read_checkpoint(opts.ckpt) if opts.ckpt is not None and os.path.isfile(opts.ckpt) else (None, None)
+    if q is not None:
+        model = quant.load_int8(q, device)
+        print("INT8 model loaded from %s (%s, output stride %d)" % (opts.ckpt, q["arch"]["model"],
+                                                                     q["arch"]["output_stride"]))
+    else:
+        model = network.modeling.__dict__[opts.model](num_classes=num_classes, output_stride=opts.output_stride,
+                                                      pretrained_backbone=False)
+        model = load_model(model, opts.ckpt, ck).to(device)
     model.eval()
 
     predictor = DevicePredictor(model, device, num_classes, fg, opts.pred_threshold, opts.min_broken_prob,
