@@ -562,9 +562,9 @@ _CLS_FUSE = True      # False: the classifier as a conv of its own (tests compar
 def cls_fusable(conv, bn, relu, cls):
     """[Conv2d(.., 256, k) -> BatchNorm2d -> ReLU] followed by the 1x1 classifier Conv2d(256, num_classes <= 4, 1): the tail of both
     DeepLab heads (network/_deeplab.py:44-52, 84-90).  The classifier is then folded into the stage's BatchNorm passes
-    (csrc/bn_classify.hip).  Not while a test records ReLU patterns or a calibration records ranges (both need the stage's
-    stored output)."""
-    return (_CLS_FUSE and MASK_RECORDER is None and CALIB_RECORDER is None and relu is True and type(conv) is Conv2d and conv.out_channels == 256 and
+    (csrc/bn_classify.hip).  Not while a calibration records ranges (it needs the stage's stored output); a test's ReLU-pattern
+    recorder is served by cba_cls_fwd itself."""
+    return (_CLS_FUSE and CALIB_RECORDER is None and relu is True and type(conv) is Conv2d and conv.out_channels == 256 and
             conv.bias is None and type(cls) is Conv2d and cls.in_channels == 256 and cls.out_channels <= 4 and
             tuple(cls.kernel_size) == (1, 1) and tuple(cls.stride) == (1, 1) and tuple(cls.padding) == (0, 0) and
             bn.momentum is not None and bn.track_running_stats and bn.affine)
@@ -588,6 +588,10 @@ def cba_cls_fwd(conv, bn, cls, x, save):
     wc4 = ops.pad_weights(cls.weight, 4, 256).view(4, 256)
     b4 = None if cls.bias is None else ops.pad_weights(cls.bias.view(-1, 1, 1, 1), 4, 1).view(-1)
     logits = ops.bn_apply_classify(y, coef, wc4, b4)
+    if MASK_RECORDER is not None:
+        # the stage's ReLU pattern, as _cba_finish records it: the unfused apply on the same y and coefficients evaluates the
+        # fold's (y - mean) * scale + shift (tests/test_cls_fuse.py pins all of the fold's decisions to it bit for bit)
+        MASK_RECORDER[bn] = ops.bn_apply(y, coef, True) > 0
     ctx = dict(x=x, y=y, coef=coef, g=g, training=training, wc4=wc4, cls=cls, cls_fused=True) if save else None
     return logits, ctx
 

@@ -130,8 +130,7 @@ class OracleDeepLab:
         x = self._conv(x, "backbone.conv1.weight", 2, 3)
         x = self._relu(self._bn(x, "backbone.bn1"), "backbone.bn1", store=False)
         if self.pool_index is not None:
-            self.pool_gap = float((F.max_pool2d(x, 3, 2, 1) - _pool_select(x, self.pool_index)).detach().abs().max() /
-                                  x.detach().abs().max())          # how far the imposed choices are from this evaluation's maxima
+            self.pool_gap, self.pool_moved, self.pool_windows = pool_choice_stats(x.detach(), self.pool_index)
         x = self._store(F.max_pool2d(x, 3, 2, 1) if self.pool_index is None else _pool_select(x, self.pool_index))
         feats = OrderedDict()
         for li, L in enumerate(self.cfg.layers()):
@@ -182,6 +181,17 @@ class OracleDeepLab:
         return F.interpolate(y, size=input_shape, mode="bilinear", align_corners=False)
 
     __call__ = forward
+
+
+def pool_choice_stats(x, index):
+    """imposed max-pool window choices `index` against this evaluation's own: (largest gap between the window's maximum and the
+    imposed element, relative to max |x|; windows whose imposed tap is not ATen's own argmax; windows)"""
+    own, ind = F.max_pool2d(x, 3, 2, 1, return_indices=True)
+    gap = float((own - _pool_select(x, index)).abs().max() / x.abs().max())
+    w, (ho, wo) = x.shape[3], own.shape[2:]
+    oh, ow = torch.arange(ho).view(1, 1, ho, 1), torch.arange(wo).view(1, 1, 1, wo)
+    tap = (ind // w - (2 * oh - 1)) * 3 + (ind % w - (2 * ow - 1))       # flat input index -> kh * 3 + kw
+    return gap, int((tap != index.long()).sum()), tap.numel()
 
 
 def _pool_select(x, index):

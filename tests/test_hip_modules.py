@@ -87,6 +87,40 @@ class record_masks:
             o.pool_index = next(iter(self.pools.values())).permute(0, 3, 1, 2).cpu()
 
 
+class spy_calls:
+    """context manager: every library entry point called through ops.call while it is open, as (name, arguments with each
+    pointer replaced by "P") -- what ran, in order, independent of where torch's allocator put the tensors"""
+
+    def __enter__(self):
+        import ctypes
+        from iswm_amd import ops
+        self.ops, self.real, self.seq = ops, ops.call, []
+
+        def arg(a):
+            if a is None or isinstance(a, (int, float)):
+                return a
+            return "P" if isinstance(a, ctypes.c_void_p) else type(a).__name__
+
+        def spy(name, *a):
+            self.seq.append((name,) + tuple(arg(x) for x in a))
+            return self.real(name, *a)
+        ops.call = spy
+        return self
+
+    def __exit__(self, *a):
+        self.ops.call = self.real
+
+    def count(self, name):
+        return sum(1 for c in self.seq if c[0] == name)
+
+
+def assert_fold_ran(calls, steps=1):
+    """the training step under comparison ran the folded classifier (csrc/bn_classify.hip), forward and backward: the same-mask
+    comparisons record ReLU patterns, and before the recorder served the fold they silently took the unfolded head"""
+    assert calls.count("iswm_bn_apply_classify") == steps and calls.count("iswm_bn_backward_classify") == steps, \
+        (calls.count("iswm_bn_apply_classify"), calls.count("iswm_bn_backward_classify"))
+
+
 def check_sign_patterns(o, masks):
     """every disagreement between the oracle's own ReLU signs and the HIP path's is a near-tie"""
     total = bad = 0
@@ -98,8 +132,23 @@ def check_sign_patterns(o, masks):
         if mism.any():
             assert float(z[mism].abs().max()) <= RTOL * float(z.abs().max()), site
     assert bad <= max(3, 1e-4 * total), (bad, total)
-    assert getattr(o, "pool_gap", 0.0) <= RTOL, o.pool_gap        # imposed max-pool choices: near-ties of the oracle's own maxima
+    if getattr(o, "pool_index", None) is not None:
+        check_pool_choices(o)
     return bad, total
+
+
+POOL_GAP = 1e-5     # of max |x|: fp32 vs bf16x6 / fp32-MFMA stems put genuine near-ties at ~1e-6
+
+
+def check_pool_choices(o):
+    """the stem max-pool's imposed window choices are near-ties of the oracle's own maxima (gap <= POOL_GAP of max |x|) and,
+    like ReLU flips, rare: at most max(3, 1e-4 of the windows) differ from the oracle's own argmax"""
+    import os
+    if os.environ.get("ISWM_TEST_REPORT"):
+        with open(os.environ["ISWM_TEST_REPORT"], "a") as f:
+            f.write("pool choices: gap %.3e, %d of %d windows re-routed\n" % (o.pool_gap, o.pool_moved, o.pool_windows))
+    assert o.pool_gap <= POOL_GAP, o.pool_gap
+    assert o.pool_moved <= max(3, 1e-4 * o.pool_windows), (o.pool_moved, o.pool_windows)
 
 
 def oracle_for(sd, rates=(6, 12, 18)):
@@ -234,10 +283,23 @@ def _build(backbone, os_, num_classes=2):
     return m.to(dev()), cfg, sd
 
 
-@pytest.mark.parametrize("tag,backbone,os_", [("r50_os16", "resnet50", 16), ("r101_os8", "resnet101", 8)])
-def test_whole_model(tag, backbone, os_):
+@pytest.mark.parametrize("tag,backbone,os_,fold", [
+    pytest.param("r50_os16", "resnet50", 16, True, id="r50_os16-resnet50-16"),
+    pytest.param("r50_os16", "resnet50", 16, False, id="r50_os16-resnet50-16-unfolded"),
+    pytest.param("r101_os8", "resnet101", 8, True, id="r101_os8-resnet101-8")])
+def test_whole_model(tag, backbone, os_, fold):
     """logits, bit-exact argmax mask, loss, gradients and BN running stats of one training
-    step on [2,3,65,65] vs the reference's _segm_resnet + nn.CrossEntropyLoss(weight)."""
+    step on [2,3,65,65] vs the reference's _segm_resnet + nn.CrossEntropyLoss(weight).  The training step runs the folded
+    classifier (the product's step); `unfolded` pins the classifier as a conv of its own (_hip._CLS_FUSE = False)."""
+    from iswm_amd.network import _hip
+    try:
+        _hip._CLS_FUSE = fold
+        _whole_model(tag, backbone, os_, fold)
+    finally:
+        _hip._CLS_FUSE = True
+
+
+def _whole_model(tag, backbone, os_, fold):
     from iswm_amd import ops
     from iswm_amd.utils.loss import CrossEntropyLoss
     from oracle import loss as oloss
@@ -288,12 +350,17 @@ def test_whole_model(tag, backbone, os_):
     # and any fp32 implementation is only good to ~1e-2 on that branch's contribution.
     m.load_state_dict(sd, strict=True)
     x4 = synth_images(8, 65, 65, seed=72)
-    with record_masks(m, "") as rec:
-        lg4 = m(x4.to(dev()))
-    for p in m.parameters():
-        p.grad = None
-    up = upstream(lg4.shape, 12)
-    lg4.backward(up.to(dev()))
+    with spy_calls() as calls:
+        with record_masks(m, "") as rec:
+            lg4 = m(x4.to(dev()))
+        for p in m.parameters():
+            p.grad = None
+        up = upstream(lg4.shape, 12)
+        lg4.backward(up.to(dev()))
+    if fold:
+        assert_fold_ran(calls)
+    else:
+        assert calls.count("iswm_bn_apply_classify") == 0 and calls.count("iswm_bn_backward_classify") == 0
     o = OracleDeepLab(cfg, sd, dropout_p=0.0).train()
     rec.apply_to(o)
     lgo = o(x4)
@@ -337,11 +404,13 @@ def test_train_steps_match_oracle():
     for it in range(3):
         x = synth_images(6, 81, 81, seed=100 + it)      # batch 6: see the image-pooling note above
         lab = synth_labels(6, 81, 81, seed=100 + it, p_fg=0.2, p_ignore=0.05)
-        with record_masks(m, "") as rec:
-            lg = m(x.to(dev()))
-        l = crit(lg, lab.to(dev()))
-        opt.zero_grad()
-        l.backward()
+        with spy_calls() as calls:
+            with record_masks(m, "") as rec:
+                lg = m(x.to(dev()))
+            l = crit(lg, lab.to(dev()))
+            opt.zero_grad()
+            l.backward()
+        assert_fold_ran(calls)
         opt.step()
         rec.apply_to(o)
         lo = oloss.weighted_ce(o(x), lab, w)
@@ -371,6 +440,124 @@ def test_train_steps_match_oracle():
     assert int(msd["backbone.bn1.num_batches_tracked"]) == 3
 
 
+def test_train_steps_undamped_vs_float64():
+    """test_train_steps_match_oracle's three SGD-nesterov steps WITHOUT its bn3 damping -- gamma ~ 1 on every residual branch,
+    torchvision's default initialisation and the ill-conditioned case -- against a float64 oracle, with an fp32 oracle as the
+    yardstick; both oracles follow the HIP path's ReLU patterns and max-pool choices at every step.  Every step's loss and the
+    BatchNorm buffers within 1e-3 of float64; per parameter tensor, the HIP update's error against float64 at most
+    3 x max(the fp32 oracle's, 1e-3): no worse than a plain fp32 evaluation of the same steps.  Measured on an MI355X (bf16x6 /
+    fp32 MFMA): loss 3.0e-5 / 1.0e-5, buffers 9.6e-5 / 8.0e-5, worst update error 1.19e-3 / 1.57e-3 against the fp32 oracle's
+    9.8e-4 / 1.53e-3, worst ratio to max(fp32, 1e-3) 1.19 / 1.38."""
+    import os
+    from iswm_amd.optim import FusedSGD
+    from iswm_amd.utils.loss import CrossEntropyLoss
+    from oracle import loss as oloss
+    from oracle.deeplab import OracleDeepLab
+    from oracle.optim import OracleSGD
+    from oracle.synth import synth_images, synth_labels
+    m, cfg, sd = _build("resnet50", 16)
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    o32, o64 = OracleDeepLab(cfg, sd, dropout_p=0.0).train(), OracleDeepLab(cfg, sd64, dropout_p=0.0).train()
+    lr = 1e-3
+    opt32, opt64 = OracleSGD(o32.parameters(), lr=lr), OracleSGD(o64.parameters(), lr=lr)
+    opt = FusedSGD(m.parameters(), lr=lr, momentum=0.9, weight_decay=1e-4, nesterov=True)
+    w = torch.tensor([1.0, 3.0])
+    crit = CrossEntropyLoss(weight=w)
+    m.train()
+    loss_err = 0.0
+    for it in range(3):
+        x = synth_images(6, 81, 81, seed=100 + it)
+        lab = synth_labels(6, 81, 81, seed=100 + it, p_fg=0.2, p_ignore=0.05)
+        with spy_calls() as calls:
+            with record_masks(m, "") as rec:
+                lg = m(x.to(dev()))
+            l = crit(lg, lab.to(dev()))
+            opt.zero_grad()
+            l.backward()
+        assert_fold_ran(calls)
+        opt.step()
+        for o, oopt, xx, ww in ((o32, opt32, x, w), (o64, opt64, x.double(), w.double())):
+            rec.apply_to(o)
+            lo = oloss.weighted_ce(o(xx), lab, ww)
+            o.zero_grad()
+            lo.backward()
+            oopt.step()
+        # (no near-tie rule on the imposed patterns here: undamped, two fp32 evaluations of the decoder's last stage already
+        # differ by ~2e-3 of its scale after the first update -- the ill-conditioning this test is about)
+        loss_err = max(loss_err, rel_err(l, lo.detach()))
+    s32, s64, sh = o32.state_dict(), o64.state_dict(), m.state_dict()
+    worst_b, worst_h, worst_32, worst_r = (0.0, ""), (0.0, ""), (0.0, ""), (0.0, "")
+    for k in s64:
+        if not s64[k].is_floating_point():
+            continue
+        if "running_" in k:
+            worst_b = max(worst_b, (rel_err(sh[k], s64[k]), k))
+            continue
+        du64 = s64[k] - sd64[k]
+        slack = 4 * 1.2e-7 * float(sd[k].abs().max())          # the fp32 parameters' own rounding
+        def err(p):
+            return max(0.0, float((p.cpu().double() - sd64[k] - du64).abs().max()) - slack) / float(du64.abs().max())
+        eh, e32 = err(sh[k]), err(s32[k])
+        worst_h, worst_32 = max(worst_h, (eh, k)), max(worst_32, (e32, k))
+        worst_r = max(worst_r, (eh / max(e32, 1e-3), k))
+    if os.environ.get("ISWM_TEST_REPORT"):
+        with open(os.environ["ISWM_TEST_REPORT"], "a") as f:
+            f.write("undamped steps vs fp64: loss %.2e, buffers %.2e (%s), update err hip %.3e (%s) fp32 oracle %.3e (%s), "
+                    "worst hip / max(fp32, 1e-3) %.3f (%s)\n" % ((loss_err,) + worst_b + worst_h + worst_32 + worst_r))
+    assert loss_err <= RTOL, loss_err
+    assert worst_b[0] <= RTOL, worst_b
+    assert worst_r[0] <= 3.0, (worst_r, worst_h, worst_32)
+    assert int(sh["backbone.bn1.num_batches_tracked"]) == 3
+
+
+def test_mask_recorder_leaves_the_step_alone():
+    """the same-mask recorder does not change what a training step runs: with MASK_RECORDER / POOL_RECORDER set, the library calls
+    of one forward + loss + backward are the plain step's, in order and with the same arguments, plus one iswm_bn_apply_pl (ReLU,
+    fp32 out, no residual) right after the folded classifier's forward -- the pattern it records -- and the recorder's reads of
+    pre-split stage outputs (iswm_join_planes)"""
+    from iswm_amd.network import _hip
+    from iswm_amd.utils.loss import CrossEntropyLoss
+    from oracle.synth import synth_images, synth_labels
+    m, cfg, sd = _build("resnet50", 16)
+    m.train()
+    x = synth_images(4, 65, 65, seed=41).to(dev())
+    lab = synth_labels(4, 65, 65, seed=41, p_fg=0.2).to(dev())
+    crit = CrossEntropyLoss(weight=torch.tensor([1.0, 3.0]))
+
+    def step(record):
+        for p in m.parameters():
+            p.grad = None
+        rec = {}
+        with spy_calls() as calls:
+            _hip.MASK_RECORDER, _hip.POOL_RECORDER = (rec, {}) if record else (None, None)
+            try:
+                lg = m(x)
+            finally:
+                _hip.MASK_RECORDER = _hip.POOL_RECORDER = None
+            crit(lg, lab).backward()
+        torch.cuda.synchronize()
+        return calls.seq, rec
+    step(False)                                   # one-time setup (weight packing, plans) out of the comparison
+    plain, _ = step(False)
+    recorded, masks = step(True)
+    assert step(False)[0] == plain
+    folds = [j + 1 for j, c in enumerate(recorded) if c[0] == "iswm_bn_apply_classify"]
+    assert len(folds) == 1 and m.classifier.classifier[1] in masks
+    for j in folds:
+        # iswm_bn_apply_pl(y, M, C, ldy, scale, shift, mean, residual None, 0, 0, relu 1, out, ldo C, plane stride 0, stream)
+        assert recorded[j][:5] == ("iswm_bn_apply_pl",) + recorded[j - 1][1:5], (recorded[j - 1], recorded[j])
+        assert recorded[j][8:] == (None, 0, 0, 1, "P", 256, 0, "P"), recorded[j]
+    i = 0
+    for c in (c for j, c in enumerate(recorded) if j not in folds):
+        if i < len(plain) and c == plain[i]:
+            i += 1
+        else:
+            assert c[0] == "iswm_join_planes", (i, c)
+    assert i == len(plain)
+    mk = masks[m.classifier.classifier[1]]
+    assert mk.dtype == torch.bool and mk.shape == (4, 17, 17, 256) and 0.2 < float(mk.float().mean()) < 0.8
+
+
 def test_full_size_step_vs_oracle():
     """BASELINE.json configs[1] geometry (deeplabv3plus_resnet50, output_stride 16, 513 x 513) against the CPU oracle at
     FULL size: eval logits, train logits and weighted-CE loss element-wise at 1e-3, and every parameter gradient
@@ -393,12 +580,14 @@ def test_full_size_step_vs_oracle():
     assert rel_err(lg_e, ref_e) <= RTOL
     del lg_e, ref_e
     m.train()
-    with record_masks(m, "") as rec:
-        lg = m(x.to(dev()))
-    loss = CrossEntropyLoss(weight=w, ignore_index=255)(lg, lab.to(dev()))
-    for p in m.parameters():
-        p.grad = None
-    loss.backward()
+    with spy_calls() as calls:
+        with record_masks(m, "") as rec:
+            lg = m(x.to(dev()))
+        loss = CrossEntropyLoss(weight=w, ignore_index=255)(lg, lab.to(dev()))
+        for p in m.parameters():
+            p.grad = None
+        loss.backward()
+    assert_fold_ran(calls)                # M = 4 x 129 x 129: the fold's 1024-tile cap is reached end to end
     o = OracleDeepLab(cfg, sd, dropout_p=0.0).train()
     rec.apply_to(o)
     lgo = o(x)
@@ -612,15 +801,17 @@ def test_whole_model_v3_head_5_channel_stem():
     sure = margin > 2 * RTOL * np.abs(fx["eval_logits"]).max()
     assert (ops.argmax_nchw(lg).cpu().numpy()[sure] == fx["eval_mask"][sure]).all()
     m.train()
-    with record_masks(m, "") as rec:
-        lg = m(x.to(dev()))
-    assert rel_err(lg, fx["train_logits"]) <= RTOL
-    loss = CrossEntropyLoss(weight=torch.tensor([1.0, 3.0]), ignore_index=255)(lg, labels.to(dev()))
-    assert rel_err(loss, fx["loss"]) <= RTOL
-    for p in m.parameters():
-        p.grad = None
-    up = upstream(lg.shape, 14)
-    lg.backward(up.to(dev()))
+    with spy_calls() as calls:
+        with record_masks(m, "") as rec:
+            lg = m(x.to(dev()))
+        assert rel_err(lg, fx["train_logits"]) <= RTOL
+        loss = CrossEntropyLoss(weight=torch.tensor([1.0, 3.0]), ignore_index=255)(lg, labels.to(dev()))
+        assert rel_err(loss, fx["loss"]) <= RTOL
+        for p in m.parameters():
+            p.grad = None
+        up = upstream(lg.shape, 14)
+        lg.backward(up.to(dev()))
+    assert_fold_ran(calls)                # DeepLabHead: ASPP -> 3x3 -> BN -> ReLU -> folded 1x1
     o = OracleDeepLab(cfg, sd, dropout_p=0.0).train()
     rec.apply_to(o)
     lgo = o(x)
@@ -876,12 +1067,14 @@ def test_fix_bn_training_step():
             mod.eval()
     x = synth_images(4, 65, 65, seed=61)
     lab = synth_labels(4, 65, 65, seed=61, p_fg=0.2)
-    with record_masks(m, "") as rec:
-        lg = m(x.to(dev()))
-    for p in m.parameters():
-        p.grad = None
-    up = upstream(lg.shape, 15)
-    lg.backward(up.to(dev()))
+    with spy_calls() as calls:
+        with record_masks(m, "") as rec:
+            lg = m(x.to(dev()))
+        for p in m.parameters():
+            p.grad = None
+        up = upstream(lg.shape, 15)
+        lg.backward(up.to(dev()))
+    assert_fold_ran(calls)                # eval-mode BatchNorm in a training step: k_bn_bwd_apply_cls<false>
     for k, v in m.state_dict().items():
         if "running" in k or "num_batches" in k:
             assert torch.equal(v.cpu(), sd[k]), k                # frozen statistics

@@ -296,3 +296,29 @@ def test_oracle_pool_select_is_maxpool_for_its_own_argmax():
     (gx,) = torch.autograd.grad(ys, x, g, retain_graph=True)
     (gr,) = torch.autograd.grad(y, x, g)
     assert torch.equal(gx != 0, gr != 0) and rel_err(gx, gr) < 1e-6
+
+
+def test_oracle_pool_choice_stats_counts_rerouted_windows():
+    """pool_choice_stats (the stem max-pool rule of smoke() and tests/test_hip_modules.py::check_pool_choices): the oracle's own
+    argmax gives gap 0 and no re-routed window; moving three windows to their second-largest element counts exactly three, with
+    the gap of the largest move.  Ties in a window of zeros (after the ReLU) resolve to the first tap, as ATen and the HIP kernel do."""
+    import torch.nn.functional as F
+    from oracle.deeplab import pool_choice_stats
+    x = F.relu(torch.randn(2, 5, 9, 11, generator=torch.Generator().manual_seed(6)))
+    x[0, 0, :3, :3] = 0.0                                                    # window (0, 0) and its neighbours: exact ties
+    y, ind = F.max_pool2d(x, 3, 2, 1, return_indices=True)
+    ho, wo = y.shape[2:]
+    oh, ow = torch.arange(ho).view(1, 1, ho, 1), torch.arange(wo).view(1, 1, 1, wo)
+    tap = ((ind // 11 - (2 * oh - 1)) * 3 + (ind % 11 - (2 * ow - 1))).to(torch.uint8)
+    assert pool_choice_stats(x, tap) == (0.0, 0, tap.numel())
+    assert int(tap[0, 0, 0, 0]) == 4                                         # first in-bounds tap of an all-zero window
+    moved, gaps = tap.clone(), []
+    xp = F.pad(x, (1, 1, 1, 1), value=float("-inf"))
+    for n, c, i, j in ((0, 1, 2, 3), (1, 4, 0, 5), (1, 2, 4, 1)):
+        win = xp[n, c, 2 * i:2 * i + 3, 2 * j:2 * j + 3].reshape(9)
+        second = int(win.argsort(descending=True)[1])
+        moved[n, c, i, j] = second
+        gaps.append(float(win.max() - win[second]))
+    gap, count, windows = pool_choice_stats(x, moved)
+    assert count == 3 and windows == tap.numel()
+    assert gap == pytest.approx(max(gaps) / float(x.abs().max()), rel=1e-6) and gap > 0
