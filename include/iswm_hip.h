@@ -419,6 +419,34 @@ int iswm_augment_batch(const unsigned char* images, const unsigned char* labels,
                        const int* tables, int B, int crop_h, int crop_w, const float* mean3, const float* std3,
                        float* out_nchw, unsigned char* out_labels, iswm_stream_t stream);
 
+/* ---- GPU-resident tile store (dataset.hip) ------------------------------------------
+ * A data set is decoded once into two uint8 device arenas (images HWC RGB, masks HW); every tile starts at a
+ * multiple of 16 bytes.  No atomics: per-workgroup partial counts go to the workspace and are summed by one
+ * workgroup in index order.  All pointers are device pointers unless stated; the entry points only enqueue.
+ * label_prepare: in place, every non-zero byte of the nbytes-long label arena (nbytes % 16 == 0, 16-byte aligned)
+ * becomes 1; counts[2] (int64) = {n(0), n(1)} of the result (alignment padding, being 0, is counted in n(0)).
+ * label_count: ADDS {n(label == 0), n(label == 1), n(other)} of n uint8 labels (16-byte aligned) to the int64
+ * accumulator counts_accum[3]; a label equal to ignore_index (-1: none) is counted as other.
+ * aug_tables: fills, for each of the B iswm_aug_sample records, the table block iswm_augment_batch reads at
+ * tab_off from src_h, src_w, rs_h, rs_w, ksize_h, ksize_v alone -- Pillow's bounds, 22-bit integer weights and
+ * nearest indices, the same int32 values the host computes (fp64, uncontracted, same operation order).  max_rs >=
+ * every rs_h and rs_w (sizes the grid).  A record whose block would end past tables_bytes is left unwritten.
+ * iswm_aug_tables_workspace(HOST copy of the records, B) = bytes the table buffer needs (0: a bad record).
+ * gather_normalize: B tiles of H x W at offsets[B][2] = (image byte offset, label byte offset), multiples of 16,
+ * -> fp32 NCHW [B][3][H][W] with iswm_predict_normalize's arithmetic and the uint8 labels [B][H][W], one launch.
+ * mean3 / std3 are HOST arrays of 3 floats. */
+size_t iswm_label_prepare_workspace(long long nbytes);
+int iswm_label_prepare(unsigned char* labels, long long nbytes, long long* counts, void* workspace,
+                       size_t workspace_bytes, iswm_stream_t stream);
+size_t iswm_label_count_workspace(long long n);
+int iswm_label_count(const unsigned char* labels, long long n, int ignore_index, long long* counts_accum,
+                     void* workspace, size_t workspace_bytes, iswm_stream_t stream);
+size_t iswm_aug_tables_workspace(const void* host_samples, int B);
+int iswm_aug_tables(const void* samples, int B, int max_rs, int* tables, size_t tables_bytes, iswm_stream_t stream);
+int iswm_gather_normalize(const unsigned char* images, const unsigned char* labels, const long long* offsets, int B,
+                          int H, int W, const float* mean3, const float* std3, float* out_nchw,
+                          unsigned char* out_labels, iswm_stream_t stream);
+
 /* ---- inference outputs (predict.hip) ------------------------------------------------
  * predict_normalize: uint8 [N][H][W][3] RGB -> fp32 NCHW [N][3][H][W], (v / 255.0f - mean) / std in IEEE fp32
  * (ToTensor + Normalize, predict.py:93-97).

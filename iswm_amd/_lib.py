@@ -122,6 +122,13 @@ _SIGS = {
     "iswm_loss_bwd_scale": (c_int, [P, c_int64, P, P, c_int, c_int64, P]),
     "iswm_argmax_nchw": (c_int, [P, c_int, c_int, c_int64, P, P]),
     "iswm_augment_batch": (c_int, [P, P, P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P, P]),
+    "iswm_label_prepare_workspace": (c_size_t, [c_int64]),
+    "iswm_label_prepare": (c_int, [P, c_int64, P, P, c_size_t, P]),
+    "iswm_label_count_workspace": (c_size_t, [c_int64]),
+    "iswm_label_count": (c_int, [P, c_int64, c_int, P, P, c_size_t, P]),
+    "iswm_aug_tables_workspace": (c_size_t, [P, c_int]),
+    "iswm_aug_tables": (c_int, [P, c_int, c_int, P, c_size_t, P]),
+    "iswm_gather_normalize": (c_int, [P, P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P, P]),
     "iswm_confusion_matrix": (c_int, [P, c_int, P, c_int, c_int64, c_int, P, P]),
     "iswm_confusion_matrix_logits": (c_int, [P, c_int, P, c_int, c_int, c_int64, c_int, P, P]),
     "iswm_mask_morph": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),

@@ -7,7 +7,9 @@ forced by the reference not being runnable as shipped:
 
   * data: ``--dataset synthetic`` (default) generates seeded tiles with the reference's
     ``(image float32 [3,H,W], label uint8 [H,W])`` tuple contract, ``.images`` list and
-    ``decode_target``; the DVC/S3 ``BinarySegmentation`` set is not in the reference tree;
+    ``decode_target``; ``--dataset binary`` reads ``<data_root>/{train,val}/{imgs,masks}`` (datasets.py: the
+    reference's ``BinarySegmentation`` is not in its tree, the file convention is), decodes both splits once into
+    device memory and augments / validates from there (DESIGN.md section 11);
   * ``--model`` is honoured (the reference always builds resnet50, train.py:412-419);
   * ``--loss_type`` defaults to IWce_loss (the reference's default 'cross_entropy' is not in its own
     choices and yields ``None``);
@@ -33,7 +35,7 @@ from torch.utils import data
 from . import network, ops
 from .optim import FusedAdam, FusedAdamW, FusedSGD
 from .parallel import DistributedDataParallelHIP
-from .utils.loss import CrossEntropyLoss, calculate_class_weights
+from .utils.loss import CrossEntropyLoss, calculate_class_weights, calculate_class_weights_resident
 
 
 def get_argparser():
@@ -77,7 +79,8 @@ def get_argparser():
     # additions
     parser.add_argument("--synthetic_len", type=int, default=256, help="tiles in the synthetic train split")
     parser.add_argument("--num_workers", type=int, default=2,
-                        help="DataLoader worker processes of the train loader (the reference hard-codes 4, train.py:950)")
+                        help="DataLoader worker processes of the train loader (the reference hard-codes 4, train.py:950); "
+                             "with --dataset binary: the threads that decode the files once (1 to 16)")
     parser.add_argument("--device_augment", action='store_true', default=False,
                         help="run the reference's train_transform (random scale / crop / flip / normalise, "
                              "train.py:355-362) as one HIP kernel per batch on uint8 tiles")
@@ -118,12 +121,24 @@ class SyntheticBinarySegmentation(data.Dataset):
 
 
 def get_dataset(opts):
-    if opts.dataset != 'synthetic':
-        raise NotImplementedError("the BinarySegmentation dataset (DVC/S3, data.dvc) is not part of this build")
+    if opts.dataset == 'binary':
+        from .datasets import BinarySegmentation
+        return (BinarySegmentation(opts.data_root, split='train'), BinarySegmentation(opts.data_root, split='val'))
     return (SyntheticBinarySegmentation(split='train', size=opts.crop_size, length=opts.synthetic_len,
                                         seed=opts.random_seed, raw=opts.device_augment),
             SyntheticBinarySegmentation(split='val', size=opts.crop_size, length=max(8, opts.val_batch_size * 2),
                                         seed=opts.random_seed))
+
+
+def epoch_batches(n, batch_size, seed, epoch, rank=0, world=1):
+    """tile indices of one epoch's batches for one rank over a resident store of n tiles: the order is
+    torch.randperm(n) from a generator seeded with (seed, epoch) -- identical on every rank --, the last partial
+    batch is dropped and rank r takes the batches r, r + world, ... (every rank the same number of them)"""
+    g = torch.Generator()
+    g.manual_seed((int(seed) * 1000003 + int(epoch)) % (2 ** 63))
+    order = torch.randperm(n, generator=g).tolist()
+    nb = n // batch_size // world * world
+    return [order[b * batch_size:(b + 1) * batch_size] for b in range(rank, nb, world)]
 
 
 def load_checkpoint(path):
@@ -328,19 +343,64 @@ def main(argv=None):
     random.seed(opts.random_seed)
 
     train_dst, val_dst = get_dataset(opts)
+    if opts.dataset == 'binary':
+        return _main_resident(opts, train_dst, val_dst, device, rank, world)
+    return _main_loader(opts, train_dst, val_dst, device, rank, world)
+
+
+def _train_transform(opts, et):
+    """the reference's train_transform (train.py:355-362)"""
+    return et.ExtCompose([
+        et.ExtRandomScale((0.5, 2.0)),
+        et.ExtRandomCrop(size=(opts.crop_size, opts.crop_size), pad_if_needed=True),
+        et.ExtRandomHorizontalFlip(),
+        et.ExtToTensor(),
+        et.ExtNormalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225]),
+    ])
+
+
+def _main_resident(opts, train_dst, val_dst, device, rank, world):
+    """--dataset binary: both splits live on the device (datasets.DeviceTileStore); a training batch is
+    ExtCompose.batch_resident over the epoch's index order, a validation batch is iswm_gather_normalize"""
+    from .datasets import DeviceTileStore
+    from .utils import ext_transforms as et
+    workers = max(1, min(16, opts.num_workers))
+    if rank == 0:
+        print("Dataset binary: device pipeline (tiles decoded once by %d threads, resident on %s; augmentation and "
+              "validation batches are built there)" % (workers, device))
+    val_store = DeviceTileStore(val_dst, device, workers=workers)
+    if opts.val_metrics == 'sequence' and not val_store.uniform_size:
+        raise ValueError("--val_metrics sequence needs validation tiles of ONE size (its windows stack consecutive "
+                         "frames); %s holds tiles of mixed sizes: %s" %
+                         (val_dst.img_dir, sorted(set(m[2:] for m in val_store.meta))))
+    val_loader = val_store.batches(opts.val_batch_size)
+    if opts.test_only:                        # nothing of the train split is needed to score a checkpoint
+        return _run(opts, device, rank, world, None, 0, val_loader, torch.ones(2))
+    train_store = DeviceTileStore(train_dst, device, workers=workers)
+    per_rank = len(epoch_batches(len(train_store), opts.batch_size, opts.random_seed, 0, rank, world))
+    if per_rank < 1:
+        raise ValueError("%d train tiles give no full batch of %d on each of %d ranks" %
+                         (len(train_store), opts.batch_size, world))
+    transform = _train_transform(opts, et)
+
+    def epoch(e):
+        for idx in epoch_batches(len(train_store), opts.batch_size, opts.random_seed, e, rank, world):
+            yield transform.batch_resident(train_store, idx)
+    # the reference's class weights: one pass of the AUGMENTED train loader (train.py:388-410), here epoch 0's order
+    class_weights = calculate_class_weights_resident(epoch(0), dist.group.WORLD if world > 1 else None)
+    if rank == 0:
+        print("Class weights - Black: %.4f, White: %.4f" % (class_weights[0], class_weights[1]))
+    return _run(opts, device, rank, world, epoch, per_rank, val_loader, class_weights)
+
+
+def _main_loader(opts, train_dst, val_dst, device, rank, world):
     sampler = data.distributed.DistributedSampler(train_dst, world, rank, shuffle=True, drop_last=True) \
         if world > 1 else None
     train_transform = None
     if opts.device_augment:
         # the reference's train_transform (train.py:355-362) as one HIP kernel per batch over uint8 tiles on the GPU
         from .utils import ext_transforms as et
-        train_transform = et.ExtCompose([
-            et.ExtRandomScale((0.5, 2.0)),
-            et.ExtRandomCrop(size=(opts.crop_size, opts.crop_size), pad_if_needed=True),
-            et.ExtRandomHorizontalFlip(),
-            et.ExtToTensor(),
-            et.ExtNormalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225]),
-        ])
+        train_transform = _train_transform(opts, et)
     train_loader = data.DataLoader(train_dst, batch_size=opts.batch_size, shuffle=sampler is None, sampler=sampler,
                                    num_workers=opts.num_workers, drop_last=True)
     val_loader = data.DataLoader(val_dst, batch_size=opts.val_batch_size, shuffle=False, num_workers=0)
@@ -348,6 +408,22 @@ def main(argv=None):
     if rank == 0:
         print("Class weights - Black: %.4f, White: %.4f" % (class_weights[0], class_weights[1]))
 
+    def epoch(e):
+        if sampler is not None:
+            sampler.set_epoch(e)
+        for images, labels in train_loader:
+            if train_transform is not None:
+                yield train_transform.batch(list(images.to(device, non_blocking=True)),
+                                            list(labels.to(device, non_blocking=True)))
+            else:
+                yield (images.to(device, dtype=torch.float32, non_blocking=True), labels.to(device, non_blocking=True))
+    return _run(opts, device, rank, world, epoch, len(train_loader), val_loader, class_weights)
+
+
+def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_weights):
+    """model, optimizer, criterion, resume, then the step loop over `epoch(e)` -- an iterable of device batches
+    (images float32 [B,3,H,W], labels) for epoch number e, `batches_per_epoch` of them on this rank"""
+    class_weights = class_weights.to(device)
     model = setup_model(opts)
     cur_itrs, best_score = 0, -1.0
     ckpt = None
@@ -389,21 +465,13 @@ def main(argv=None):
     t_last, n_last = time.time(), 0
     # a resumed run continues the epoch count where it stopped (train.py:997): DistributedSampler.set_epoch would otherwise
     # replay the shuffles the run already consumed
-    cur_epochs = cur_itrs // max(1, len(train_loader))
+    cur_epochs = cur_itrs // max(1, batches_per_epoch)
     if rank == 0 and cur_itrs:
         print("Resuming at iteration %d (epoch %d)" % (cur_itrs, cur_epochs))
     while cur_itrs < opts.total_itrs:
         cur_epochs += 1
-        if sampler is not None:
-            sampler.set_epoch(cur_epochs)
-        for images, labels in train_loader:
+        for images, labels in epoch(cur_epochs):
             cur_itrs += 1
-            if train_transform is not None:
-                images, labels = train_transform.batch(list(images.to(device, non_blocking=True)),
-                                                       list(labels.to(device, non_blocking=True)))
-            else:
-                images = images.to(device, dtype=torch.float32, non_blocking=True)
-                labels = labels.to(device, non_blocking=True)
             logits = net(images)
             loss = criterion(logits, labels)
             optimizer.zero_grad()

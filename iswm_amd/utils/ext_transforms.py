@@ -107,11 +107,30 @@ class _AugSample(ctypes.Structure):
                 ("reserved", ctypes.c_int)]
 
 
-class ExtCompose(object):
-    """Same constructor as the reference (a list of the Ext* transforms above).  `batch()` is the device path."""
+# the same 64 bytes as a numpy record, for filling a pinned buffer without a Python object per field
+_AUG_DTYPE = np.dtype([(n, "<i8" if t is ctypes.c_longlong else "<i4") for n, t in _AugSample._fields_])
 
-    def __init__(self, transforms):
+
+def _ksize(in_size, out_size):
+    """taps per output index, as _resample_tables computes them (one division and one ceil: stays on the host)"""
+    scale = float(in_size) / float(out_size)
+    support = 1.0 * (scale if scale >= 1.0 else 1.0)
+    return int(math.ceil(support)) * 2 + 1
+
+
+class ExtCompose(object):
+    """Same constructor as the reference (a list of the Ext* transforms above).  `batch()` is the device path;
+    `batch_resident()` is the same path fed from a DeviceTileStore, with the tables computed on the device.
+    `ring_depth`: pinned parameter buffers `batch_resident` rotates through (how many batches the host may run ahead
+    of the device before it waits for the oldest parameter copy)."""
+
+    def __init__(self, transforms, ring_depth=4):
         self.transforms = transforms
+        if int(ring_depth) < 1:
+            raise ValueError("ring_depth must be at least 1 (got %r)" % (ring_depth,))
+        self.ring_depth = int(ring_depth)
+        self._ring = [[None, None] for _ in range(self.ring_depth)]     # [pinned uint8 buffer, event behind its last copy]
+        self._ring_pos = 0
         self.scale = self.crop = self.hflip = self.norm = None
         for t in transforms:
             if isinstance(t, ExtRandomScale):
@@ -201,6 +220,56 @@ class ExtCompose(object):
         _lib.load()
         call("iswm_augment_batch", img_buf.data_ptr(), lbl_buf.data_ptr(), sbuf.data_ptr(), tables.data_ptr(), B, th, tw,
              mean, std, out.data_ptr(), out_lbl.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        return out, out_lbl
+
+    def batch_resident(self, store, indices, params=None):
+        """`batch()` over tiles `indices` of a datasets.DeviceTileStore, without the host touching a table or a pixel:
+        the parameters are drawn in index order (the `random` stream is consumed exactly as `batch` consumes it), the
+        64-byte records go up from a ring of pinned buffers with a non-blocking copy, iswm_aug_tables fills Pillow's
+        tables on the device and iswm_augment_batch reads the store's arenas in place.  Nothing here waits for the
+        device, except that a pinned buffer is rewritten only after the event behind its previous copy has completed:
+        a caller more than `ring_depth` batches ahead waits there for the oldest copy.  Same results as `batch`, bit
+        for bit."""
+        B = len(indices)
+        if B < 1:
+            raise ValueError("need at least one tile index")
+        th, tw = self.crop.size
+        rec = np.zeros(B, dtype=_AUG_DTYPE)
+        tab_off = max_rs = 0
+        for b, i in enumerate(indices):
+            img_off, lbl_off, sh, sw = store.meta[int(i)]
+            rs_h, rs_w, pad, ci, cj, flip = params[b] if params is not None else self.draw(sh, sw)
+            ksh, ksv = _ksize(sw, rs_w), _ksize(sh, rs_h)
+            rec[b] = (img_off, lbl_off, sh, sw, rs_h, rs_w, pad, ci, cj, flip, tab_off, ksh, ksv, 0)
+            tab_off += rs_w * (3 + ksh) + rs_h * (3 + ksv)
+            max_rs = max(max_rs, rs_h, rs_w)
+        if tab_off >= 2 ** 31:
+            raise ValueError("the batch's tables need %d ints (tab_off is an int32)" % tab_off)
+        nbytes = B * _AUG_DTYPE.itemsize
+        slot = self._ring[self._ring_pos % self.ring_depth]
+        self._ring_pos += 1
+        if slot[1] is not None:
+            slot[1].synchronize()                          # the copy that last read this buffer (back-pressure)
+        if slot[0] is None or slot[0].numel() < nbytes:
+            slot[0] = torch.empty(max(nbytes, 4096), dtype=torch.uint8, pin_memory=True)
+        slot[0].numpy()[:nbytes] = rec.view(np.uint8)
+        dev = store.device
+        _lib.load()
+        with torch.cuda.device(dev):
+            sbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            sbuf.copy_(slot[0][:nbytes], non_blocking=True)
+            if slot[1] is None:
+                slot[1] = torch.cuda.Event()
+            slot[1].record()
+            tables = torch.empty(tab_off, dtype=torch.int32, device=dev)
+            out = torch.empty((B, 3, th, tw), dtype=torch.float32, device=dev)
+            out_lbl = torch.empty((B, th, tw), dtype=torch.uint8, device=dev)
+            mean = (ctypes.c_float * 3)(*[float(np.float32(m)) for m in self.norm.mean])
+            std = (ctypes.c_float * 3)(*[float(np.float32(v)) for v in self.norm.std])
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            call("iswm_aug_tables", sbuf.data_ptr(), B, max_rs, tables.data_ptr(), tab_off * 4, stream)
+            call("iswm_augment_batch", store.img_arena.data_ptr(), store.lbl_arena.data_ptr(), sbuf.data_ptr(),
+                 tables.data_ptr(), B, th, tw, mean, std, out.data_ptr(), out_lbl.data_ptr(), stream)
         return out, out_lbl
 
     def __call__(self, img, lbl):

@@ -108,6 +108,12 @@ def calculate_class_weights(loader, group=None):
         labels = batch['mask'] if isinstance(batch, dict) else batch[1]
         black += int((labels == 0).sum())
         white += int((labels == 1).sum())
+    black, white = _sum_over_group(black, white, group)
+    return torch.tensor([1.0, math.sqrt(black / white)], dtype=torch.float32)
+
+
+def _sum_over_group(black, white, group):
+    """the two pixel counts summed over the process group (int64 all-reduce); unchanged without one"""
     try:
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
@@ -117,4 +123,37 @@ def calculate_class_weights(loader, group=None):
             black, white = int(cnt[0]), int(cnt[1])
     except ImportError:
         pass
+    return black, white
+
+
+def calculate_class_weights_resident(batches, group=None, ignore_index=255):
+    """calculate_class_weights for batches that already live on the device -- the reference's rule (train.py:388-410:
+    [1, sqrt(N_black / N_white)] over ONE pass of the augmented train loader, which also consumes the random stream).
+    `batches` yields (images, uint8 labels on the GPU); every batch is counted by iswm_label_count into one device
+    accumulator, which is read back once at the end; then the same int64 all-reduce over `group`."""
+    import ctypes
+    from .. import _lib
+    lib = _lib.load()
+    acc = ws = None
+    for batch in batches:
+        labels = batch['mask'] if isinstance(batch, dict) else batch[1]
+        if not (labels.is_cuda and labels.dtype == torch.uint8 and labels.is_contiguous()):
+            raise ValueError("calculate_class_weights_resident counts contiguous uint8 CUDA label batches (got %s %s on %s)"
+                             % (tuple(labels.shape), labels.dtype, labels.device))
+        with torch.cuda.device(labels.device):
+            if acc is None:
+                acc = torch.zeros(3, dtype=torch.int64, device=labels.device)
+            n = labels.numel()
+            need = lib.iswm_label_count_workspace(n)
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(need, dtype=torch.uint8, device=labels.device)
+            _lib.call("iswm_label_count", labels.data_ptr(), n, ignore_index, acc.data_ptr(), ws.data_ptr(), ws.numel(),
+                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if acc is None:
+        raise ValueError("calculate_class_weights_resident: no batches")
+    black, white, _other = (int(v) for v in acc.cpu())
+    black, white = _sum_over_group(black, white, group)
+    if white == 0:
+        raise ValueError("no foreground (class 1) pixel in the %d counted: the class weight sqrt(N_black / N_white) is "
+                         "undefined -- check the masks" % (black + white))
     return torch.tensor([1.0, math.sqrt(black / white)], dtype=torch.float32)
