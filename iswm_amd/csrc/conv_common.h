@@ -1,5 +1,7 @@
-// Declarations shared by the implicit-GEMM convolution kernels (conv_mfma.hip: general-K kernels and
-// the C entry points; conv_mfma_u.hip: the tap-uniform fast path).
+// Declarations shared by all convolution kernels and their launchers: the argument structs (ConvArgs, BnFuse, PatchArgs),
+// the row -> pixel maps, the weight packing of the planes kernels and the launch entry points of every family --
+// conv_mfma.hip (fp32 kernels and the C entry points), conv_mfma_u.hip (tap-uniform fast path), conv_mfma_x6*.hip (round-1
+// bf16x6), conv_mfma_pl2*.hip (planes kernels; their device-side pieces are in conv_pl2_stage.h), conv_stem.hip.
 #pragma once
 #include <stdlib.h>
 #include "common.h"
@@ -56,6 +58,20 @@ constexpr int KC_PITCH = 36;  // floats per LDS row of a K-contiguous operand ti
 
 // ---- bf16x6 helpers (see conv_mfma_x6.hip) ------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) void* lds_vptr;
+
+// LDS-DMA (planes kernels: conv_mfma_pl2*.hip, conv_wgrad_pl.hip): every lane's 16 bytes at gsrc go to LDS at lds_dst
+// (wave-uniform) + 16 * lane
+__device__ __forceinline__ void glds16b(const void* gsrc, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "memory");
+}
+
+__device__ __forceinline__ f32x4 mfma16(uint4 a, uint4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
 
 __device__ __forceinline__ f32x16 mfma_bf16(uint4 a, uint4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,

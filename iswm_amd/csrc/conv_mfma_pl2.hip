@@ -21,25 +21,9 @@
 //   * one barrier per 32-deep step; everything a step needs was issued a full step earlier.
 #include <stdlib.h>
 
-#include "conv_common.h"
+#include "conv_pl2_stage.h"
 
 namespace iswm {
-
-static __device__ __attribute__((aligned(128))) unsigned short g_zero_row_pl2[64];   // 128 B of zeros
-static __device__ float4 g_dump_pl2[64];         // where the epilogue's out-of-range lanes store (never read)
-
-typedef __attribute__((address_space(3))) void* lds_vptr2;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void glds16b(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "memory");
-}
-
-__device__ __forceinline__ f32x4 mfma16(uint4 a, uint4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 constexpr int PL2_RBWMAX = 10;     // tile height up to 160 rows
 constexpr double PL2W_EFF = 0.85;   // time per MFMA of the 256-column tiles relative to the 128-column ones
@@ -53,15 +37,14 @@ template <int RBW, int WM, int NP, bool DGRAD>
 __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
     const int GC = DGRAD ? a.Cout : a.Cin;     // channels of the gathered operand (per tap)
     const int NC = DGRAD ? a.Cin : a.Cout;     // output columns
-    constexpr int WN = 8 / WM, BN = 16 * WN, BM = 16 * RBW * WM, RG = BM / 8;
-    constexpr int PLANE = BM * 128;                   // bytes of one plane of one stage
-    constexpr int STAGE = NP * PLANE;
-    constexpr int NRG = (RG + 7) / 8;                 // 8-row DMA groups per wave
+    constexpr int WN = 8 / WM, BN = 16 * WN;
+    using S = Pl2Stage<16 * RBW * WM, NP>;
+    constexpr int BM = S::BM, RG = S::RG, NRG = S::NRG, PLANE = S::PLANE, STAGE = S::STAGE;
     constexpr int XTRA = (DGRAD ? BM * 4 : 0) + (WM > 1 ? 4 * 128 * 4 : 0);
     __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE + XTRA];
     int* rowpix = reinterpret_cast<int*>(smem + 2 * STAGE);
     float* red = reinterpret_cast<float*>(smem + 2 * STAGE + (DGRAD ? BM * 4 : 0));
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr2)smem;
+    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr)smem;
 
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -74,8 +57,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
     const int K32 = a.Ktot >> 5;
     const int ntiles = a.MT * a.NT;
     const unsigned char* xb = reinterpret_cast<const unsigned char*>(a.x);
-    // DMA role of this lane: row (lane >> 3) of an 8-row group, source 16-byte group gs of the 128-byte row
-    const int gs = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
+    const int gs = pl2_dma_group(lane, wave);
     const unsigned char* zrow = reinterpret_cast<const unsigned char*>(g_zero_row_pl2) + gs * 16;
 
     // ---- issue side: the tile / tap / channel stage the DMA pointers stand on
@@ -116,7 +98,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
                 iwb[i] = DGRAD ? rw + a.pad : rw * a.stride - a.pad;
                 pb[i] = n * GH * GW;
             } else {
-                ihb[i] = -(1 << 28);
+                ihb[i] = PL2_NO_ROW;
                 iwb[i] = 0;
                 pb[i] = 0;
             }
@@ -199,39 +181,12 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < RBW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // fragment address of this lane inside a plane: row (lane & 15) of a 16-row block, k group (lane >> 4) [+4 in the
-    // second half of the stage -> slot ^ 4 -> byte ^ 64]
-    const int fbase = wm * (RBW * 2048) + (lane & 15) * 128 + (((lane >> 4) ^ ((lane & 15) >> 1)) * 16);
-    struct AFrag {
-        uint4 v[NP];
-    };
+    const int fbase = PL2_FBASE(wm * (RBW * 2048), lane);
     // Multiply stage `st`; when `more`, the loads of the FOLLOWING stage (weight fragments into bn, activation DMA into stage
     // buffer st ^ 1) are issued one or two at a time BETWEEN the row blocks.  Issued in one burst at the top of the stage
     // they serialise with the multiply: with one workgroup per CU the vector-memory path takes ~34 cycles per 1-KB
     // instruction (30 B/clk/CU, tools/ta_bw.hip) and a wave sits in the issue queue instead of feeding the matrix pipe.
     auto compute = [&](int st, const BFrag& b, bool more, BFrag& bn, int k32n) __attribute__((always_inline)) {
-        // fragments of row block i+1 are read while block i is multiplied; the scheduling fences keep hipcc from
-        // hoisting all 2 * RBW * NP fragment reads of a stage to its top (216 VGPRs for RBW = 9)
-        auto aload = [&](AFrag& f, int idx) __attribute__((always_inline)) {          // idx = half * RBW + rb
-            const int half = idx / RBW, rb = idx - half * RBW;
-            const unsigned char* p = smem + st * STAGE + (fbase ^ (half * 64)) + rb * 2048;
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) f.v[pl] = *reinterpret_cast<const uint4*>(p + pl * PLANE);
-        };
-        auto mul = [&](const AFrag& f, int idx) __attribute__((always_inline)) {
-            const int half = idx / RBW, rb = idx - half * RBW;
-            f32x4 c = acc[rb];
-            if constexpr (NP == 3) {
-                // weights are the MFMA's row operand: lane = pixel, 4 registers = 4 consecutive channels (16-byte stores)
-                c = mfma16(b.v[half][0], f.v[2], c);     // smallest terms first: bh*al, bl*ah, bm*am, bh*am, bm*ah, bh*ah
-                c = mfma16(b.v[half][2], f.v[0], c);
-                c = mfma16(b.v[half][1], f.v[1], c);
-                c = mfma16(b.v[half][0], f.v[1], c);
-                c = mfma16(b.v[half][1], f.v[0], c);
-            }
-            c = mfma16(b.v[half][0], f.v[0], c);
-            acc[rb] = c;
-        };
         constexpr int NB_SLOTS = 2 * NP, NA_SLOTS = NRG * NP, NSLOTS = NB_SLOTS + NA_SLOTS;
         // spread evenly over the row blocks (front-loading them -- two per block over the first half of the stage -- measured
         // 8-12 % slower: the issue burst is what hurts)
@@ -257,17 +212,18 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
                 if (pp == NP - 1) aptr[i] += astep[i];          // this row group's pointer moves on to the stage after
             }
         };
-        // fragments are read TWO row blocks ahead of their multiply, with the order pinned: left to itself hipcc sinks two
-        // of a block's three reads behind the 4th MFMA of the previous block and waits for them (lgkmcnt(0)) two MFMAs
-        // later -- 32 cycles of cover for a ~100-cycle LDS round trip, at every row block
-        AFrag f[3];
-        aload(f[0], 0);
-        if (2 * RBW > 1) aload(f[1], 1);
+        // fragments are read TWO row blocks ahead of their multiply, with the order pinned by the two scheduling fences (the
+        // same loop in k_conv_pl2w and k_conv_pl2t): left to itself hipcc hoists all 2 * RBW * NP fragment reads of a stage to
+        // its top (216 VGPRs for RBW = 9), or sinks two of a block's three reads behind the 4th MFMA of the previous block and
+        // waits for them (lgkmcnt(0)) two MFMAs later -- 32 cycles of cover for a ~100-cycle LDS round trip, at every row block
+        Pl2AFrag<NP> f[3];
+        pl2_aload<S, RBW>(f[0], smem, st, fbase, 0);
+        pl2_aload<S, RBW>(f[1], smem, st, fbase, 1);
 #pragma unroll
         for (int idx = 0; idx < 2 * RBW; ++idx) {
-            if (idx + 2 < 2 * RBW) aload(f[(idx + 2) % 3], idx + 2);
+            if (idx + 2 < 2 * RBW) pl2_aload<S, RBW>(f[(idx + 2) % 3], smem, st, fbase, idx + 2);
             __builtin_amdgcn_sched_barrier(0);
-            mul(f[idx % 3], idx);
+            pl2_mul(acc[idx % RBW], b.v[idx / RBW], f[idx % 3]);
 #pragma unroll
             for (int q = 0; q < PER; ++q) slot(idx * PER + q);
             __builtin_amdgcn_sched_barrier(0);
@@ -606,30 +562,17 @@ bool launch_conv_pl2(ConvArgs a, hipStream_t s, bool dgrad, int planes, int rbw)
     a.NT = narrow ? 1 : (nc + 127) / 128;
     const int tiles = a.MT * a.NT, ncu = device_cus();
     dim3 grid(tiles < ncu ? tiles : ncu), blk(512);
-    if (planes == 1) {          // ONE bf16 plane per operand (conv math "bf16": activations stored rounded, one MFMA per product)
-#define PL2_LAUNCH1(R, W)                                                                      \
-    do {                                                                                       \
-        if (dgrad) hipLaunchKernelGGL((k_conv_pl2<R, W, 1, true>), grid, blk, 0, s, a);         \
-        else hipLaunchKernelGGL((k_conv_pl2<R, W, 1, false>), grid, blk, 0, s, a);              \
-    } while (0)
-        if (narrow) {
-            if (rbw == 8) PL2_LAUNCH1(4, 2);
-            else if (rbw == 10) PL2_LAUNCH1(5, 2);
-            else return false;
-        } else {
-            if (rbw == 8) PL2_LAUNCH1(8, 1);
-            else if (rbw == 9) PL2_LAUNCH1(9, 1);
-            else if (rbw == 10) PL2_LAUNCH1(10, 1);
-            else return false;
-        }
-#undef PL2_LAUNCH1
-        return true;
-    }
-    if (planes != 3) return false;
+    // planes == 1: ONE bf16 plane per operand (conv math "bf16": activations stored rounded, one MFMA per product)
+    if (planes != 1 && planes != 3) return false;
 #define PL2_LAUNCH(R, W)                                                                       \
     do {                                                                                       \
-        if (dgrad) hipLaunchKernelGGL((k_conv_pl2<R, W, 3, true>), grid, blk, 0, s, a);         \
-        else hipLaunchKernelGGL((k_conv_pl2<R, W, 3, false>), grid, blk, 0, s, a);              \
+        if (planes == 1) {                                                                     \
+            if (dgrad) hipLaunchKernelGGL((k_conv_pl2<R, W, 1, true>), grid, blk, 0, s, a);     \
+            else hipLaunchKernelGGL((k_conv_pl2<R, W, 1, false>), grid, blk, 0, s, a);          \
+        } else {                                                                               \
+            if (dgrad) hipLaunchKernelGGL((k_conv_pl2<R, W, 3, true>), grid, blk, 0, s, a);     \
+            else hipLaunchKernelGGL((k_conv_pl2<R, W, 3, false>), grid, blk, 0, s, a);          \
+        }                                                                                      \
     } while (0)
     if (narrow) {
         if (rbw == 8) PL2_LAUNCH(4, 2);

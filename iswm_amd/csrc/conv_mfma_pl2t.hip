@@ -23,25 +23,9 @@
 #include <algorithm>
 #include <vector>
 
-#include "conv_common.h"
+#include "conv_pl2_stage.h"
 
 namespace iswm {
-
-static __device__ __attribute__((aligned(128))) unsigned short g_zero_row_pl2t[64];
-static __device__ float4 g_dump_pl2t[64];        // where the epilogue's out-of-range lanes store (never read)
-
-typedef __attribute__((address_space(3))) void* lds_vptr2t;
-typedef float f32x4t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void glds16bt(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "memory");
-}
-
-__device__ __forceinline__ f32x4t mfma16t(uint4 a, uint4 b, f32x4t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 constexpr int ASPP_MAXB = 4;          // branches
 constexpr int ASPP_MAXT = 32;         // taps over all branches (1 + 9 + 9 + 9 = 28)
@@ -58,8 +42,7 @@ struct AsppJob {
     int tap_begin, ntaps;    // this job's taps in AsppPlan::taps
     int branch;              // forward: the branch this job computes (its weights, output, statistics); data gradient: -1
     int rowmap_off;          // first entry of this job's row -> pixel map (ints from AsppPlan::rowmap_off)
-    int tile_begin_unused;
-    int pad0, pad1, pad2;
+    int pad[4];
 };
 struct AsppPlan {
     int magic, kind;         // kind 0 forward, 1 data gradient
@@ -90,12 +73,10 @@ struct AsppArgs {
 template <bool DGRAD>
 __global__ __launch_bounds__(512, 2) void k_conv_pl2t(const AsppArgs a) {
     constexpr int RBW = ASPP_RBW, NP = 3;
-    constexpr int BM = 16 * RBW, RG = BM / 8;
-    constexpr int PLANE = BM * 128;
-    constexpr int STAGE = NP * PLANE;
-    constexpr int NRG = (RG + 7) / 8;
+    using S = Pl2Stage<16 * RBW, NP>;
+    constexpr int BM = S::BM, RG = S::RG, NRG = S::NRG, PLANE = S::PLANE, STAGE = S::STAGE;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE];
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr2t)smem;
+    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr)smem;
     const AsppPlan& P = *a.plan;
 
     const int t = threadIdx.x, lane = t & 63;
@@ -107,8 +88,8 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2t(const AsppArgs a) {
     const int* rowmap = reinterpret_cast<const int*>(reinterpret_cast<const unsigned char*>(a.plan) + P.rowmap_off);
     const int4* tiles = reinterpret_cast<const int4*>(reinterpret_cast<const unsigned char*>(a.plan) + P.tiles_off);
     const unsigned char* xb = reinterpret_cast<const unsigned char*>(a.x);
-    const int gs = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
-    const unsigned char* zrow = reinterpret_cast<const unsigned char*>(g_zero_row_pl2t) + gs * 16;
+    const int gs = pl2_dma_group(lane, wave);
+    const unsigned char* zrow = reinterpret_cast<const unsigned char*>(g_zero_row_pl2) + gs * 16;
 
     // ---- issue side
     // workgroups b and b + 8 share an XCD: give every XCD a contiguous run of table entries -- the column tiles of one row
@@ -134,7 +115,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2t(const AsppArgs a) {
                 iwb[i] = code & 1023;
                 pb[i] = (code >> 20) * GH * GW;
             } else {
-                ihb[i] = -(1 << 28);
+                ihb[i] = PL2_NO_ROW;
                 iwb[i] = 0;
                 pb[i] = 0;
             }
@@ -174,7 +155,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2t(const AsppArgs a) {
             if (wave + 8 * i < RG) {
 #pragma unroll
                 for (int p = 0; p < NP; ++p)
-                    glds16bt(aptr[i] + p * pst[i], lds_base + st * STAGE + p * PLANE + (wave + 8 * i) * 1024);
+                    glds16b(aptr[i] + p * pst[i], lds_base + st * STAGE + p * PLANE + (wave + 8 * i) * 1024);
             }
             aptr[i] += astep[i];
         }
@@ -189,33 +170,13 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2t(const AsppArgs a) {
             for (int pl = 0; pl < NP; ++pl) b.v[h][pl] = p[(h * NP + pl) * 64];
     };
 
-    f32x4t acc[RBW];
+    f32x4 acc[RBW];
 #pragma unroll
-    for (int i = 0; i < RBW; ++i) acc[i] = f32x4t{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < RBW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int fbase = (lane & 15) * 128 + (((lane >> 4) ^ ((lane & 15) >> 1)) * 16);
-    struct AFrag {
-        uint4 v[NP];
-    };
+    const int fbase = PL2_FBASE(0, lane);
     // multiply stage `st`; the following stage's loads (weights from wn_, activation DMA) are issued between the row blocks
     auto compute = [&](int st, const BFrag& b, bool more, BFrag& bn, const uint4* wn_) __attribute__((always_inline)) {
-        auto aload = [&](AFrag& f, int idx) __attribute__((always_inline)) {
-            const int half = idx / RBW, rb = idx - half * RBW;
-            const unsigned char* p = smem + st * STAGE + (fbase ^ (half * 64)) + rb * 2048;
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) f.v[pl] = *reinterpret_cast<const uint4*>(p + pl * PLANE);
-        };
-        auto mul = [&](const AFrag& f, int idx) __attribute__((always_inline)) {
-            const int half = idx / RBW, rb = idx - half * RBW;
-            f32x4t c = acc[rb];
-            c = mfma16t(b.v[half][0], f.v[2], c);     // smallest terms first
-            c = mfma16t(b.v[half][2], f.v[0], c);
-            c = mfma16t(b.v[half][1], f.v[1], c);
-            c = mfma16t(b.v[half][0], f.v[1], c);
-            c = mfma16t(b.v[half][1], f.v[0], c);
-            c = mfma16t(b.v[half][0], f.v[0], c);
-            acc[rb] = c;
-        };
         constexpr int NB_SLOTS = 2 * NP, NA_SLOTS = NRG * NP, NSLOTS = NB_SLOTS + NA_SLOTS;
         constexpr int PER = (NSLOTS + 2 * RBW - 1) / (2 * RBW);
         const unsigned char* asrc[NRG];
@@ -231,18 +192,18 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2t(const AsppArgs a) {
             } else if (sidx < NSLOTS) {
                 const int i = (sidx - NB_SLOTS) / NP, pp = (sidx - NB_SLOTS) % NP;
                 if (8 * i + 8 <= RG || wave + 8 * i < RG)
-                    glds16bt(asrc[i] + pp * apl[i], lds_base + (st ^ 1) * STAGE + pp * PLANE + (wave + 8 * i) * 1024);
+                    glds16b(asrc[i] + pp * apl[i], lds_base + (st ^ 1) * STAGE + pp * PLANE + (wave + 8 * i) * 1024);
                 if (pp == NP - 1) aptr[i] += astep[i];
             }
         };
-        AFrag f[3];
-        aload(f[0], 0);
-        aload(f[1], 1);
+        Pl2AFrag<NP> f[3];
+        pl2_aload<S, RBW>(f[0], smem, st, fbase, 0);
+        pl2_aload<S, RBW>(f[1], smem, st, fbase, 1);
 #pragma unroll
         for (int idx = 0; idx < 2 * RBW; ++idx) {
-            if (idx + 2 < 2 * RBW) aload(f[(idx + 2) % 3], idx + 2);
+            if (idx + 2 < 2 * RBW) pl2_aload<S, RBW>(f[(idx + 2) % 3], smem, st, fbase, idx + 2);
             __builtin_amdgcn_sched_barrier(0);
-            mul(f[idx % 3], idx);
+            pl2_mul(acc[idx % RBW], b.v[idx / RBW], f[idx % 3]);
 #pragma unroll
             for (int q = 0; q < PER; ++q) slot(idx * PER + q);
             __builtin_amdgcn_sched_barrier(0);
@@ -272,8 +233,8 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2t(const AsppArgs a) {
             }
         }
         // branch-free (see k_conv_pl2's epilogue): out-of-range lanes read a zero line / store into a dump slot by address select
-        const float4* const zero4 = reinterpret_cast<const float4*>(g_zero_row_pl2t);
-        float4* const dump = g_dump_pl2t + lane;
+        const float4* const zero4 = reinterpret_cast<const float4*>(g_zero_row_pl2);
+        float4* const dump = g_dump_pl2 + lane;
         if constexpr (DGRAD) {
             const bool acc_old = a.accumulate != 0;
 #pragma unroll
@@ -332,7 +293,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2t(const AsppArgs a) {
         }
         if (!zero) {
 #pragma unroll
-            for (int i = 0; i < RBW; ++i) acc[i] = f32x4t{0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < RBW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     };
 

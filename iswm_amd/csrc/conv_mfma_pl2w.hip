@@ -1,5 +1,5 @@
 // bf16x6 implicit-GEMM convolution over planes, (16*rbw) x 256 tiles: k_conv_pl2 (conv_mfma_pl2.hip) with TWO 16-column
-// blocks per wave.
+// blocks per wave (what the two share as code: conv_pl2_stage.h).
 //
 // Why: in k_conv_pl2 a wave reads three activation fragments from LDS (ds_read_b128) and issues one load slot per SIX
 // MFMAs; v_mfma_f32_16x16x32_bf16 holds the SIMD's vector issue for 8 of its 16 cycles (MI355X_MICROARCH.md, constants
@@ -15,25 +15,9 @@
 // registers take the next stage's fragments, and vice versa (no second fragment set, no 24-register copy per stage).
 #include <stdlib.h>
 
-#include "conv_common.h"
+#include "conv_pl2_stage.h"
 
 namespace iswm {
-
-static __device__ __attribute__((aligned(128))) unsigned short g_zero_row_pl2w[64];   // 128 B of zeros
-static __device__ float4 g_dump_pl2w[64];        // where the epilogue's out-of-range lanes store (never read)
-
-typedef __attribute__((address_space(3))) void* lds_vptr2w;
-typedef float f32x4w __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void glds16bw(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "memory");
-}
-
-__device__ __forceinline__ f32x4w mfma16w(uint4 a, uint4 b, f32x4w c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // Same operand conventions as k_conv_pl2 (ConvArgs; weights packed by k_pack_weights_pl2, whose column blocks run to
 // ceil(NC / 128) * 8: a.cbs).  Tile = (16 * RBW) rows x 256 columns; wave w owns columns 32 w .. 32 w + 31 and ALL rows.
@@ -44,12 +28,10 @@ template <int RBW, int NP, bool DGRAD>
 __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
     const int GC = DGRAD ? a.Cout : a.Cin;
     const int NC = DGRAD ? a.Cin : a.Cout;
-    constexpr int BM = 16 * RBW, RG = BM / 8;
-    constexpr int PLANE = BM * 128;
-    constexpr int STAGE = NP * PLANE;
-    constexpr int NRG = (RG + 7) / 8;
+    using S = Pl2Stage<16 * RBW, NP>;
+    constexpr int BM = S::BM, RG = S::RG, NRG = S::NRG, PLANE = S::PLANE, STAGE = S::STAGE;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE];
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr2w)smem;
+    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr)smem;
 
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -61,8 +43,8 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
     const int ntiles = a.MT * a.NT;
     const int cbs = ((NC + 127) >> 7) << 3;         // packed column blocks
     const unsigned char* xb = reinterpret_cast<const unsigned char*>(a.x);
-    const int gs = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
-    const unsigned char* zrow = reinterpret_cast<const unsigned char*>(g_zero_row_pl2w) + gs * 16;
+    const int gs = pl2_dma_group(lane, wave);
+    const unsigned char* zrow = reinterpret_cast<const unsigned char*>(g_zero_row_pl2) + gs * 16;
 
     // ---- issue side
     int i_tile = xcd_remap(blockIdx.x, gridDim.x);
@@ -84,7 +66,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
                 iwb[i] = DGRAD ? rw + a.pad : rw * a.stride - a.pad;
                 pb[i] = n * GH * GW;
             } else {
-                ihb[i] = -(1 << 28);
+                ihb[i] = PL2_NO_ROW;
                 iwb[i] = 0;
                 pb[i] = 0;
             }
@@ -140,17 +122,17 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
             if (wave + 8 * i < RG) {
 #pragma unroll
                 for (int p = 0; p < NP; ++p)
-                    glds16bw(aptr[i] + p * pst[i], lds_base + st * STAGE + p * PLANE + (wave + 8 * i) * 1024);
+                    glds16b(aptr[i] + p * pst[i], lds_base + st * STAGE + p * PLANE + (wave + 8 * i) * 1024);
             }
             aptr[i] += astep[i];
         }
     };
 
-    f32x4w acc[2][RBW];
+    f32x4 acc[2][RBW];
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-        for (int i = 0; i < RBW; ++i) acc[cb][i] = f32x4w{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < RBW; ++i) acc[cb][i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // weight fragments of the stage in hand: [column block][32-deep k half][plane]
     uint4 B[2][2][NP];
@@ -163,10 +145,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
         }
     };
 
-    const int fbase = (lane & 15) * 128 + (((lane >> 4) ^ ((lane & 15) >> 1)) * 16);
-    struct AFrag {
-        uint4 v[NP];
-    };
+    const int fbase = PL2_FBASE(0, lane);
     // compute side of the weight stream: the packed blocks and k32 index of the stage being multiplied
     const uint4* wpk_c[2] = {nullptr, nullptr};
     int k32_c = 0;
@@ -177,26 +156,14 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
     //                  stage ended), then the first part of the next stage's activation DMA;
     //   second k half: the FIRST half's weight fragments of the NEXT stage (in place), then the rest of the DMA.
     auto compute = [&](int st, bool more, int k32n) __attribute__((always_inline)) {
-        auto aload = [&](AFrag& f, int idx) __attribute__((always_inline)) {
-            const int half = idx / RBW, rb = idx - half * RBW;
-            const unsigned char* p = smem + st * STAGE + (fbase ^ (half * 64)) + rb * 2048;
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) f.v[pl] = *reinterpret_cast<const uint4*>(p + pl * PLANE);
+        auto aload = [&](Pl2AFrag<NP>& f, int idx) __attribute__((always_inline)) {
+            pl2_aload<S, RBW>(f, smem, st, fbase, idx);
         };
-        auto mul = [&](const AFrag& f, int idx) __attribute__((always_inline)) {
+        auto mul = [&](const Pl2AFrag<NP>& f, int idx) __attribute__((always_inline)) {
             const int half = idx / RBW, rb = idx - half * RBW;
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) {
-                f32x4w c = acc[cb][rb];
-                if constexpr (NP == 3) {
-                    c = mfma16w(B[cb][half][0], f.v[2], c);     // smallest terms first
-                    c = mfma16w(B[cb][half][2], f.v[0], c);
-                    c = mfma16w(B[cb][half][1], f.v[1], c);
-                    c = mfma16w(B[cb][half][0], f.v[1], c);
-                    c = mfma16w(B[cb][half][1], f.v[0], c);
-                }
-                c = mfma16w(B[cb][half][0], f.v[0], c);
-                acc[cb][rb] = c;
+                pl2_mul(acc[cb][rb], B[cb][half], f);
             }
         };
         constexpr int NB = 2 * NP;                      // weight loads per k half (two column blocks)
@@ -216,7 +183,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
         auto dma = [&](int j) __attribute__((always_inline)) {       // j-th DMA instruction of the next stage
             const int i = j / NP, pp = j - i * NP;
             if (8 * i + 8 <= RG || wave + 8 * i < RG)
-                glds16bw(asrc[i] + pp * apl[i], lds_base + (st ^ 1) * STAGE + pp * PLANE + (wave + 8 * i) * 1024);
+                glds16b(asrc[i] + pp * apl[i], lds_base + (st ^ 1) * STAGE + pp * PLANE + (wave + 8 * i) * 1024);
             if (pp == NP - 1) aptr[i] += astep[i];
         };
         auto slot = [&](int half, int s) __attribute__((always_inline)) {
@@ -230,9 +197,9 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
                 else { if (j < NA1) dma(NA0 + j); }
             }
         };
-        AFrag f[3];
+        Pl2AFrag<NP> f[3];
         aload(f[0], 0);
-        if (2 * RBW > 1) aload(f[1], 1);
+        aload(f[1], 1);
 #pragma unroll
         for (int idx = 0; idx < 2 * RBW; ++idx) {
             if (idx + 2 < 2 * RBW) aload(f[(idx + 2) % 3], idx + 2);
@@ -273,7 +240,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
                 // FORWARD: BRANCH-FREE (see k_conv_pl2's epilogue: a predicate around each store made hipcc wait vmcnt(0) before
                 // every one of them, i.e. every store waited for the previous store's acknowledgement): out-of-range lanes
                 // store into a per-lane dump slot, selected by address
-                float4* const dump = g_dump_pl2w + lane;
+                float4* const dump = g_dump_pl2 + lane;
 #pragma unroll
                 for (int rb = 0; rb < RBW; ++rb) {
                     const int row = m0 + rb * 16 + lp;
@@ -412,7 +379,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-                for (int i = 0; i < RBW; ++i) acc[cb][i] = f32x4w{0.f, 0.f, 0.f, 0.f};
+                for (int i = 0; i < RBW; ++i) acc[cb][i] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     };
 

@@ -21,13 +21,7 @@
 
 namespace iswm {
 
-typedef float stem_f32x4 __attribute__((ext_vector_type(4)));
-
 static __device__ __attribute__((aligned(16))) float g_stem_zero[4];         // a zero pixel
-
-__device__ __forceinline__ stem_f32x4 stem_mfma(uint4 a, uint4 b, stem_f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 constexpr int STEM_RB = 6;                  // 96 output pixels per wave-tile: 96 accumulator registers
 constexpr int STEM_TILE = 16 * STEM_RB;
@@ -77,11 +71,11 @@ __global__ __launch_bounds__(512) void k_stem_fwd(const ConvArgs a) {
             okA[rb] = valid[rb] && (unsigned)iw < (unsigned)W;
             okB[rb] = valid[rb] && (unsigned)(iw + 1) < (unsigned)W;
         }
-        stem_f32x4 acc[RB][4];
+        f32x4 acc[RB][4];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-            for (int cb = 0; cb < 4; ++cb) acc[rb][cb] = stem_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int cb = 0; cb < 4; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
         // (fetching the pixels a kernel row ahead into the registers the split frees was measured: no faster -- 214 vs 202 us at the
         // RB = 5 it needs to stay clear of spills; two waves per SIMD cover the load latency already)
@@ -109,13 +103,13 @@ __global__ __launch_bounds__(512) void k_stem_fwd(const ConvArgs a) {
                             xl = make_uint4(l0.x, l0.y, l1.x, l1.y);
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) {
-                    stem_f32x4 c = acc[rb][cb];
-                    c = stem_mfma(wf[cb][0], xl, c);          // smallest terms first, as everywhere (conv_mfma_pl2.hip)
-                    c = stem_mfma(wf[cb][2], xh, c);
-                    c = stem_mfma(wf[cb][1], xm, c);
-                    c = stem_mfma(wf[cb][0], xm, c);
-                    c = stem_mfma(wf[cb][1], xh, c);
-                    c = stem_mfma(wf[cb][0], xh, c);
+                    f32x4 c = acc[rb][cb];
+                    c = mfma16(wf[cb][0], xl, c);          // smallest terms first, as everywhere (conv_mfma_pl2.hip)
+                    c = mfma16(wf[cb][2], xh, c);
+                    c = mfma16(wf[cb][1], xm, c);
+                    c = mfma16(wf[cb][0], xm, c);
+                    c = mfma16(wf[cb][1], xh, c);
+                    c = mfma16(wf[cb][0], xh, c);
                     acc[rb][cb] = c;
                 }
             }

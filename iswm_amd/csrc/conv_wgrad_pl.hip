@@ -22,14 +22,6 @@ namespace iswm {
 
 static __device__ __attribute__((aligned(256))) unsigned short g_zero_row_wg[128];   // 256 B of zeros
 
-typedef __attribute__((address_space(3))) void* lds_vptr3;
-
-__device__ __forceinline__ void glds16w(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "memory");
-}
-
 struct WgArgs {
     const unsigned short* dy;   // planes of dy [P][ldy]
     const unsigned short* x;    // planes of x  [N*H*W][ldx]
@@ -57,7 +49,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pl(const WgArgs a) {
     constexpr int NST = 3;                     // stage buffers: two steps in flight behind the one being multiplied
     constexpr int SMEM = NST * STAGE < 65536 ? 65536 : NST * STAGE;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM];
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr3)smem;
+    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr)smem;
 
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -147,9 +139,9 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pl(const WgArgs a) {
     };
     auto issue = [&](int st) __attribute__((always_inline)) {
 #pragma unroll
-        for (int pl = 0; pl < NP; ++pl) glds16w(asrc + pl * apst, lds_base + st * STAGE + pl * PLANE + wave * 1024);
+        for (int pl = 0; pl < NP; ++pl) glds16b(asrc + pl * apst, lds_base + st * STAGE + pl * PLANE + wave * 1024);
 #pragma unroll
-        for (int pl = 0; pl < NP; ++pl) glds16w(bsrc + pl * bpst, lds_base + st * STAGE + OPER + pl * PLANE + wave * 1024);
+        for (int pl = 0; pl < NP; ++pl) glds16b(bsrc + pl * bpst, lds_base + st * STAGE + OPER + pl * PLANE + wave * 1024);
     };
 
     // ---- transposing fragment reads (see conv_mfma.hip k_conv_wgrad): 16-lane group g = lane >> 4 covers rows
@@ -282,7 +274,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_plw(const WgArgs a) {
     constexpr int NST = 2;
     constexpr int SMEM = NST * STAGE < 65536 ? 65536 : NST * STAGE;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM];
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr3)smem;
+    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr)smem;
 
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -381,8 +373,8 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_plw(const WgArgs a) {
     auto dma = [&](int i, int st) __attribute__((always_inline)) {
         const int img = i / NP, pl = i - img * NP;
         const unsigned dst = lds_base + st * STAGE + img * IMG + pl * PLANE + wave * 1024;
-        if (img == 0) glds16w(asrc + pl * apst, dst);
-        else glds16w(bsrc[img - 1] + pl * bpst[img - 1], dst);
+        if (img == 0) glds16b(asrc + pl * apst, dst);
+        else glds16b(bsrc[img - 1] + pl * bpst[img - 1], dst);
     };
     auto issue = [&](int st) __attribute__((always_inline)) {
 #pragma unroll
@@ -523,7 +515,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pls(const WgArgs a) {
     constexpr int STAGE = 3 * IMG;             // A image, then the two B images
     constexpr int NST = 4;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[NST * STAGE];
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr3)smem;
+    const unsigned lds_base = (unsigned)(uintptr_t)(lds_vptr)smem;
 
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -640,11 +632,11 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pls(const WgArgs a) {
                 }
                 const unsigned dstr = lds_base + (kc & 3) * STAGE + rg * 1024;
 #pragma unroll
-                for (int pl = 0; pl < NP; ++pl) glds16w(asrc + pl * apst, dstr + pl * PLANE);
+                for (int pl = 0; pl < NP; ++pl) glds16b(asrc + pl * apst, dstr + pl * PLANE);
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int pl = 0; pl < NP; ++pl) glds16w(bsrc[i] + pl * bpst[i], dstr + (1 + i) * IMG + pl * PLANE);
+                    for (int pl = 0; pl < NP; ++pl) glds16b(bsrc[i] + pl * bpst[i], dstr + (1 + i) * IMG + pl * PLANE);
                 return;
             }
             asrc = (pin && aok) ? abase + (size_t)p * a.ldy * 2 : zrow;
@@ -683,11 +675,11 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pls(const WgArgs a) {
             }
             const unsigned dst = lds_base + (kc & 3) * STAGE + rg * 1024;
 #pragma unroll
-            for (int pl = 0; pl < NP; ++pl) glds16w(asrc + pl * apst, dst + pl * PLANE);
+            for (int pl = 0; pl < NP; ++pl) glds16b(asrc + pl * apst, dst + pl * PLANE);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int pl = 0; pl < NP; ++pl) glds16w(bsrc[i] + pl * bpst[i], dst + (1 + i) * IMG + pl * PLANE);
+                for (int pl = 0; pl < NP; ++pl) glds16b(bsrc[i] + pl * bpst[i], dst + (1 + i) * IMG + pl * PLANE);
         };
         const int pre = nK < 3 ? nK : 3;
         for (int kc = 0; kc < pre; ++kc) issue(kc);
