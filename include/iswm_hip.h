@@ -213,6 +213,24 @@ int iswm_dwconv2d_dgrad(const iswm_conv_desc* d, const float* dy, const float* w
 size_t iswm_dwconv2d_wgrad_workspace(const iswm_conv_desc* d);
 int iswm_dwconv2d_wgrad(const iswm_conv_desc* d, const float* x, const float* dy, int Cw, float* dw, void* workspace,
                         size_t workspace_bytes, iswm_stream_t stream);
+/* ---- depthwise 3x3 (KH == KW == 3, pad == dil, stride 1 or 2): the depthwise -> BatchNorm stage of MobileNetV2's
+ * inverted-residual blocks (csrc/dwconv3.hip).  Same operand conventions as iswm_dwconv2d_*, and y / dx are bit-identical
+ * to iswm_dwconv2d_fwd / iswm_dwconv2d_dgrad.
+ *   iswm_dwconv3x3_fwd_stats : y = dwconv(x, w) and, when stat_partials != NULL, the BatchNorm partials [2][tiles][Cin]
+ *                              (sum, centred M2) over tiles of iswm_dwconv3x3_stat_tile_rows(d) consecutive output pixels
+ *                              in raster order, the last tile short -- the layout iswm_bn_finalize takes from iswm_colstat.
+ *                              The two queries are pure host functions of the descriptor.
+ *   iswm_dwconv3x3_bwd       : dx (=|+=) the data gradient and dw[Cw][9] the weight gradient from ONE pass over dy and x
+ *                              (fp32 per-workgroup partials in the workspace, merged in double in a fixed order: no
+ *                              atomics, run-to-run identical).  dx [N,H,W,lddx] has a pitch of its own; dx == NULL or
+ *                              dw == NULL skips that half (x and the workspace are needed for dw only). */
+int iswm_dwconv3x3_stat_tile_rows(const iswm_conv_desc* d);
+int iswm_dwconv3x3_stat_tiles(const iswm_conv_desc* d);
+int iswm_dwconv3x3_fwd_stats(const iswm_conv_desc* d, const float* x, const float* w, int Cw, float* y,
+                             float* stat_partials, iswm_stream_t stream);
+size_t iswm_dwconv3x3_bwd_workspace(const iswm_conv_desc* d);
+int iswm_dwconv3x3_bwd(const iswm_conv_desc* d, const float* x, const float* dy, const float* w, int Cw, float* dx,
+                       int lddx, int accumulate, float* dw, void* workspace, size_t workspace_bytes, iswm_stream_t stream);
 /* dw[Cout][KH][KW][Cin] = sum over pixels.  workspace holds split-K slabs. */
 size_t iswm_conv2d_wgrad_workspace(const iswm_conv_desc* d);
 int iswm_conv2d_wgrad(const iswm_conv_desc* d, const float* x, const float* dy, float* dw,

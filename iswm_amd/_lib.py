@@ -80,6 +80,11 @@ _SIGS = {
     "iswm_dwconv2d_dgrad": (c_int, [POINTER(ConvDesc), P, P, c_int, P, c_int, P]),
     "iswm_dwconv2d_wgrad_workspace": (c_size_t, [POINTER(ConvDesc)]),
     "iswm_dwconv2d_wgrad": (c_int, [POINTER(ConvDesc), P, P, c_int, P, P, c_size_t, P]),
+    "iswm_dwconv3x3_stat_tile_rows": (c_int, [POINTER(ConvDesc)]),
+    "iswm_dwconv3x3_stat_tiles": (c_int, [POINTER(ConvDesc)]),
+    "iswm_dwconv3x3_fwd_stats": (c_int, [POINTER(ConvDesc), P, P, c_int, P, P, P]),
+    "iswm_dwconv3x3_bwd_workspace": (c_size_t, [POINTER(ConvDesc)]),
+    "iswm_dwconv3x3_bwd": (c_int, [POINTER(ConvDesc), P, P, P, c_int, P, c_int, c_int, P, P, c_size_t, P]),
     "iswm_conv2d_wgrad": (c_int, [POINTER(ConvDesc), P, P, P, P, c_size_t, P]),
     "iswm_colstat_tiles": (c_int, [c_int64]),
     "iswm_colstat_tile_rows": (c_int64, [c_int64]),

@@ -267,6 +267,36 @@ class DepthwiseConv2d(HipModule, nn.Conv2d):
         self._saved = (x, g) if save else None
         return y
 
+    def is_dw3x3(self):
+        """the geometry csrc/dwconv3.hip covers: 3x3, stride 1 / 2, padding == dilation, no bias (MobileNetV2's)"""
+        return (self.kernel_size[0] == 3 and self.stride[0] in (1, 2) and self.padding[0] == self.dilation[0] and
+                self.bias is None)
+
+    def fwd_stats(self, x, save, want_stats):
+        """forward of a depthwise -> BatchNorm stage (is_dw3x3): (y, partials | None, (tiles, tile_rows)), the tile
+        statistics taken by the convolution's own launch"""
+        g = self.geometry(x)
+        y, partials, tiles = ops.dwconv3x3_fwd_stats(x, self.weight.contiguous(), g, want_stats)
+        self._saved = (x, g) if save else None
+        return y, partials, tiles
+
+    def bwd_fused(self, dy, sink, need_dx=True, dx=None, accumulate=False):
+        """backward of fwd_stats: data and weight gradient from one pass over dy and x"""
+        x, g = self._saved
+        self._saved = None
+        need_dw, buf, tgt = self.weight.requires_grad, None, None
+        if need_dw:
+            buf = sink.target(self.weight)
+            tgt = buf if buf.is_contiguous() else None
+        if not (need_dx or need_dw):
+            return None
+        dx, dw = ops.dwconv3x3_bwd(x, dy, self.weight.contiguous(), g, self.in_channels, dx, accumulate, tgt, need_dx, need_dw)
+        if need_dw:
+            if tgt is None:
+                buf.copy_(dw)
+            sink.done(self.weight)
+        return dx
+
     def bwd(self, dy, sink, need_dx=True, dx=None, accumulate=False):
         x, g = self._saved
         self._saved = None
@@ -340,9 +370,12 @@ def cba_fwd(conv, bn, relu, x, save, residual=None, out=None, out_fmt=None):
     training = bn.training
     if bn.momentum is None or not bn.track_running_stats or not bn.affine:
         raise NotImplementedError("HIP BatchNorm2d supports affine=True, momentum!=None, running stats")
-    if isinstance(conv, DepthwiseConv2d):       # depthwise conv -> BN (MobileNetV2): statistics from a column pass
+    if isinstance(conv, DepthwiseConv2d):       # depthwise conv -> BN (MobileNetV2)
         g = conv.geometry(x)
-        y = conv.fwd(x, save)
+        if conv.is_dw3x3():                     # statistics from the convolution's own launch (csrc/dwconv3.hip)
+            y, partials, tiles = conv.fwd_stats(x, save, training)
+            return _cba_finish(conv, bn, relu, x, y, g, partials, tiles, training, save, residual, out, sep, True, out_fmt)
+        y = conv.fwd(x, save)                   # other filter sizes: statistics from a column pass
         partials, tiles = None, (0, 0)
         if training:
             partials, nt, tr = ops.colstat(y)
@@ -448,6 +481,8 @@ def cba_bwd(conv, bn, ctx, dout, sink, need_dx=True, dx=None, accumulate=False, 
     if sep is not None:
         conv = sep.body[1]
     if ctx.get("dw"):
+        if conv.is_dw3x3():
+            return conv.bwd_fused(dy, sink, need_dx, dx, accumulate), dres
         return conv.bwd(dy, sink, need_dx, dx, accumulate), dres
     conv.write_wgrad(x, dy, g, sink)
     if conv.bias is not None and conv.bias.requires_grad:

@@ -7,14 +7,16 @@ Differences, all deliberate:
   * ``pretrained_backbone`` defaults to False: the reference default triggers an HTTP
     download (network/backbone/resnet.py:220-223) that cannot work offline;
   * ``deeplabv3plus_resnet101`` / ``deeplabv3_resnet50/101`` are exposed (the reference
-    reaches ResNet-101 only through the private ``_segm_resnet``).
+    reaches ResNet-101 only through the private ``_segm_resnet``);
+  * ``deeplabv3plus_mobilenet`` / ``deeplabv3_mobilenet``: the reference has no MobileNet; the backbone
+    and its state_dict keys follow the public MobileNetV2 / DeepLabV3Plus-Pytorch definition.
 """
 import torch
 from torch import nn
 
 from . import _hip
 from ._deeplab import DeepLabHead, DeepLabHeadV3Plus, DeepLabV3
-from .backbone import resnet
+from .backbone import mobilenetv2, resnet
 from .utils import IntermediateLayerGetter
 
 
@@ -63,11 +65,36 @@ def _segm_resnet(name, backbone_name, num_classes, output_stride, pretrained_bac
     return model
 
 
+def _segm_mobilenet(name, backbone_name, num_classes, output_stride, pretrained_backbone):
+    aspp_dilate = [12, 24, 36] if output_stride == 8 else [6, 12, 18]
+    backbone = mobilenetv2.mobilenet_v2(pretrained=pretrained_backbone, output_stride=output_stride)
+    # slices of an nn.Sequential keep the original indices: backbone.low_level_features.{0..3}, high_level_features.{4..17}
+    backbone.low_level_features = backbone.features[0:4]
+    backbone.high_level_features = backbone.features[4:]
+    backbone.features = None
+    inplanes = 320
+    low_level_planes = 24
+
+    if name == 'deeplabv3plus':
+        return_layers = {'high_level_features': 'out', 'low_level_features': 'low_level'}
+        classifier = DeepLabHeadV3Plus(inplanes, low_level_planes, num_classes, aspp_dilate)
+    elif name == 'deeplabv3':
+        return_layers = {'high_level_features': 'out'}
+        classifier = DeepLabHead(inplanes, num_classes, aspp_dilate)
+    else:
+        raise NotImplementedError(name)
+    backbone = IntermediateLayerGetter(backbone, return_layers=return_layers)
+    return DeepLabV3(backbone, classifier)
+
+
 def _load_model(arch_type, backbone, num_classes, output_stride, pretrained_backbone, temporal=False,
                 model_type='parallel', opts=None, in_channels=3):
     if backbone.startswith('resnet'):
         model = _segm_resnet(arch_type, backbone, num_classes, output_stride=output_stride,
                              pretrained_backbone=pretrained_backbone, in_channels=in_channels)
+    elif backbone == 'mobilenetv2':
+        model = _segm_mobilenet(arch_type, backbone, num_classes, output_stride=output_stride,
+                                pretrained_backbone=pretrained_backbone)
     else:
         raise NotImplementedError
     return model
@@ -92,4 +119,15 @@ def deeplabv3_resnet50(num_classes=21, output_stride=8, pretrained_backbone=Fals
 
 def deeplabv3_resnet101(num_classes=21, output_stride=8, pretrained_backbone=False):
     return _load_model('deeplabv3', 'resnet101', num_classes, output_stride=output_stride,
+                       pretrained_backbone=pretrained_backbone)
+
+
+def deeplabv3plus_mobilenet(num_classes=21, output_stride=8, pretrained_backbone=False):
+    """DeepLabV3+ with a MobileNetV2 backbone (BASELINE.json configs[0])."""
+    return _load_model('deeplabv3plus', 'mobilenetv2', num_classes, output_stride=output_stride,
+                       pretrained_backbone=pretrained_backbone)
+
+
+def deeplabv3_mobilenet(num_classes=21, output_stride=8, pretrained_backbone=False):
+    return _load_model('deeplabv3', 'mobilenetv2', num_classes, output_stride=output_stride,
                        pretrained_backbone=pretrained_backbone)

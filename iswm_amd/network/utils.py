@@ -187,6 +187,9 @@ class IntermediateLayerGetter(nn.ModuleDict):
                 below = order[k + 1] if k + 1 < len(order) else None
                 if below in tap and getattr(self[name], "accepts_dx0", False) and not ops.is_planes(tap[below]):
                     dy = self[name].bwd(dy, sink, dx0=tap.pop(below))
+                elif below is None and isinstance(self[name], _hip.HipSequential):
+                    # the first child holds the stem (MobileNetV2's low_level_features): no image gradient unless asked for
+                    dy = self[name].bwd(dy, sink, need_dx=need_dx)
                 else:
                     dy = self[name].bwd(dy, sink)
         self._saved = None

@@ -672,6 +672,46 @@ def dwconv2d_wgrad(x, dy, g, cw, dw=None):
     return dw
 
 
+def dwconv3x3_fwd_stats(x, w, g, want_stats, out=None):
+    """depthwise 3x3 (pad == dil, stride 1 / 2) with the BatchNorm tile statistics taken in the same launch
+    (csrc/dwconv3.hip); w the parameter [Cw,1,3,3] (contiguous).  Returns (y, partials|None, (tiles, tile_rows))."""
+    x = as_f32(x)
+    if out is None:
+        out = new_act(g.n, g.ho, g.wo, g.cin, x.device)
+    d = g.desc(geom(x)[4], geom(out)[4])
+    partials, tiles = None, (0, 0)
+    if want_stats:
+        lib = _lib.load()
+        tiles = (lib.iswm_dwconv3x3_stat_tiles(ctypes.byref(d)), lib.iswm_dwconv3x3_stat_tile_rows(ctypes.byref(d)))
+        partials = torch.empty((2, tiles[0], g.cin), dtype=torch.float32, device=x.device)
+    call("iswm_dwconv3x3_fwd_stats", ctypes.byref(d), _p(x), _p(w), w.shape[0], _p(out), _p(partials), _stream())
+    return out, partials, tiles
+
+
+def dwconv3x3_bwd(x, dy, w, g, cw, dx=None, accumulate=False, dw=None, need_dx=True, need_dw=True):
+    """data gradient (into dx, optionally accumulating) and weight gradient dw [Cw,1,3,3] of the depthwise 3x3 in one pass
+    over dy and x.  Returns (dx|None, dw|None)."""
+    x, dy = as_f32(x), as_f32(dy)
+    if need_dx and dx is None:
+        assert not accumulate
+        dx = new_act(*x.shape, dy.device)
+    if not need_dx:
+        dx = None
+    d = g.desc(geom(x)[4], geom(dy)[4])
+    lddx = geom(dx)[4] if dx is not None else 0
+    ws, need = None, 0
+    if need_dw:
+        if dw is None:
+            dw = torch.empty((cw, 1, 3, 3), dtype=torch.float32, device=x.device)
+        need = _lib.load().iswm_dwconv3x3_bwd_workspace(ctypes.byref(d))
+        ws = torch.empty((need // 4,), dtype=torch.float32, device=x.device)
+    else:
+        dw = None
+    call("iswm_dwconv3x3_bwd", ctypes.byref(d), _p(x), _p(dy), _p(w), cw, _p(dx), lddx, int(bool(accumulate)), _p(dw), _p(ws),
+         need, _stream())
+    return dx, dw
+
+
 def rows(t):
     n, h, w, c, ld = geom(t)
     return n * h * w, c, ld
