@@ -254,6 +254,15 @@ int iswm_bn_finalize(const float* partials, int tiles, int C, int64_t count, int
                      const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
                      float eps, float* scale, float* shift, float* save_mean, float* save_invstd,
                      iswm_stream_t stream);
+/* The same pair with the residual of the tile sum: partials[3][tiles][C], [2] = R_t = sum over the tile of (x - mu_t) about the
+ * fp32 centre mu_t = S_t / n_t that M2_t is taken about.  S_t is an fp32 sum, so mu_t is not the tile's true mean; with R_t the
+ * merge is exact:  mean = sum (n_t mu_t + R_t) / N,  M2 = sum [M2_t + 2 (mu_t - mean) R_t + n_t (mu_t - mean)^2].  Planes [0], [1]
+ * are bit-identical to iswm_colstat's.  Without R_t the variance is off by ~2^-23 |mean| / sigma (3e-5 at |mean| = 2000 sigma). */
+int iswm_colstat_res(const float* x, int64_t M, int C, int ld, float* partials, iswm_stream_t stream);
+int iswm_bn_finalize_res(const float* partials, int tiles, int C, int64_t count, int64_t tile_rows,
+                         const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
+                         float eps, float* scale, float* shift, float* save_mean, float* save_invstd,
+                         iswm_stream_t stream);
 /* eval mode: scale/shift from the running statistics */
 int iswm_bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,
                         const float* running_var, float eps, float* scale, float* shift,

@@ -90,6 +90,8 @@ _SIGS = {
     "iswm_colstat_tile_rows": (c_int64, [c_int64]),
     "iswm_colstat": (c_int, [P, c_int64, c_int, c_int, P, P]),
     "iswm_bn_finalize": (c_int, [P, c_int, c_int, c_int64, c_int64, P, P, P, P, c_float, c_float, P, P, P, P, P]),
+    "iswm_colstat_res": (c_int, [P, c_int64, c_int, c_int, P, P]),
+    "iswm_bn_finalize_res": (c_int, [P, c_int, c_int, c_int64, c_int64, P, P, P, P, c_float, c_float, P, P, P, P, P]),
     "iswm_bn_eval_coeffs": (c_int, [c_int, P, P, P, P, c_float, P, P, P, P, P]),
     "iswm_bn_apply": (c_int, [P, c_int64, c_int, c_int, P, P, P, P, c_int, c_int, P, c_int, P]),
     "iswm_bn_bwd_workspace": (c_size_t, [c_int64, c_int]),

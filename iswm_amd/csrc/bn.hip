@@ -15,6 +15,10 @@ namespace iswm {
 // ---- per-channel tile statistics: sum and centred sum of squares over a row range ---------
 // tile t covers rows [t*R, min(M, (t+1)*R)); two passes over the tile (the second re-reads it
 // through L2) so that M2 is taken about the tile mean -- see iswm_bn_finalize.
+// RES: a third plane R_t = sum (x - mu_t) about the SAME fp32 centre mu_t = S_t / n_t the squares are taken about.  S_t is an fp32
+// sum, so mu_t is off the tile's true mean by ~ulp(S_t) / n_t; R_t (a sum of small exact differences) is what S_t lost, and
+// iswm_bn_finalize_res merges exactly with it (the first two planes are the same bits with or without it).
+template <bool RES>
 __global__ __launch_bounds__(256) void k_colstat(const float* __restrict__ x, int64_t M, int C4, int ld,
                                                  int CQ, int RL, int tiles, int C, int64_t R,
                                                  float* __restrict__ partials) {
@@ -43,13 +47,14 @@ __global__ __launch_bounds__(256) void k_colstat(const float* __restrict__ x, in
         st4(&mean_s[t * 4], make_float4(s.x / cnt, s.y / cnt, s.z / cnt, s.w / cnt));
     }
     __syncthreads();
-    float4 q = make_float4(0, 0, 0, 0);
+    float4 q = make_float4(0, 0, 0, 0), rs = q;
     if (rt.active) {
         const float4 mu = ld4(&mean_s[(t - rt.rl * CQ) * 4]);
         for (int64_t r = r_begin + rt.rl; r < r_end; r += RL) {
             float4 v = ld4(p + r * ld);
             float dx = v.x - mu.x, dy = v.y - mu.y, dz = v.z - mu.z, dw = v.w - mu.w;
             q.x += dx * dx; q.y += dy * dy; q.z += dz * dz; q.w += dw * dw;
+            if (RES) { rs.x += dx; rs.y += dy; rs.z += dz; rs.w += dw; }
         }
     }
     st4(&red[t * 4], q);
@@ -60,6 +65,18 @@ __global__ __launch_bounds__(256) void k_colstat(const float* __restrict__ x, in
             q.x += a.x; q.y += a.y; q.z += a.z; q.w += a.w;
         }
         st4(&partials[(size_t)(tiles + blockIdx.x) * C + rt.c4 * 4], q);
+    }
+    if (RES) {
+        __syncthreads();
+        st4(&red[t * 4], rs);
+        __syncthreads();
+        if (rt.active && rt.rl == 0) {
+            for (int k = 1; k < RL; ++k) {
+                float4 a = ld4(&red[(t + k * CQ) * 4]);
+                rs.x += a.x; rs.y += a.y; rs.z += a.z; rs.w += a.w;
+            }
+            st4(&partials[(size_t)(2 * tiles + blockIdx.x) * C + rt.c4 * 4], rs);
+        }
     }
 }
 
@@ -135,6 +152,62 @@ __global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ p
         save_invstd[c] = invstd;
         if (running_mean) {
             double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+            running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
+            running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+        }
+    }
+}
+
+// The same merge with the residual plane of k_colstat<true>: the centre of tile t is mu_t = fp32(S_t / n_t), exactly as that
+// kernel formed it, its true sum is n_t mu_t + R_t, and
+//   mean = sum (n_t mu_t + R_t) / N;   M2 = sum [M2_t + 2 (mu_t - mean) R_t + n_t (mu_t - mean)^2]
+// is an identity, not an approximation: at |mean| = 2000 sigma the plain merge loses 3e-5 of the variance to the rounding of S_t.
+// block = 4 channels x 64 tile lanes
+__global__ __launch_bounds__(256) void k_bn_finalize_res(const float* __restrict__ partials, int tiles, int C, double count,
+                                                         double R, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float* running_mean,
+                                                         float* running_var, float momentum, float eps, float* scale,
+                                                         float* shift, float* save_mean, float* save_invstd) {
+    constexpr int CPB = 4, TL = 64;
+    __shared__ double red[TL][CPB + 1];
+    __shared__ double mean_s[CPB];
+    const int cl = threadIdx.x % CPB, tl = threadIdx.x / CPB;
+    const int c = blockIdx.x * CPB + cl;
+    auto rows = [&](int k) -> double { return fmin(R, count - (double)k * R); };
+    auto centre = [&](int k) -> double { return (double)(partials[(size_t)k * C + c] / (float)rows(k)); };
+    double s = 0.0;
+    if (c < C)
+        for (int k = tl; k < tiles; k += TL) s += rows(k) * centre(k) + (double)partials[(size_t)(2 * tiles + k) * C + c];
+    red[tl][cl] = s;
+    __syncthreads();
+    if (tl == 0) {
+        for (int k = 1; k < TL; ++k) s += red[k][cl];
+        mean_s[cl] = s / count;
+    }
+    __syncthreads();
+    const double mean = mean_s[cl];
+    double m2 = 0.0;
+    if (c < C)
+        for (int k = tl; k < tiles; k += TL) {
+            const double d = centre(k) - mean;
+            m2 += (double)partials[(size_t)(tiles + k) * C + c] + 2.0 * d * (double)partials[(size_t)(2 * tiles + k) * C + c] +
+                  rows(k) * d * d;
+        }
+    __syncthreads();
+    red[tl][cl] = m2;
+    __syncthreads();
+    if (tl == 0 && c < C) {
+        for (int k = 1; k < TL; ++k) m2 += red[k][cl];
+        double var = m2 / count;
+        if (var < 0.0) var = 0.0;
+        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+        const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
+        scale[c] = g * invstd;
+        shift[c] = b;
+        save_mean[c] = (float)mean;
+        save_invstd[c] = invstd;
+        if (running_mean) {
+            const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
             running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
             running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
         }
@@ -474,9 +547,20 @@ extern "C" int iswm_colstat(const float* x, int64_t M, int C, int ld, float* par
     const int64_t R = iswm_colstat_tile_rows(M);
     const int tiles = (int)((M + R - 1) / R);
     RowPlan p = plan_rows(M, C, tiles);
-    hipLaunchKernelGGL(k_colstat, dim3(p.rowblocks, p.colblocks), dim3(256), 0, (hipStream_t)stream, x, M, p.C4,
+    hipLaunchKernelGGL((k_colstat<false>), dim3(p.rowblocks, p.colblocks), dim3(256), 0, (hipStream_t)stream, x, M, p.C4,
                        ld, p.CQ, p.RL, tiles, C, R, partials);
     return check_launch("colstat");
+}
+
+extern "C" int iswm_colstat_res(const float* x, int64_t M, int C, int ld, float* partials, iswm_stream_t stream) {
+    if (int e = chk_rows("colstat_res", M, C, ld)) return e;
+    ISWM_REQUIRE(x && partials && aligned16(x) && aligned16(partials), "colstat_res: bad pointer");
+    const int64_t R = iswm_colstat_tile_rows(M);
+    const int tiles = (int)((M + R - 1) / R);
+    RowPlan p = plan_rows(M, C, tiles);
+    hipLaunchKernelGGL((k_colstat<true>), dim3(p.rowblocks, p.colblocks), dim3(256), 0, (hipStream_t)stream, x, M, p.C4,
+                       ld, p.CQ, p.RL, tiles, C, R, partials);
+    return check_launch("colstat_res");
 }
 
 extern "C" int iswm_bn_finalize(const float* partials, int tiles, int C, int64_t count, int64_t tile_rows,
@@ -500,6 +584,20 @@ extern "C" int iswm_bn_finalize(const float* partials, int tiles, int C, int64_t
                            C, (double)count, (double)tile_rows, gamma, beta, running_mean, running_var, momentum, eps,
                            scale, shift, save_mean, save_invstd);
     return check_launch("bn_finalize");
+}
+
+extern "C" int iswm_bn_finalize_res(const float* partials, int tiles, int C, int64_t count, int64_t tile_rows,
+                                    const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                    float momentum, float eps, float* scale, float* shift, float* save_mean,
+                                    float* save_invstd, iswm_stream_t stream) {
+    ISWM_REQUIRE(partials && scale && shift && save_mean && save_invstd && tiles > 0 && C > 0 && count > 0 && tile_rows > 0 &&
+                     (int64_t)tiles == (count + tile_rows - 1) / tile_rows,
+                 "bn_finalize_res: bad argument (tiles %d, count %lld, tile_rows %lld)", tiles, (long long)count,
+                 (long long)tile_rows);
+    hipLaunchKernelGGL(k_bn_finalize_res, dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, partials, tiles, C,
+                       (double)count, (double)tile_rows, gamma, beta, running_mean, running_var, momentum, eps, scale, shift,
+                       save_mean, save_invstd);
+    return check_launch("bn_finalize_res");
 }
 
 extern "C" int iswm_bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,

@@ -18,22 +18,37 @@
 
 namespace iswm {
 
+// log softmax of one class, in one of two forms chosen per pixel by |m| (m = the pixel's largest logit):
+//   |m| <  LSE_SPLIT   z - (m + log(se)), what this kernel has always evaluated.  The sum lse = m + log(se) is rounded to an ulp of
+//                      |lse| < 8 + log C < 16, at most 2^-21 = 4.8e-7 of a probability: at torch's own fp32 floor (3e-7).
+//   |m| >= LSE_SPLIT   (z - m) - log(se): the maximum comes off first, so nothing is rounded at the scale of |m| (the first form
+//                      costs 4e-6 on every probability at logits of magnitude 30-80).
+// Why not the second form everywhere: it differs from the first in the last bit of about half the probabilities, and a training
+// run amplifies that (ReLU and max-pool ties) to 2e-3 of the loss within 25 steps -- every recorded loss curve, golden vector and
+// parent-vs-child comparison of a training run would move for no gain in accuracy where logits are of order 1.  Both forms are
+// the same function to rounding, so the loss steps by at most one rounding (1e-6 relative) where |m| crosses the split; the
+// branch is per pixel (m is shared by the pixel's classes) in an HBM-bound kernel.
+constexpr float LSE_SPLIT = 8.f;
+__device__ __forceinline__ float log_softmax(float z, float m, float lg) {
+    return fabsf(m) < LSE_SPLIT ? z - (m + lg) : (z - m) - lg;
+}
+
 // one pixel: value terms and the unnormalised gradient coefficient
 __device__ __forceinline__ void loss_pixel(const float* zc, int C, long long y, const float* __restrict__ cw, int ignore_index,
-                                           float alpha, float gamma, int mode, float& s1, float& s2, float& coef, float& lse,
-                                           bool& valid) {
-    float m = zc[0];
+                                           float alpha, float gamma, int mode, float& s1, float& s2, float& coef, float& m,
+                                           float& lg, bool& valid) {
+    m = zc[0];
     for (int c = 1; c < C; ++c) m = fmaxf(m, zc[c]);
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += expf(zc[c] - m);
-    lse = m + logf(se);
+    lg = logf(se);
     valid = (y != (long long)ignore_index) && y >= 0 && y < C;
     coef = 0.f;  // dL_i/dce_i * w[y]
     if (valid) {
         const float w = cw ? cw[y] : 1.f;
         float zy = zc[0];
         for (int c = 1; c < C; ++c) zy = (c == (int)y) ? zc[c] : zy;
-        const float nll = lse - zy;
+        const float nll = -log_softmax(zy, m, lg);
         if (mode == 0) {
             s1 += w * nll;
             s2 += w;
@@ -92,13 +107,13 @@ __global__ __launch_bounds__(256) void k_loss_fwd(const float* __restrict__ logi
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 if (off[u] < 0) continue;
-                float coef, lse;
+                float coef, m, lg;
                 bool valid;
-                loss_pixel(z[u], C, y[u], cw, ignore_index, alpha, gamma, mode, s1, s2, coef, lse, valid);
+                loss_pixel(z[u], C, y[u], cw, ignore_index, alpha, gamma, mode, s1, s2, coef, m, lg, valid);
 #pragma unroll
                 for (int c = 0; c < CMAX; ++c)
                     if (c < C) {
-                        const float pc = expf(z[u][c] - lse);
+                        const float pc = expf(log_softmax(z[u][c], m, lg));
                         grad[off[u] + c * HW] = valid ? coef * (pc - (c == (int)y[u] ? 1.f : 0.f)) : 0.f;
                     }
             }
@@ -112,14 +127,14 @@ __global__ __launch_bounds__(256) void k_loss_fwd(const float* __restrict__ logi
                 for (int c = 1; c < C; ++c) m = fmaxf(m, zp[c * HW]);
                 float se = 0.f;
                 for (int c = 0; c < C; ++c) se += expf(zp[c * HW] - m);
-                const float lse = m + logf(se);
+                const float lg = logf(se);
                 const long long yy = (long long)labels[i];
                 const bool valid = (yy != (long long)ignore_index) && yy >= 0 && yy < C;
                 float coef = 0.f;
                 if (valid) {
                     const float zy = zp[yy * HW];
                     const float w = cw ? cw[yy] : 1.f;
-                    const float nll = lse - zy;
+                    const float nll = -log_softmax(zy, m, lg);
                     if (mode == 0) {
                         s1 += w * nll;
                         s2 += w;
@@ -144,7 +159,7 @@ __global__ __launch_bounds__(256) void k_loss_fwd(const float* __restrict__ logi
                 }
                 float* g = grad + b * C * HW + p;
                 for (int c = 0; c < C; ++c) {
-                    const float pc = expf(zp[c * HW] - lse);
+                    const float pc = expf(log_softmax(zp[c * HW], m, lg));
                     g[c * HW] = valid ? coef * (pc - (c == (int)yy ? 1.f : 0.f)) : 0.f;
                 }
             }

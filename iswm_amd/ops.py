@@ -724,19 +724,26 @@ def xrows(t):
 
 
 def colstat(x):
-    """per-tile column statistics {S_t, M2_t}; returns (partials, tiles, tile_rows)"""
+    """per-tile column statistics in the three-plane layout {S_t, M2_t, R_t} (iswm_colstat_res; R_t = sum (x - fp32(S_t / n_t)): what
+    the fp32 tile sum lost, bn_finalize merges exactly with it); returns (partials [3, tiles, C], tiles, tile_rows).
+    Only this column pass has the third plane.  The convolution epilogues and dwconv3 publish [2, tiles, C]: their variance keeps an
+    error of ~2^-23 |mean| / sigma, which matters only for channels whose mean is thousands of standard deviations from 0."""
     m, c, ld = rows(x)
     tile_rows = _lib.load().iswm_colstat_tile_rows(m)
     tiles = (m + tile_rows - 1) // tile_rows
-    partials = torch.empty((2, tiles, c), dtype=torch.float32, device=x.device)
-    call("iswm_colstat", _p(x), m, c, ld, _p(partials), _stream())
+    partials = torch.empty((3, tiles, c), dtype=torch.float32, device=x.device)
+    call("iswm_colstat_res", _p(x), m, c, ld, _p(partials), _stream())
     return partials, tiles, tile_rows
 
 
 def bn_finalize(partials, tiles, count, tile_rows, gamma, beta, running_mean, running_var, momentum, eps=BN_EPS):
+    """tile statistics -> coef [4, C] = (scale, beta, mean, invstd), running buffers updated.  The layout of `partials` is its first
+    dimension: [2, tiles, C] = {S_t, M2_t} (convolution epilogues, dwconv3: iswm_bn_finalize), [3, tiles, C] = that pair plus the
+    residual plane of colstat (iswm_bn_finalize_res, the exact merge)."""
     c = partials.shape[2]
     coef = torch.empty((4, c), dtype=torch.float32, device=partials.device)  # scale, beta, mean, invstd
-    call("iswm_bn_finalize", _p(partials), tiles, c, count, tile_rows, _p(gamma), _p(beta), _p(running_mean),
+    name = "iswm_bn_finalize_res" if (partials.dim() == 3 and partials.shape[0] == 3) else "iswm_bn_finalize"
+    call(name, _p(partials), tiles, c, count, tile_rows, _p(gamma), _p(beta), _p(running_mean),
          _p(running_var), float(momentum), float(eps), _p(coef[0]), _p(coef[1]), _p(coef[2]), _p(coef[3]), _stream())
     return coef
 
