@@ -1,0 +1,759 @@
+"""Float64 restatements of the convolution kernels' operations, the fp32 floors they are judged by, a CPU emulation of the
+bf16x6 product (csrc/planes.h split3, six plane products) and the cases of tests/test_conv_kernels_gpu.py.
+
+Rule (the one of tests/streaming_ref.py): every float comparison of the GPU file is rel_err = max|a - b| / max|b| against the
+float64 restatement and must be <= 4 x FLOOR[check]; FLOOR[check] is torch's own fp32 CPU operator against the same
+restatement on the same inputs, the largest over the check's cases.  tests/test_conv_ref_cpu.py measures the floors again,
+ties them to profiles/conv_kernel_tests.txt and shows, case by case, that a product with one plane pair missing or one plane
+misrouted errs by at least 3 x the bound -- so the bound sees every term of the split.
+
+Layouts are the op wrappers': activations NHWC, weights OHWI, all fp32 on the host."""
+import collections
+import contextlib
+import ctypes
+import zlib
+
+import torch
+import torch.nn.functional as F
+
+from tests.util import rel_err
+
+# ---- cases ---------------------------------------------------------------------------------------------------------------
+# mode: "pl"   conv math bf16x6, operands pre-split into planes where the network would (gathered channels % 64 == 0)
+#       "x6"   conv math bf16x6, fp32 operands (the planes-off data path: packed-weight kernels, k_conv_wgrad, the stem)
+#       "f32"  conv math 0: the exact-fp32 MFMA kernels
+#       "bf16" conv math 2 on fp32 operands, "bf16pl" on one-plane operands: ONE bf16 MFMA per product; the restatement runs on
+#              operands rounded to nearest-even bf16
+# geom: n, h, w, cin, cout, k, stride, pad, dil.   names: the device kernel each operation has to reach (also which run).
+# sub:  0 = compare every channel; s > 0 = a strided subset of s output / input channels over every pixel (and s x 2s x taps
+#       weight-gradient entries), as tests/test_production_shapes.py does.   half: the K stage is 32 channels (k_conv_pl2w)
+Route = collections.namedtuple("Route", "id mode geom names sub half")
+
+
+def _r(id, mode, geom, fwd=None, dgrad=None, wgrad=None, sub=0, half=False):
+    names = collections.OrderedDict((k, v) for k, v in (("fwd", fwd), ("dgrad", dgrad), ("wgrad", wgrad)) if v)
+    return Route(id, mode, geom, names, sub, half)
+
+
+ROUTES = [
+    # -- k_conv_pl2<8, 1>, the 64-column layout <4, 2>, k_wgrad_pl (pl_narrow: with a multi-split plan, plain slab reduction)
+    # 5 x 7 x 11 = 385 rows = 3 tiles of 128 + ONE row; tiles straddle images
+    _r("pl_1x1", "pl", (5, 7, 11, 64, 128, 1, 1, 0, 1), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<4, 2, 3, true>", "k_wgrad_pl<3>"),
+    _r("pl_3x3", "pl", (1, 9, 15, 128, 128, 3, 1, 1, 1), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<8, 1, 3, true>", "k_wgrad_pls<3>"),
+    _r("pl_narrow", "pl", (2, 17, 19, 64, 64, 1, 1, 0, 1), "k_conv_pl2<4, 2, 3, false>", "k_conv_pl2<4, 2, 3, true>", "k_wgrad_pl<3>"),
+    _r("pl_narrow3", "pl", (1, 9, 15, 128, 64, 3, 1, 1, 1), "k_conv_pl2<4, 2, 3, false>", "k_conv_pl2<8, 1, 3, true>", "k_wgrad_pls<3>"),
+    # -- the parity-ordered strided data gradient
+    #    (3 x 3 x 128 channels is K = 1152, where torch's own fp32 error is too large for the bound to see a lost term --
+    #    see SENSITIVITY in tests/test_conv_ref_cpu.py -- so the strided 3 x 3 runs each direction at 64 gathered channels)
+    _r("pl_s2", "pl", (2, 15, 15, 128, 64, 3, 2, 1, 1), dgrad="k_conv_pl2<8, 1, 3, true>", wgrad="k_wgrad_pls<3>"),
+    _r("pl_s3", "pl", (2, 16, 17, 128, 64, 3, 3, 1, 1), dgrad="k_conv_pl2<8, 1, 3, true>", wgrad="k_wgrad_pls<3>"),
+    _r("pl_s2_fwd", "pl", (1, 15, 15, 64, 128, 3, 2, 1, 1), fwd="k_conv_pl2<8, 1, 3, false>"),
+    _r("pl_s2_1x1", "pl", (2, 13, 13, 128, 128, 1, 2, 0, 1), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<8, 1, 3, true>", "k_wgrad_pl<3>"),
+    # -- edges: ragged last column block (200, 320), dilation 2, pad 0, pad >= map (dilation 18), 5 x 5, 1 x 1 maps
+    _r("pl_c200_d2", "pl", (1, 11, 13, 64, 200, 3, 1, 2, 2), fwd="k_conv_pl2<8, 1, 3, false>", wgrad="k_wgrad_pls<3>"),
+    _r("pl_c320_fwd", "pl", (1, 11, 13, 64, 320, 1, 1, 0, 1), fwd="k_conv_pl2<8, 1, 3, false>", wgrad="k_wgrad_pl<3>"),
+    _r("pl_c320_dgrad", "pl", (1, 11, 13, 320, 64, 1, 1, 0, 1), dgrad="k_conv_pl2<8, 1, 3, true>", wgrad="k_wgrad_pls<3>"),
+    _r("pl_pad0", "pl", (1, 11, 13, 64, 128, 3, 1, 0, 1), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<4, 2, 3, true>", "k_wgrad_pls<3>"),
+    _r("pl_d18", "pl", (1, 9, 9, 64, 128, 3, 1, 18, 18), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<4, 2, 3, true>", "k_wgrad_plw<3>"),
+    _r("pl_5x5", "pl", (1, 11, 11, 64, 128, 5, 1, 2, 1), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<4, 2, 3, true>", "k_wgrad_pls<3>"),
+    _r("pl_map1", "pl", (3, 1, 1, 128, 128, 1, 1, 0, 1), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<8, 1, 3, true>", "k_wgrad_pl<3>"),
+    # -- weight gradient: tap rectangles (pad >= 4, Cin % 256 == 0), one with a multi-split plan; k_wgrad_pls with a multi-split
+    #    plan (k_reduce_slabs_frag)
+    _r("pl_rect", "pl", (1, 9, 9, 256, 128, 3, 1, 18, 18), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<8, 1, 3, true>", "k_wgrad_pls<3>"),
+    _r("pl_rect_split", "pl", (1, 19, 19, 256, 64, 3, 1, 4, 4), wgrad="k_wgrad_pls<3>"),
+    _r("pl_wsplit", "pl", (2, 13, 13, 128, 128, 3, 1, 1, 1), wgrad="k_wgrad_pls<3>"),
+    # -- taller tiles: 512 columns are 4 column blocks, so 9000 / 9800 rows fill 256 CUs in one round only at 144 / 160 rows;
+    #    the 64-column layout has one column block and needs 37 050 rows for its <5, 2> form
+    _r("pl_r9_fwd", "pl", (1, 90, 100, 64, 512, 1, 1, 0, 1), fwd="k_conv_pl2<9, 1, 3, false>", sub=8),
+    _r("pl_r9_dgrad", "pl", (1, 90, 100, 512, 64, 1, 1, 0, 1), dgrad="k_conv_pl2<9, 1, 3, true>", sub=8),
+    _r("pl_r10_fwd", "pl", (1, 98, 100, 64, 512, 1, 1, 0, 1), fwd="k_conv_pl2<10, 1, 3, false>", sub=8),
+    _r("pl_r10_dgrad", "pl", (1, 98, 100, 512, 64, 1, 1, 0, 1), dgrad="k_conv_pl2<10, 1, 3, true>", sub=8),
+    _r("pl_r5_narrow", "pl", (1, 190, 195, 64, 64, 1, 1, 0, 1), "k_conv_pl2<5, 2, 3, false>", "k_conv_pl2<5, 2, 3, true>", sub=8),
+    # -- k_conv_pl2w: the smallest M at which conv_pl2_plan takes the wide tiles is 10 248 rows at 512 columns (K >= 256
+    #    forward, >= 512 data gradient); 2 x 61 x 84 = 10 248
+    _r("pl_wide", "pl", (2, 61, 84, 512, 512, 1, 1, 0, 1), "k_conv_pl2w<8, 3, false>", "k_conv_pl2w<8, 3, true>", "k_wgrad_pls<3>",
+       sub=8, half=True),
+    _r("pl_wide3", "pl", (2, 61, 84, 64, 512, 3, 1, 1, 1), fwd="k_conv_pl2w<8, 3, false>", sub=8, half=True),
+    # -- the fp32 fallbacks bf16x6 keeps: data gradients that gather 48 / 4 channels
+    _r("pl_c48", "pl", (2, 13, 13, 256, 48, 1, 1, 0, 1), "k_conv_pl2<4, 2, 3, false>", "k_conv_dgrad<64>", "k_wgrad_pls<3>"),
+    _r("pl_c4", "pl", (2, 13, 13, 256, 4, 1, 1, 0, 1), "k_conv_pl2<4, 2, 3, false>", "k_conv_dgrad<64>", "k_wgrad_pls<3>"),
+    # -- planes off: k_conv_x6 (64- and 128-row tiles), k_conv_x6_patch, k_conv_wgrad, the stem at an even and an odd map
+    _r("x6_1x1", "x6", (5, 7, 11, 64, 128, 1, 1, 0, 1), "k_conv_x6<64, 64, false, true, 3>", "k_conv_x6<64, 64, true, true, 3>",
+       "k_conv_wgrad<64, 64, 2, true, 3>"),
+    _r("x6_s2", "x6", (1, 13, 13, 96, 160, 3, 2, 1, 1), "k_conv_x6<64, 64, false, true, 3>", "k_conv_x6<64, 64, true, true, 3>",
+       "k_conv_wgrad<64, 64, 0, true, 3>"),
+    _r("x6_patch", "x6", (1, 10, 12, 64, 64, 3, 1, 1, 1), "k_conv_x6_patch<false, 3>", "k_conv_x6_patch<true, 3>",
+       "k_conv_wgrad<64, 64, 1, true, 3>"),
+    _r("x6_patch_d2", "x6", (1, 24, 26, 32, 32, 3, 1, 2, 2), "k_conv_x6_patch<false, 3>", "k_conv_x6_patch<true, 3>",
+       "k_conv_wgrad<64, 64, 1, true, 3>"),
+    _r("x6_m128", "x6", (1, 79, 79, 64, 512, 1, 1, 0, 1), fwd="k_conv_x6<128, 64, false, true, 3>", sub=8),
+    _r("stem_even", "x6", (1, 38, 38, 4, 64, 7, 2, 3, 1), fwd="k_stem_fwd<6>", wgrad="k_stem_wgrad"),
+    _r("stem_odd", "x6", (1, 37, 41, 4, 64, 7, 2, 3, 1), fwd="k_stem_fwd<6>", wgrad="k_stem_wgrad"),
+    # -- conv math 0: the _u kernels (K a multiple of 32) and the general-K kernels in their narrow and wide tiles
+    _r("f32_u", "f32", (5, 7, 11, 64, 128, 1, 1, 0, 1), "k_conv_fwd_u<64, 64>", "k_conv_dgrad_u<64, 64>",
+       "k_conv_wgrad<64, 64, 2, false, 3>"),
+    _r("f32_u_s2", "f32", (1, 13, 13, 96, 160, 3, 2, 1, 1), "k_conv_fwd_u<64, 64>", "k_conv_dgrad_u<64, 64>",
+       "k_conv_wgrad<64, 64, 0, false, 3>"),
+    _r("f32_u_m128", "f32", (1, 128, 130, 64, 64, 1, 1, 0, 1), fwd="k_conv_fwd_u<128, 64>", sub=8),
+    _r("f32_narrow", "f32", (1, 13, 13, 48, 48, 3, 1, 1, 1), "k_conv_fwd<64>", "k_conv_dgrad<64>", "k_conv_wgrad<64, 64, 1, false, 3>"),
+    _r("f32_wide_fwd", "f32", (1, 128, 129, 48, 128, 1, 1, 0, 1), fwd="k_conv_fwd<128>", sub=8),
+    _r("f32_wide_dgrad", "f32", (1, 128, 129, 128, 48, 1, 1, 0, 1), dgrad="k_conv_dgrad<128>", sub=8),
+    # -- the one-plane bf16 mode
+    _r("bf16_1x1", "bf16", (5, 7, 11, 64, 128, 1, 1, 0, 1), "k_conv_x6<64, 64, false, true, 1>", "k_conv_x6<64, 64, true, true, 1>",
+       "k_conv_wgrad<64, 64, 2, true, 1>"),
+    _r("bf16_patch", "bf16", (1, 10, 12, 64, 64, 3, 1, 1, 1), "k_conv_x6_patch<false, 1>", "k_conv_x6_patch<true, 1>",
+       "k_conv_wgrad<64, 64, 1, true, 1>"),
+    _r("bf16_pl", "bf16pl", (1, 9, 15, 128, 128, 3, 1, 1, 1), "k_conv_pl2<8, 1, 1, false>", "k_conv_pl2<8, 1, 1, true>",
+       "k_wgrad_pls<1>"),
+]
+ROUTE = {r.id: r for r in ROUTES}
+# routes whose dense K is too long for the bound to see a lost term (5 x 5 x 64 = 1600; a 3 x 3 on the wide tiles): they run the
+# exact-integer and the stage-isolating kinds only (a dense 5 x 5 has K >= 800 on any bf16x6 kernel, where torch's floor is
+# 8e-7 .. 9.5e-7 and the weakest single-term mutant 2.4 x the bound)
+NO_DENSE = ("pl_5x5", "pl_wide3")
+SLICE_ROUTES = ["pl_3x3", "pl_narrow", "pl_s2_1x1", "x6_patch", "x6_1x1", "f32_u", "bf16_pl"]     # bias + channel slices of wider buffers
+
+MATH = {"pl": 1, "x6": 1, "f32": 0, "bf16": 2, "bf16pl": 2}
+QTY = {"fwd": ("y",), "dgrad": ("dx", "dx_acc"), "wgrad": ("dw",)}
+
+
+def out_size(h, k, stride, pad, dil):
+    return (h + 2 * pad - dil * (k - 1) - 1) // stride + 1
+
+
+def stage_width(rt):
+    return 32 if rt.half else 64
+
+
+def kinds(rt):
+    """operand kinds of a route: dense, scaled, exact integers, and the stage-isolating ones -- first, second and last K stage
+    ("s0", "s1", "sL": ordinal over (tap, channel chunk)), every further tap of a 3 x 3 ("t1" .. "t8", chunk 0), and for the
+    wide kernel the second 32-channel half of the first chunk ("h1")"""
+    n, h, w, cin, cout, k, stride, pad, dil = rt.geom
+    out = ["int", "s0"] if rt.id in NO_DENSE else ["dense", "scaled", "int", "s0"]
+    if rt.id.startswith("stem"):
+        return out + ["sL"]                       # 7 x 7 x 4: pixel bands for the weight gradient, first / last tap forward
+    wd = stage_width(rt)
+    stages = k * k * max((cin + wd - 1) // wd if "fwd" in rt.names else 1, (cout + wd - 1) // wd if "dgrad" in rt.names else 1)
+    npix = n * out_size(h, k, stride, pad, dil) * out_size(w, k, stride, pad, dil)
+    if stages > 1 or ("wgrad" in rt.names and npix > 32):
+        out.append("s1")
+    if stages > 2 or ("wgrad" in rt.names and npix > 64):
+        out.append("sL")
+    if k == 3:
+        out += ["t%d" % t for t in range(1, 9)]
+    if rt.half:
+        out.append("h1")
+    return out
+
+
+CASES = [(rt.id, kind) for rt in ROUTES for kind in kinds(rt)]
+
+
+def gen(*key):
+    return torch.Generator().manual_seed(zlib.crc32(repr(key).encode()) & 0x7FFFFFFF)
+
+
+def _stage(kind, taps, nchunk):
+    """(tap, chunk) of a stage-isolating kind on a K axis of taps x nchunk stages, tap-major"""
+    total = taps * nchunk
+    if kind[0] == "t":
+        return int(kind[1:]) % taps, 0
+    s = {"s0": 0, "s1": min(1, total - 1), "sL": total - 1, "h1": 0}[kind]
+    return s // nchunk, s % nchunk
+
+
+def band(kind, npix):
+    """pixel range [a, b) of the flattened (n, ho, wo) axis that a stage-isolating kind leaves in dy for the weight gradient:
+    one 32-pixel step of the kernels' pixel loop"""
+    steps = (npix + 31) // 32
+    if kind[0] == "t":
+        s = int(kind[1:]) % steps
+    else:
+        s = {"s0": 0, "s1": min(1, steps - 1), "sL": steps - 1, "h1": min(2, steps - 1)}[kind]
+    return 32 * s, min(npix, 32 * s + 32)
+
+
+def operands(rt, kind, xkey=None):
+    """dict of fp32 host tensors: x [N,H,W,Cin], dy [N,Ho,Wo,Cout], w_f / w_d (OHWI: the forward's and the data gradient's
+    weights -- they differ only in the stage-isolating kinds), dy_w (the weight gradient's dy), base (what the accumulating
+    data gradient adds into), ex / ey (per-channel exponents of the scaled kind, else zeros).  Kind "zero": w and dy_w are 0
+    (an ASPP branch next to the isolated one).  xkey: seed of x, base, ex when several routes share one input (ASPP)."""
+    n, h, w, cin, cout, k, stride, pad, dil = rt.geom
+    ho, wo = out_size(h, k, stride, pad, dil), out_size(w, k, stride, pad, dil)
+    gx, g = gen(xkey or rt.id, "x", kind == "int"), gen(rt.id, "w", kind == "int")
+    if kind == "int":          # hi plane only, |partial sums| <= 18 432 x 12 < 2^24: fp32, bf16x6, bf16 and float64 agree exactly
+        ri = lambda gg, lo, hi, *s: torch.randint(lo, hi + 1, s, generator=gg).float()
+        x, base = ri(gx, -4, 4, n, h, w, cin), ri(gx, -9, 9, n, h, w, cin)
+        wt, dy = ri(g, -3, 3, cout, k, k, cin), ri(g, -4, 4, n, ho, wo, cout)
+    else:
+        x, base = torch.randn(n, h, w, cin, generator=gx), torch.randn(n, h, w, cin, generator=gx)
+        wt = torch.randn(cout, k, k, cin, generator=g) * (2.0 / (cin * k * k)) ** 0.5
+        dy = torch.randn(n, ho, wo, cout, generator=g)
+    if rt.id.startswith("stem"):                  # the 3-channel image padded to 4: channel 3 carries nothing
+        x[..., 3] = 0
+        wt[..., 3] = 0
+    o = dict(x=x, dy=dy, w_f=wt, w_d=wt, dy_w=dy, base=base, ex=torch.zeros(cin), ey=torch.zeros(cout))
+    if kind == "scaled":
+        # x[c] * 2^ex[c], dy[o] * 2^ey[o], w[o, c] * 2^-(ex[c] + ey[o]): every product is the dense one times a power of two, so
+        # y, dx, dw are the dense results times 2^-ey, 2^-ex, 2^(ex + ey) -- the comparison removes that factor again (exactly)
+        # and keeps the dense case's metric, while the planes carry magnitudes from 2^-12 to 2^12 side by side
+        ex = torch.randint(-12, 13, (cin,), generator=gx).float()
+        ey = torch.randint(-12, 13, (cout,), generator=g).float()
+        ws = wt * torch.exp2(-ex) * torch.exp2(-ey).view(-1, 1, 1, 1)
+        o.update(x=x * torch.exp2(ex), dy=dy * torch.exp2(ey), w_f=ws, w_d=ws, base=base * torch.exp2(-ex), ex=ex, ey=ey)
+        o["dy_w"] = o["dy"]
+    elif kind == "zero":
+        o.update(w_f=torch.zeros_like(wt), w_d=torch.zeros_like(wt), dy_w=torch.zeros_like(dy))
+    elif kind not in ("dense", "int"):
+        wd = stage_width(rt)
+        if rt.id.startswith("stem"):
+            wf = torch.zeros_like(wt)
+            tap = 0 if kind == "s0" else k * k - 1
+            wf.view(cout, k * k, cin)[:, tap] = wt.view(cout, k * k, cin)[:, tap]
+            o["w_f"] = wf
+        else:
+            wf, wdg = torch.zeros_like(wt), torch.zeros_like(wt)
+            width = 32 if kind == "h1" else wd
+            tap, ch = _stage(kind, k * k, (cin + wd - 1) // wd)
+            c0 = ch * wd + (32 if kind == "h1" else 0)
+            wf.view(cout, k * k, cin)[:, tap, c0:c0 + width] = wt.view(cout, k * k, cin)[:, tap, c0:c0 + width]
+            tap, ch = _stage(kind, k * k, (cout + wd - 1) // wd)
+            c0 = ch * wd + (32 if kind == "h1" else 0)
+            wdg.view(cout, k * k, cin)[c0:c0 + width, tap] = wt.view(cout, k * k, cin)[c0:c0 + width, tap]
+            o.update(w_f=wf, w_d=wdg)
+        a, b = band(kind, n * ho * wo)
+        dyw = torch.zeros_like(dy)
+        dyw.view(-1, cout)[a:b] = dy.view(-1, cout)[a:b]
+        o["dy_w"] = dyw
+    if kind != "int":
+        # the base of the accumulating data gradient at the gradient's own magnitude (sigma_dx^2 = sum over (tap, cout) of w^2
+        # for unit-variance dy), so that dx_acc = base + dx shows an error of dx as clearly as dx does -- also when only one
+        # K stage carries weights
+        wd = o["w_d"].double() * torch.exp2(o["ex"]).double() * torch.exp2(o["ey"]).double().view(-1, 1, 1, 1)
+        o["dx_scale"] = float(wd.pow(2).sum().div(cin).sqrt()) / stride
+        o["base_unit"] = o["base"]
+        o["base"] = o["base"] * (o["dx_scale"] or 1.0)
+    if MATH[rt.mode] == 2:                        # what the one-plane kernels multiply: operands rounded to nearest-even bf16
+        for key in ("x", "dy", "w_f", "w_d", "dy_w"):
+            o[key + "_r"] = o[key].bfloat16().float()
+    return o
+
+
+def bias_of(rt):
+    return torch.randn(rt.geom[4], generator=gen(rt.id, "bias"))
+
+
+def rounded(rt, o):
+    """the operands the restatement of this route runs on (bf16-rounded under conv math 2)"""
+    sfx = "_r" if MATH[rt.mode] == 2 else ""
+    return dict((k, o[k + sfx]) for k in ("x", "dy", "w_f", "w_d", "dy_w"))
+
+
+# ---- the float64 restatement (and, with dtype=torch.float32, torch's own fp32 operator: the floor) ----------------------------
+def subset(c, k):
+    """k channel indices spread over [0, c), one per block of c // k at an offset that changes from block to block -- equal
+    offsets would sample ONE residue class of the kernels' column layout (one column block of a wave, one lane quad); every
+    channel for k == 0"""
+    if k == 0 or k >= c:
+        return torch.arange(c)
+    i = torch.arange(k)
+    return i * (c // k) + (7 + 13 * i) % (c // k)
+
+
+def channels(rt):
+    """(output channels, input channels, weight-gradient input channels) a route's comparison covers"""
+    cin, cout = rt.geom[3], rt.geom[4]
+    return subset(cout, rt.sub), subset(cin, rt.sub), subset(cin, 2 * rt.sub)
+
+
+def _nchw(t, dtype):
+    return t.permute(0, 3, 1, 2).to(dtype)
+
+
+def conv_fwd(rt, x, w, dtype=torch.float64, bias=None):
+    """y[N,Ho,Wo,co] = conv(x, w[co]) (+ bias)"""
+    _, _, _, _, _, k, stride, pad, dil = rt.geom
+    co = channels(rt)[0]
+    b = None if bias is None else bias[co].to(dtype)
+    return F.conv2d(_nchw(x, dtype), _nchw(w[co], dtype), b, stride, pad, dil).permute(0, 2, 3, 1)
+
+
+def conv_dgrad(rt, dy, w, dtype=torch.float64):
+    """dx[N,H,W,ci] = conv^T(dy, w[:, ci])"""
+    _, h, wd, _, _, k, stride, pad, dil = rt.geom
+    ci = channels(rt)[1]
+    opad = (h + 2 * pad - dil * (k - 1) - 1) % stride, (wd + 2 * pad - dil * (k - 1) - 1) % stride
+    dx = F.conv_transpose2d(_nchw(dy, dtype), _nchw(w[..., ci], dtype), None, stride, pad, opad, 1, dil)
+    assert tuple(dx.shape[2:]) == (h, wd)
+    return dx.permute(0, 2, 3, 1)
+
+
+def conv_wgrad(rt, x, dy, dtype=torch.float64):
+    """dw[co,KH,KW,ci2] = sum over pixels of dy (x) gathered x, by autograd through F.conv2d"""
+    _, _, _, _, _, k, stride, pad, dil = rt.geom
+    co, _, ci2 = channels(rt)
+    ws = torch.zeros(len(co), len(ci2), k, k, dtype=dtype, requires_grad=True)
+    F.conv2d(_nchw(x[..., ci2], dtype), ws, None, stride, pad, dil).backward(_nchw(dy[..., co], dtype))
+    return ws.grad.permute(0, 2, 3, 1)
+
+
+def factor(rt, o, q, dtype=torch.float64):
+    """the power of two per element that takes quantity q of the scaled kind back to the dense kind's values (1 otherwise)"""
+    co, ci, ci2 = channels(rt)
+    sy, sx = torch.exp2(o["ey"]).to(dtype), torch.exp2(o["ex"]).to(dtype)
+    if q.startswith("y"):
+        return sy[co]
+    if q.startswith("dx"):
+        return sx[ci]
+    return 1.0 / (sy[co].view(-1, 1, 1, 1) * sx[ci2])
+
+
+def restate(rt, o, dtype=torch.float64, bias=None):
+    """{"y", "dx", "dx_acc", "dw"} of the operations the route has, on its (sub-sampled) channels, with the scaled kind's
+    powers of two removed.  dtype float32 gives torch's own fp32 result in the same form."""
+    ci = channels(rt)[1]
+    r = rounded(rt, o)
+    out = {}
+    if "fwd" in rt.names:
+        out["y"] = conv_fwd(rt, r["x"], r["w_f"], dtype, bias) * factor(rt, o, "y", dtype)
+    if "dgrad" in rt.names:
+        dx = conv_dgrad(rt, r["dy"], r["w_d"], dtype)
+        out["dx"] = dx * factor(rt, o, "dx", dtype)
+        out["dx_acc"] = (o["base"][..., ci].to(dtype) + dx) * factor(rt, o, "dx", dtype)
+    if "wgrad" in rt.names:
+        out["dw"] = conv_wgrad(rt, r["x"], r["dy_w"], dtype) * factor(rt, o, "dw", dtype)
+    return out
+
+
+def unscale(rt, o, got):
+    """a kernel's outputs (full tensors, fp32, host) in the form restate() returns: channel subset, powers of two removed"""
+    co, ci, ci2 = channels(rt)
+    out = {}
+    for k, v in got.items():
+        v = v.double()
+        v = v[..., co] if k.startswith("y") else (v[..., ci] if k.startswith("dx") else v[co][..., ci2])
+        out[k] = v * factor(rt, o, k)
+    return out
+
+
+@contextlib.contextmanager
+def one_thread():
+    old = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(old)
+
+
+def floor(rt, o, ref=None):
+    """{quantity: rel_err of torch's fp32 CPU operator against the float64 restatement} on one thread"""
+    ref = restate(rt, o) if ref is None else ref
+    with one_thread():
+        f32 = restate(rt, o, torch.float32)
+    return dict((k, rel_err(f32[k], ref[k])) for k in ref)
+
+
+def check_name(rt, q):
+    """the FLOOR key of a route's quantity"""
+    return "%s.%s" % (rt.id, q)
+
+
+# ---- the bf16x6 product on the CPU ---------------------------------------------------------------------------------------------
+def split3(x):
+    """the truncating 3-way split of csrc/planes.h in torch integer ops: (hi, mid, lo) fp32 tensors, each with a zero low
+    half-word (bf16-representable), hi + mid + lo == x bit for bit (for |x| >= 2^-110, as the kernel's)"""
+    assert x.dtype == torch.float32
+    trunc = lambda v: (v.contiguous().view(torch.int32) & -65536).view(torch.float32)
+    hi = trunc(x)
+    r1 = x - hi
+    mid = trunc(r1)
+    lo = trunc(r1 - mid)
+    return hi, mid, lo
+
+
+SIX = ((0, 0), (0, 1), (1, 0), (0, 2), (2, 0), (1, 1))          # (plane of a, plane of b): h.h, h.m, m.h, h.l, l.h, m.m
+MUTANTS = collections.OrderedDict(
+    [("drop a%s.b%s" % ("hml"[i], "hml"[j]), tuple(p for p in SIX if p != (i, j))) for i, j in SIX[1:]] +
+    [("mid for lo in a", tuple((1, 0) if p == (2, 0) else p for p in SIX)),
+     ("mid for lo in b", tuple((0, 1) if p == (0, 2) else p for p in SIX))])
+
+
+def plane_terms(f, a, b):
+    """{(i, j): f(plane i of a, plane j of b)} in float64 for the six pairs; f is the bilinear operation on fp32-valued inputs"""
+    pa, pb = split3(a), split3(b)
+    return dict(((i, j), f(pa[i], pb[j])) for i, j in SIX)
+
+
+def combine(terms, keep=SIX):
+    """the chosen plane-pair products summed in float64 and rounded ONCE to fp32 (a pair may appear twice: a misrouted plane)"""
+    return sum(terms[p] for p in keep).float()
+
+
+def six_term(f, a, b, keep=SIX, stage=None):
+    """f(a, b) as the bf16x6 kernels form it: the plane pairs of `keep` in float64, rounded once to fp32.  stage: a function
+    that zeroes b outside one K stage -- `keep` then applies inside that stage only and the rest of K keeps all six pairs."""
+    if stage is None:
+        return combine(plane_terms(f, a, b), keep)
+    inside = stage(b)
+    return (sum(plane_terms(f, a, b - inside)[p] for p in SIX) + sum(plane_terms(f, a, inside)[p] for p in keep)).float()
+
+
+def bilinear_ops(rt, o):
+    """{quantity: (f, a, b)} -- each operation of the route as a bilinear function of two fp32 operands"""
+    r = rounded(rt, o)
+    ops = {}
+    if "fwd" in rt.names:
+        ops["y"] = (lambda a, b: conv_fwd(rt, a, b), r["x"], r["w_f"])
+    if "dgrad" in rt.names:
+        ops["dx"] = (lambda a, b: conv_dgrad(rt, a, b), r["dy"], r["w_d"])
+    if "wgrad" in rt.names:
+        ops["dw"] = (lambda a, b: conv_wgrad(rt, a, b), r["x"], r["dy_w"])
+    return ops
+
+
+# ---- host queries: which entry point the op wrappers take and which kernel it launches ---------------------------------------------
+KIND = {"iswm_conv2d_fwd": 0, "iswm_conv2d_dgrad": 1, "iswm_conv2d_dgrad_wt": 1, "iswm_conv2d_wgrad": 2, "iswm_conv2d_fwd_packed": 3,
+        "iswm_conv2d_dgrad_packed": 4, "iswm_conv2d_fwd_pl2": 5, "iswm_conv2d_dgrad_pl2": 6, "iswm_conv2d_dgrad_pl2_bn": 6,
+        "iswm_conv2d_wgrad_planes": 7}
+
+
+@contextlib.contextmanager
+def conv_math(rt):
+    from iswm_amd import _lib
+    lib = _lib.load()
+    old = lib.iswm_get_conv_math()
+    lib.iswm_set_conv_math(MATH[rt.mode])
+    try:
+        yield lib
+    finally:
+        lib.iswm_set_conv_math(old)
+
+
+def planes_operand(rt, c):
+    """does an activation with c gathered channels travel as planes on this route (as network/_hip.py decides)?"""
+    return rt.mode in ("pl", "bf16pl") and c % 64 == 0
+
+
+def desc(rt, ldx=None, ldy=None, cout=None):
+    from iswm_amd import _lib
+    n, h, w, cin, co, k, stride, pad, dil = rt.geom
+    co = co if cout is None else cout
+    return _lib.ConvDesc(n, h, w, cin, out_size(h, k, stride, pad, dil), out_size(w, k, stride, pad, dil), co, k, k, stride, pad, dil,
+                         ldx or cin, ldy or co)
+
+
+def kernel_name(lib, d, kind):
+    buf = ctypes.create_string_buffer(64)
+    assert lib.iswm_conv2d_kernel_name(ctypes.byref(d), kind, buf, 64) == 0
+    return buf.value.decode()
+
+
+def planned(rt):
+    """{operation: (entry point, kernel name)} from the library's own host-side queries, following the choices of
+    iswm_amd/ops.py -- needs no GPU.  The GPU tests assert that the wrappers made the same calls."""
+    cin, cout = rt.geom[3], rt.geom[4]
+    out = {}
+    with conv_math(rt) as lib:
+        d = desc(rt)
+        ref = ctypes.byref(d)
+        if "fwd" in rt.names:
+            if planes_operand(rt, cin) and lib.iswm_conv2d_pl2_weight_bytes(ref, 0):
+                e = "iswm_conv2d_fwd_pl2"
+            else:
+                e = "iswm_conv2d_fwd_packed" if lib.iswm_conv2d_packed_weight_bytes(ref, 0) else "iswm_conv2d_fwd"
+            out["fwd"] = (e, kernel_name(lib, d, KIND[e]))
+        if "dgrad" in rt.names:
+            if planes_operand(rt, cout) and lib.iswm_conv2d_pl2_weight_bytes(ref, 1):
+                e = "iswm_conv2d_dgrad_pl2"
+            elif lib.iswm_conv2d_packed_weight_bytes(ref, 1):
+                e = "iswm_conv2d_dgrad_packed"
+            else:
+                e = "iswm_conv2d_dgrad_wt" if lib.iswm_conv2d_dgrad_wants_wt(ref) else "iswm_conv2d_dgrad"
+            out["dgrad"] = (e, kernel_name(lib, d, KIND[e]))
+        if "wgrad" in rt.names:
+            d8 = desc(rt, cout=(cout + 7) // 8 * 8)
+            if planes_operand(rt, cin) and lib.iswm_conv2d_wgrad_planes_ok(ctypes.byref(d8)):
+                out["wgrad"] = ("iswm_conv2d_wgrad_planes", kernel_name(lib, d8, 7))
+            else:
+                out["wgrad"] = ("iswm_conv2d_wgrad", kernel_name(lib, d, 2))
+    return out
+
+
+def wgrad_workspace(rt):
+    """bytes of split slabs the planes weight gradient asks for: > 0 means a multi-split plan and a reduction kernel after it"""
+    with conv_math(rt) as lib:
+        return lib.iswm_conv2d_wgrad_planes_workspace(ctypes.byref(desc(rt, cout=(rt.geom[4] + 7) // 8 * 8)))
+
+
+# ---- the fused ASPP pair: four branches (1 x 1 and three atrous 3 x 3) over ONE input, as branch routes that share x ---------------
+ASPP = collections.OrderedDict([      # n, h, w, cin, cout, rates
+    ("aspp_small", (1, 9, 11, 64, 128, (6, 12, 18))),       # every rate reaches past the map: centre taps only at the far edge
+    ("aspp_large", (1, 20, 21, 64, 128, (6, 12, 18))),      # larger than the largest rate: every tap of every branch in bounds
+])
+ASPP_NAMES = ("k_conv_pl2t<false>", "k_conv_pl2t<true>")
+
+
+def aspp_routes(cid):
+    n, h, w, cin, cout, rates = ASPP[cid]
+    return [_r("%s.b%d" % (cid, b), "pl", (n, h, w, cin, cout, k, 1, dl * (k - 1) // 2, dl), "k_conv_pl2t<false>", None, "k_wgrad")
+            for b, (k, dl) in enumerate(zip((1, 3, 3, 3), (1,) + tuple(rates)))]
+
+
+def aspp_kinds(cid):
+    out = ["dense", "scaled", "int"]
+    for b in range(4):
+        out += ["b%ds0" % b, "b%dsL" % b] + (["b%dt%d" % (b, t) for t in range(1, 9)] if b else [])
+    return out
+
+
+ASPP_CASES = [(cid, kind) for cid in ASPP for kind in aspp_kinds(cid)]
+
+
+def aspp_operands(cid, kind):
+    """per-branch operand dicts over one shared x / base / ex; kind "b<i><stage>" isolates that stage of branch i and zeroes
+    the other branches' weights and weight-gradient dy"""
+    rts = aspp_routes(cid)
+    if kind[0] == "b":
+        os_ = [operands(rt, kind[2:] if b == int(kind[1]) else "zero", xkey=cid) for b, rt in enumerate(rts)]
+    else:
+        os_ = [operands(rt, kind, xkey=cid) for rt in rts]
+    if kind != "int":                             # one base for the summed gradient, at its magnitude
+        base = os_[0]["base_unit"] * sum(o["dx_scale"] ** 2 for o in os_) ** 0.5
+        for o in os_:
+            o["base"] = base
+    return os_
+
+
+def aspp_restate(cid, os_, dtype=torch.float64):
+    """{"b<i>.y", "b<i>.dw", "dx", "dx_acc"}: dx = sum over branches of conv^T(dy_b, w_b)"""
+    out, dx = {}, 0
+    for b, (rt, o) in enumerate(zip(aspp_routes(cid), os_)):
+        r = restate(rt, o, dtype)
+        out["b%d.y" % b], out["b%d.dw" % b] = r["y"], r["dw"]
+        dx = dx + conv_dgrad(rt, o["dy"], o["w_d"], dtype)
+    f = factor(rts0(cid), os_[0], "dx", dtype)
+    out["dx"], out["dx_acc"] = dx * f, (os_[0]["base"].to(dtype) + dx) * f
+    return out
+
+
+def rts0(cid):
+    return aspp_routes(cid)[0]
+
+
+def aspp_floor(cid, os_, ref):
+    with one_thread():
+        f32 = aspp_restate(cid, os_, torch.float32)
+    return dict((k, rel_err(f32[k], ref[k])) for k in ref)
+
+
+def aspp_bilinear_ops(cid, os_):
+    """the ASPP quantities as bilinear functions: per-branch forward and weight gradient, and the summed data gradient as a
+    function of (the concatenated dy, the stacked weights)"""
+    rts = aspp_routes(cid)
+    ops = {}
+    for b, (rt, o) in enumerate(zip(rts, os_)):
+        ops["b%d.y" % b] = ((lambda a, w, rt=rt: conv_fwd(rt, a, w)), o["x"], o["w_f"])
+        ops["b%d.dw" % b] = ((lambda a, d, rt=rt: conv_wgrad(rt, a, d)), o["x"], o["dy_w"])
+    cout = ASPP[cid][4]
+    dyc = torch.cat([o["dy"] for o in os_], 3)
+    wflat = torch.cat([o["w_d"].reshape(-1) for o in os_])
+
+    def dsum(dy, wf):
+        tot, off = 0, 0
+        for b, (rt, o) in enumerate(zip(rts, os_)):
+            nel = o["w_d"].numel()
+            tot = tot + conv_dgrad(rt, dy[..., b * cout:(b + 1) * cout], wf[off:off + nel].view_as(o["w_d"]))
+            off += nel
+        return tot
+
+    ops["dx"] = (dsum, dyc, wflat)
+    return ops
+
+
+def aspp_plan_bytes(cid, kind):
+    from iswm_amd import _lib
+    n, h, w, cin, cout, rates = ASPP[cid]
+    lib = _lib.load()
+    old = lib.iswm_get_conv_math()
+    lib.iswm_set_conv_math(1)
+    try:
+        d = _lib.ConvDesc(n, h, w, cin, h, w, cout, 1, 1, 1, 0, 1, cin, cout)
+        ks, dl = (ctypes.c_int * 4)(1, 3, 3, 3), (ctypes.c_int * 4)(1, *rates)
+        return lib.iswm_aspp_plan_bytes(ctypes.byref(d), 4, ks, dl, kind)
+    finally:
+        lib.iswm_set_conv_math(old)
+
+
+# ---- bounds ----------------------------------------------------------------------------------------------------------------------
+# bound = 4 x floor, except the data gradient of pl_3x3 (3 x 3 x 128 gathered channels, K = 1152): 8 x floor.  torch's CPU data
+# gradient is one GEMM per tap (fp32 chains of Cout = 128 products) followed by col2im additions; the kernel accumulates all
+# 9 x 128 products in ONE fp32 chain.  In the random-walk model a chain `taps` times longer carries sqrt(taps) = 3 times the
+# rounding error, which would allow 12 x floor; the sensitivity condition of tests/test_conv_ref_cpu.py (3 x bound <= the
+# weakest single-term mutant: 9.3e-6 on dx, 6.9e-6 on dx_acc) allows at most 9.9, and 8 -- the project's margin doubled once
+# more -- is what is taken.  Measured figures: profiles/conv_kernel_tests.txt, finding 1.
+FACTOR = {"pl_3x3.dx": 8.0, "pl_3x3.dx_acc": 8.0}
+
+
+def bound(key):
+    return FACTOR.get(key, 4.0) * FLOOR[key]
+
+
+# ---- recorded floors (profiles/conv_kernel_tests.txt carries the same figures; tests/test_conv_ref_cpu.py ties the two) ------
+FLOOR = {
+    "pl_1x1.y": 2.6e-07,
+    "pl_1x1.dx": 4.4e-07,
+    "pl_1x1.dx_acc": 3.0e-07,
+    "pl_1x1.dw": 2.4e-07,
+    "pl_3x3.y": 5.1e-07,
+    "pl_3x3.dx": 3.0e-07,
+    "pl_3x3.dx_acc": 2.3e-07,
+    "pl_3x3.dw": 4.0e-07,
+    "pl_3x3.y_bias": 4.7e-07,
+    "pl_narrow.y": 3.4e-07,
+    "pl_narrow.dx": 3.2e-07,
+    "pl_narrow.dx_acc": 2.6e-07,
+    "pl_narrow.dw": 4.5e-07,
+    "pl_narrow.y_bias": 2.4e-07,
+    "pl_narrow3.y": 5.1e-07,
+    "pl_narrow3.dx": 3.4e-07,
+    "pl_narrow3.dx_acc": 2.6e-07,
+    "pl_narrow3.dw": 4.2e-07,
+    "pl_s2.dx": 6.1e-07,
+    "pl_s2.dx_acc": 4.4e-07,
+    "pl_s2.dw": 4.6e-07,
+    "pl_s3.dx": 3.3e-07,
+    "pl_s3.dx_acc": 3.4e-07,
+    "pl_s3.dw": 2.7e-07,
+    "pl_s2_fwd.y": 4.9e-07,
+    "pl_s2_1x1.y": 4.2e-07,
+    "pl_s2_1x1.dx": 4.7e-07,
+    "pl_s2_1x1.dx_acc": 3.7e-07,
+    "pl_s2_1x1.dw": 3.4e-07,
+    "pl_s2_1x1.y_bias": 3.2e-07,
+    "pl_c200_d2.y": 4.9e-07,
+    "pl_c200_d2.dw": 3.7e-07,
+    "pl_c320_fwd.y": 2.4e-07,
+    "pl_c320_fwd.dw": 3.4e-07,
+    "pl_c320_dgrad.dx": 3.6e-07,
+    "pl_c320_dgrad.dx_acc": 2.4e-07,
+    "pl_c320_dgrad.dw": 5.7e-07,
+    "pl_pad0.y": 4.0e-07,
+    "pl_pad0.dx": 4.1e-07,
+    "pl_pad0.dx_acc": 3.7e-07,
+    "pl_pad0.dw": 3.9e-07,
+    "pl_d18.y": 1.6e-07,
+    "pl_d18.dx": 4.4e-07,
+    "pl_d18.dx_acc": 2.2e-07,
+    "pl_d18.dw": 3.6e-07,
+    "pl_5x5.y": 2.9e-07,
+    "pl_5x5.dx": 2.5e-07,
+    "pl_5x5.dx_acc": 2.2e-07,
+    "pl_5x5.dw": 1.4e-07,
+    "pl_map1.y": 1.4e-07,
+    "pl_map1.dx": 2.6e-07,
+    "pl_map1.dx_acc": 2.6e-07,
+    "pl_map1.dw": 6.9e-08,
+    "pl_rect.y": 4.9e-07,
+    "pl_rect.dx": 4.3e-07,
+    "pl_rect.dx_acc": 2.1e-07,
+    "pl_rect.dw": 3.0e-07,
+    "pl_rect_split.dw": 7.4e-07,
+    "pl_wsplit.dw": 2.1e-07,
+    "pl_r9_fwd.y": 3.4e-07,
+    "pl_r9_dgrad.dx": 3.1e-07,
+    "pl_r9_dgrad.dx_acc": 2.2e-07,
+    "pl_r10_fwd.y": 3.1e-07,
+    "pl_r10_dgrad.dx": 2.9e-07,
+    "pl_r10_dgrad.dx_acc": 1.9e-07,
+    "pl_r5_narrow.y": 3.6e-07,
+    "pl_r5_narrow.dx": 2.7e-07,
+    "pl_r5_narrow.dx_acc": 2.3e-07,
+    "pl_wide.y": 6.0e-07,
+    "pl_wide.dx": 4.7e-07,
+    "pl_wide.dx_acc": 3.3e-07,
+    "pl_wide.dw": 5.4e-07,
+    "pl_wide3.y": 2.8e-07,
+    "pl_c48.y": 4.8e-07,
+    "pl_c48.dx": 2.2e-07,
+    "pl_c48.dx_acc": 1.6e-07,
+    "pl_c48.dw": 3.5e-07,
+    "pl_c4.y": 4.1e-07,
+    "pl_c4.dx": 9.4e-08,
+    "pl_c4.dx_acc": 1.1e-07,
+    "pl_c4.dw": 4.0e-07,
+    "x6_1x1.y": 2.6e-07,
+    "x6_1x1.dx": 5.0e-07,
+    "x6_1x1.dx_acc": 2.7e-07,
+    "x6_1x1.dw": 2.7e-07,
+    "x6_1x1.y_bias": 2.4e-07,
+    "x6_s2.y": 3.9e-07,
+    "x6_s2.dx": 4.4e-07,
+    "x6_s2.dx_acc": 3.7e-07,
+    "x6_s2.dw": 2.8e-07,
+    "x6_patch.y": 5.9e-07,
+    "x6_patch.dx": 3.3e-07,
+    "x6_patch.dx_acc": 2.2e-07,
+    "x6_patch.dw": 3.7e-07,
+    "x6_patch.y_bias": 4.6e-07,
+    "x6_patch_d2.y": 5.7e-07,
+    "x6_patch_d2.dx": 2.1e-07,
+    "x6_patch_d2.dx_acc": 1.7e-07,
+    "x6_patch_d2.dw": 3.9e-07,
+    "x6_m128.y": 3.1e-07,
+    "stem_even.y": 4.1e-07,
+    "stem_even.dw": 5.4e-07,
+    "stem_odd.y": 3.8e-07,
+    "stem_odd.dw": 6.2e-07,
+    "f32_u.y": 2.8e-07,
+    "f32_u.dx": 3.5e-07,
+    "f32_u.dx_acc": 3.0e-07,
+    "f32_u.dw": 2.1e-07,
+    "f32_u.y_bias": 2.6e-07,
+    "f32_u_s2.y": 5.1e-07,
+    "f32_u_s2.dx": 4.2e-07,
+    "f32_u_s2.dx_acc": 3.8e-07,
+    "f32_u_s2.dw": 2.5e-07,
+    "f32_u_m128.y": 3.6e-07,
+    "f32_narrow.y": 4.5e-07,
+    "f32_narrow.dx": 3.4e-07,
+    "f32_narrow.dx_acc": 2.7e-07,
+    "f32_narrow.dw": 4.3e-07,
+    "f32_wide_fwd.y": 2.9e-07,
+    "f32_wide_dgrad.dx": 2.4e-07,
+    "f32_wide_dgrad.dx_acc": 2.0e-07,
+    "bf16_1x1.y": 1.3e-07,
+    "bf16_1x1.dx": 1.7e-07,
+    "bf16_1x1.dx_acc": 1.2e-07,
+    "bf16_1x1.dw": 9.9e-08,
+    "bf16_patch.y": 2.2e-07,
+    "bf16_patch.dx": 1.2e-07,
+    "bf16_patch.dx_acc": 1.1e-07,
+    "bf16_patch.dw": 1.2e-07,
+    "bf16_pl.y": 2.9e-07,
+    "bf16_pl.dx": 1.7e-07,
+    "bf16_pl.dx_acc": 1.2e-07,
+    "bf16_pl.dw": 1.6e-07,
+    "bf16_pl.y_bias": 2.2e-07,
+    "aspp_small.b0.y": 3.4e-07,
+    "aspp_small.b0.dw": 2.7e-07,
+    "aspp_small.b1.y": 4.5e-07,
+    "aspp_small.b1.dw": 3.8e-07,
+    "aspp_small.b2.y": 1.4e-07,
+    "aspp_small.b2.dw": 3.3e-07,
+    "aspp_small.b3.y": 1.6e-07,
+    "aspp_small.b3.dw": 3.6e-07,
+    "aspp_small.dx": 4.0e-07,
+    "aspp_small.dx_acc": 2.5e-07,
+    "aspp_large.b0.y": 2.8e-07,
+    "aspp_large.b0.dw": 4.2e-07,
+    "aspp_large.b1.y": 4.4e-07,
+    "aspp_large.b1.dw": 6.3e-07,
+    "aspp_large.b2.y": 3.5e-07,
+    "aspp_large.b2.dw": 3.9e-07,
+    "aspp_large.b3.y": 3.9e-07,
+    "aspp_large.b3.dw": 4.1e-07,
+    "aspp_large.dx": 3.9e-07,
+    "aspp_large.dx_acc": 2.8e-07,
+}
