@@ -70,7 +70,11 @@ int iswm_conv2d_stat_tile_rows(const iswm_conv_desc* d);
 int iswm_conv2d_stat_tiles(const iswm_conv_desc* d);
 /* y = conv(x, w) (+ bias).  If stat_partials != NULL it receives per-M-tile
  * per-channel statistics [2][tiles][Cout] = {S_t, M2_t} (see iswm_colstat) for the training-mode
- * BatchNorm that follows every conv (network/backbone/resnet.py:89-93). */
+ * BatchNorm that follows every conv (network/backbone/resnet.py:89-93).
+ * The partials describe the convolution BEFORE the bias: they are the same bits with bias == NULL, and with a bias they are
+ * the statistics of y - bias, not of y (M2_t is the same either way, S_t lacks n_t * bias).  A caller that normalises a
+ * biased output takes its statistics from iswm_colstat_res instead.  The same holds for iswm_conv2d_fwd_packed and
+ * iswm_conv2d_fwd_pl2 (tests/test_bn_partials_gpu.py). */
 int iswm_conv2d_fwd(const iswm_conv_desc* d, const float* x, const float* w, const float* bias,
                     float* y, float* stat_partials, iswm_stream_t stream);
 /* dx (=|+=) conv_transpose(dy, w): autograd backward of the conv wrt its input;
@@ -111,6 +115,7 @@ int iswm_pack_weights_batch(const iswm_pack_job* jobs_dev, int njobs, int total_
  * image patches of varying size and their row counts follow the planes as floats (partials + 2*tiles*Cout), so
  * the buffer is 2*tiles*Cout + tiles floats -- iswm_bn_finalize takes tile_rows = 0 for that layout. */
 int iswm_conv2d_fwd_packed_stat_layout(const iswm_conv_desc* d, int* tiles, int* tile_rows);
+/* (stat_partials: the statistics of the convolution BEFORE the bias, as iswm_conv2d_fwd's) */
 int iswm_conv2d_fwd_packed(const iswm_conv_desc* d, const float* x, const void* wpk, const float* bias,
                            float* y, float* stat_partials, iswm_stream_t stream);
 int iswm_conv2d_dgrad_packed(const iswm_conv_desc* d, const float* dy, const void* wpk, float* dx, int accumulate,
@@ -147,6 +152,8 @@ int iswm_bilinear_fwd_pl(const float* x, int N, int Hi, int Wi, int C, int ldx, 
 size_t iswm_conv2d_pl2_weight_bytes(const iswm_conv_desc* d, int kind);
 int iswm_conv2d_pl2_pack_weights(const iswm_conv_desc* d, int kind, const float* w, void* packed, iswm_stream_t stream);
 int iswm_conv2d_pl2_tile_rows(const iswm_conv_desc* d, int kind);
+/* (stat_partials: [2][ceil(M / iswm_conv2d_pl2_tile_rows(d, 0))][Cout], the statistics of the convolution BEFORE the bias, as
+ * iswm_conv2d_fwd's) */
 int iswm_conv2d_fwd_pl2(const iswm_conv_desc* d, const void* xp, int64_t plane_stride, const void* wpk,
                         const float* bias, float* y, float* stat_partials, iswm_stream_t stream);
 int iswm_conv2d_dgrad_pl2(const iswm_conv_desc* d, const void* dyp, int64_t plane_stride, const void* wpk,

@@ -116,23 +116,21 @@ __global__ __launch_bounds__(512) void k_stem_fwd(const ConvArgs a) {
         }
 
         // ---- epilogue: lane -> pixel lp of each row block, its 4 registers -> channels 16 cb + 4 g + r
-        if (a.bias != nullptr) {
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) {
-                const float4 bv = *reinterpret_cast<const float4*>(a.bias + cb * 16 + 4 * g);
-#pragma unroll
-                for (int rb = 0; rb < RB; ++rb) {
-                    acc[rb][cb][0] += bv.x; acc[rb][cb][1] += bv.y; acc[rb][cb][2] += bv.z; acc[rb][cb][3] += bv.w;
-                }
-            }
-        }
+        // (the bias is added at the store only: the BatchNorm partials below describe the convolution BEFORE the bias, as those of
+        // every other forward epilogue do -- include/iswm_hip.h)
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
             if (valid[rb]) {
                 float* o = a.y + (size_t)(m0 + rb * 16 + lp) * a.ldy + 4 * g;
 #pragma unroll
-                for (int cb = 0; cb < 4; ++cb)
-                    *reinterpret_cast<float4*>(o + cb * 16) = make_float4(acc[rb][cb][0], acc[rb][cb][1], acc[rb][cb][2], acc[rb][cb][3]);
+                for (int cb = 0; cb < 4; ++cb) {
+                    float4 v = make_float4(acc[rb][cb][0], acc[rb][cb][1], acc[rb][cb][2], acc[rb][cb][3]);
+                    if (a.bias != nullptr) {
+                        const float4 bv = *reinterpret_cast<const float4*>(a.bias + cb * 16 + 4 * g);
+                        v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
+                    }
+                    *reinterpret_cast<float4*>(o + cb * 16) = v;
+                }
             }
         }
         if (a.stats != nullptr) {

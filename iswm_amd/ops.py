@@ -337,7 +337,8 @@ def weights_changed():
 
 def conv2d_fwd(x, w_ohwi, g, bias=None, out=None, want_stats=False, wpk=None, wpk2=None):
     """y = conv(x, w) [+ bias]; returns (y, partials|None, (tiles, tile_rows)).  wpk: this weight already packed
-    for the forward kernel (network._hip.WeightPacker), else it is packed here."""
+    for the forward kernel (network._hip.WeightPacker), else it is packed here.  The partials describe the convolution BEFORE
+    the bias (the same bits with and without one): a caller that normalises a biased output takes colstat(y) instead."""
     _check_w(w_ohwi, g)
     if out is None:
         out = new_act(g.n, g.ho, g.wo, g.cout, x.device)

@@ -7,7 +7,7 @@ product in every case, also when only one K stage carries it).  Exact-integer op
 taken from the kernel under test; each test asserts the entry point the wrapper took and the kernel it launches, so a planner
 change cannot move a case to another kernel unnoticed.  profiles/conv_kernel_tests.txt has the measured figures.
 
-Not covered here: the BatchNorm partials of the epilogues (the older convolution tests pin them)."""
+The BatchNorm partials of the epilogues are pinned tile by tile in tests/test_bn_partials_gpu.py."""
 import ctypes
 
 import pytest
@@ -169,8 +169,8 @@ def test_conv_bias_and_channel_slices(rid, monkeypatch):
 @pytest.mark.parametrize("accumulate", [False, True])
 def test_conv_dgrad_bn_relu_codes(rid, code, accumulate, monkeypatch):
     """iswm_conv2d_dgrad_pl2_bn at each relu code.  Codes 0 and 2 store the plain gradient (the pattern only enters the
-    BatchNorm partials, which are out of scope here); code 3 stores it masked by (hi plane of the producer's saved output
-    > 0): the reference applies the same mask in float64 and masked elements must be exactly 0 -- on a saved output that
+    BatchNorm partials: tests/test_bn_partials_gpu.py::test_backward_sums_and_their_consumer pins those); code 3 stores it
+    masked by (hi plane of the producer's saved output > 0): the reference applies the same mask in float64 and masked elements must be exactly 0 -- on a saved output that
     holds exact zeros, negative zeros and tiny positive values (2^-100: its hi plane is still positive)"""
     from iswm_amd import ops
     rt = R.ROUTE[rid]

@@ -432,14 +432,15 @@ def test_batchnorm_large_mean_batch_statistics(stats, shape):
     """colstat + bn_finalize where |mean| is 2000 - 3000 standard deviations.  A one-pass sum of squares is off by 0.6 - 3 here
     (test_streaming_ref_cpu.test_naive_variance_misses_the_bound_by_100x); the centred tile statistics are not.
 
-    SCOPE: this pins the column-pass producer only (ops.colstat = iswm_colstat_res, which serves depthwise filters other than 3 x 3
+    SCOPE: this pins the column-pass producer (ops.colstat = iswm_colstat_res, which serves depthwise filters other than 3 x 3
     and biased convolutions in front of a BatchNorm).  Its third plane R_t makes bn_finalize's merge exact.  Before it the
     variance was 1.3e-5 .. 3.3e-5 off here (bound 3e-7): the fp32 tile sum S_t puts the tile mean off by ulp(S_t) / n_t, and the
     merge M2 = sum M2_t + n_t (S_t / n_t - mean)^2 loses the cross term, ~2^-23 |mean| / sigma of the variance.  The OTHER producers
     of tile statistics -- the convolution epilogues and dwconv3.hip, which feed almost every BatchNorm of the models -- still
-    publish the pair {S_t, M2_t} and still carry that error at such means; their tests (test_hip_kernels.test_conv_fwd_dgrad_wgrad,
-    test_dwconv3_gpu) run at |mean| ~ sigma with a 1e-5 bound.  test_colstat_residual_plane_leaves_the_pair_alone shows the pair
-    alone at this input."""
+    publish the pair {S_t, M2_t} and still carry that error at such means.  tests/test_bn_partials_gpu.py pins them: every tile
+    of every producer against float64 of the stored output at 4 x the fp32 floor, also at |mean| / sigma in the tens to
+    hundreds, and the loss of their pair merge as an identity (the rounding of S_t is ALL of it).
+    test_colstat_residual_plane_leaves_the_pair_alone shows the pair alone at this input."""
     x, gamma, beta, _, _ = R.bn_inputs(stats, shape, False)
     f = R.bn_fwd_ref(x, gamma, beta, None, False)
     coef, rm, rv = bn_statistics(x, gamma, beta)
