@@ -61,7 +61,9 @@ typedef struct {
 int iswm_set_conv_math(int mode);
 int iswm_get_conv_math(void);
 /* name of the device kernel a call with this geometry launches (kind 0 fwd, 1 dgrad, 2 wgrad, 3 fwd_packed,
- * 4 dgrad_packed, 5 fwd_pl2, 6 dgrad_pl2) --
+ * 4 dgrad_packed, 5 fwd_pl2 and 6 dgrad_pl2 / dgrad_pl2_bn, 7 wgrad_planes), from the same plan the call launches by.
+ * Kind 1 names two entry points: it describes iswm_conv2d_dgrad_wt where iswm_conv2d_dgrad_wants_wt answers 1 (the call
+ * the op wrappers then make) and iswm_conv2d_dgrad otherwise --
  * lets a profiler label its timings with the symbol rocprofv3 reports */
 int iswm_conv2d_kernel_name(const iswm_conv_desc* d, int kind, char* buf, int buflen);
 /* M tiling the forward kernel will use for this geometry: rows per tile (128 or 64) and number of

@@ -1,7 +1,9 @@
 // Declarations shared by all convolution kernels and their launchers: the argument structs (ConvArgs, BnFuse, PatchArgs),
-// the row -> pixel maps, the weight packing of the planes kernels and the launch entry points of every family --
-// conv_mfma.hip (fp32 kernels and the C entry points), conv_mfma_u.hip (tap-uniform fast path), conv_mfma_x6*.hip (round-1
-// bf16x6), conv_mfma_pl2*.hip (planes kernels; their device-side pieces are in conv_pl2_stage.h), conv_stem.hip.
+// the row -> pixel maps, the weight packing of the planes kernels, the tile choices and launch entry points of every family
+// -- conv_mfma.hip (fp32 kernels), conv_mfma_u.hip (tap-uniform fast path), conv_mfma_x6*.hip (round-1 bf16x6),
+// conv_mfma_pl2*.hip (planes kernels; their device-side pieces are in conv_pl2_stage.h), conv_stem.hip, conv_wgrad_pl.hip
+// (planes weight gradient) -- and the weight-gradient plan.  conv_api.hip is the host-only file over them: the C entry
+// points, the conv-math state and the route planner that decides, once per call, which family and tile a geometry gets.
 #pragma once
 #include <stdlib.h>
 #include "common.h"
@@ -164,10 +166,9 @@ __device__ __forceinline__ void pack_weights_pl2_body(const float* __restrict__ 
 
 // second-generation planes kernel: (16*rbw) x 128 tiles, one workgroup per CU (conv_mfma_pl2.hip)
 int pack_job_blocks_pl2(int Cout, int T, int Cin, bool dgrad);
-int conv_pl2_pick_rbw(int64_t M, int cols);
-void conv_pl2_plan(int64_t M, int cols, int K, bool wide_ok, int* rbw, int* wide);      // tile height and 128- / 256-column form
+void conv_pl2_plan(int64_t M, int cols, int K, bool wide_ok, int* rbw, int* wide, int* wm);   // tile height, 128- / 256-column form, wave rows
 bool launch_conv_pl2w(ConvArgs a, hipStream_t s, bool dgrad, int planes, int rbw);  // conv_mfma_pl2w.hip
-bool launch_conv_pl2(ConvArgs a, hipStream_t s, bool dgrad, int planes, int rbw);
+bool launch_conv_pl2(ConvArgs a, hipStream_t s, bool dgrad, int planes, int rbw, int wm);  // wm 2: 64-column layout <rbw / 2, 2>
 size_t packed_weight_bytes_pl2(int Cout, int T, int Cin, bool dgrad, int planes);
 void launch_pack_weights_pl2(const float* w, void* packed, int Cout, int T, int Cin, bool dgrad, int planes, hipStream_t s);
 
@@ -193,11 +194,34 @@ struct PatchArgs {
 bool conv_patch_plan(int RH, int RW, int KH, int KW, int dil, int* PH, int* PW);
 void launch_conv_x6_patch(PatchArgs a, bool dgrad, int planes, hipStream_t s);
 
-// tap-uniform fast path (conv_mfma_u.hip); each returns false when the geometry does not qualify
-bool launch_conv_fwd_u(ConvArgs a, hipStream_t s);
+// tap-uniform fast path (conv_mfma_u.hip), gathered channels % 32 == 0; each returns false when it has no such tile
 void conv_pick_tile(int64_t M, int cols, int* bm, int* bn);
-void conv_pick_tile_x6(int64_t M, int cols, int K, bool dgrad, bool pointwise, int* bm, int* bn);
-int conv_fwd_tile_rows(int64_t M, int Cin, int Cout);   // rows per forward M tile == rows per BN partial
-bool launch_conv_dgrad_u(ConvArgs a, hipStream_t s);
+bool launch_conv_fwd_u(ConvArgs a, hipStream_t s, int bm, int bn);
+bool launch_conv_dgrad_u(ConvArgs a, hipStream_t s, int bm, int bn);
+void conv_pick_tile_x6(int64_t M, int cols, int K, bool dgrad, bool pointwise, int* bm, int* bn);   // conv_mfma_x6.hip
+
+// bf16 planes per operand of the packed / planes / weight-gradient kernels under a conv math: 3 (bf16x6) or 1 (bf16)
+inline int math_planes(int math) { return math == 2 ? 1 : 3; }
+
+// Plan of one weight-gradient call.  plan_wgrad (conv_api.hip) fills it for iswm_conv2d_wgrad, plan_wgrad_pl
+// (conv_wgrad_pl.hip) for iswm_conv2d_wgrad_planes; the workspace queries, iswm_conv2d_kernel_name and the launches read it.
+struct WgPlan {
+    int kernel;                   // wgrad: 0 k_conv_wgrad, 1 k_stem_wgrad;  planes: 0 k_wgrad_pl, 1 k_wgrad_plw, 2 k_wgrad_pls
+    int planes;                   // bf16 planes per operand: 3 (bf16x6) or 1 (bf16)
+    int x6;                       // wgrad: operands split into planes on the fly (conv math >= 1) or the fp32 MFMA
+    int bm, bn;                   // tile: 128 x 128 or 64 x 64 (wgrad); 128 x 128 or 128 x 256 (planes)
+    int mode;                     // wgrad: MODE of k_conv_wgrad (2 pointwise same-size, 1 same-size, 0 any geometry)
+    int MT, NT, nsplit, psplit;   // tile counts, pixel splits and pixels per split (multiple of 32)
+    int wide, rect, vote, always; // planes: 256-column tiles, tap rectangles (2: one column block per XCD), culling vote, no culling
+    unsigned char tap_order[32];  // planes, rect: taps by descending rectangle size
+    size_t workspace;             // bytes of split slabs the call needs
+};
+WgPlan plan_wgrad_pl(const iswm_conv_desc* d, int math);
+
+// exact-fp32 kernels (conv_mfma.hip): 128 x bn tiles, bn 64 or 128
+void launch_conv_fwd_f32(ConvArgs a, hipStream_t s, int bn);
+void launch_conv_dgrad_f32(ConvArgs a, hipStream_t s, int bn);
+void launch_conv_wgrad(ConvArgs a, hipStream_t s, const WgPlan& p);
+void launch_reduce_slabs(const float* slabs, float* dst, int64_t n4, int nsplit, hipStream_t s);
 
 }  // namespace iswm

@@ -24,11 +24,7 @@
 //     the training-mode BatchNorm that follows every conv (deterministic two-stage stats);
 //   * wgrad flattens (tap, cin) into the GEMM N axis and splits the pixel (K) axis across
 //     workgroups into slabs that a second kernel sums in a fixed order (bit-reproducible).
-#include <stdlib.h>
-#include <string.h>
-
-#include <atomic>
-
+// The C entry points that choose between these kernels and the other families are in conv_api.hip.
 #include "conv_common.h"
 
 namespace iswm {
@@ -700,582 +696,27 @@ void launch_reduce_slabs(const float* slabs, float* dst, int64_t n4, int nsplit,
     hipLaunchKernelGGL(k_reduce_slabs, dim3(stream_grid(n4, 256)), dim3(256), 0, s, slabs, dst, n4, nsplit);
 }
 
-static int validate(const iswm_conv_desc* d) {
-    ISWM_REQUIRE(d != nullptr, "conv: null descriptor");
-    ISWM_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "conv: empty tensor");
-    ISWM_REQUIRE(d->Cin % 4 == 0 && d->Cout % 4 == 0, "conv: Cin (%d) and Cout (%d) must be multiples of 4",
-                 d->Cin, d->Cout);
-    ISWM_REQUIRE(d->ldx % 4 == 0 && d->ldy % 4 == 0 && d->ldx >= d->Cin && d->ldy >= d->Cout,
-                 "conv: bad pixel pitch ldx=%d ldy=%d", d->ldx, d->ldy);
-    ISWM_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->dil > 0 && d->pad >= 0, "conv: bad geometry");
-    int ho = (d->H + 2 * d->pad - d->dil * (d->KH - 1) - 1) / d->stride + 1;
-    int wo = (d->W + 2 * d->pad - d->dil * (d->KW - 1) - 1) / d->stride + 1;
-    ISWM_REQUIRE(ho == d->Ho && wo == d->Wo, "conv: output size %dx%d does not match geometry (%dx%d)", d->Ho,
-                 d->Wo, ho, wo);
-    ISWM_REQUIRE((int64_t)d->N * d->H * d->W * d->ldx < (1ll << 31) &&
-                     (int64_t)d->N * d->Ho * d->Wo * d->ldy < (1ll << 31),
-                 "conv: tensor exceeds 2^31 elements");
-    return 0;
-}
-
-// Tile-width choice for the forward / dgrad kernels.  A CU works through ceil(tiles/256) tiles
-// (co-resident workgroups share its SIMDs), so a 128x128 grid of 274 tiles (the 33x33 stages with 256
-// output channels) costs two full tile times where 128x64 tiles cost three half tile times.
-// Narrow tiles re-read the activation panel once more and pay ~10 % in MFMA:staging ratio.
-static bool use_narrow_tile(int64_t MT, int cols) {
-    if (cols <= 64 || (cols % 128 != 0 && cols % 128 <= 64)) return true;
-    const int64_t t128 = MT * ((cols + 127) / 128), t64 = MT * ((cols + 63) / 64);
-    const double c128 = (double)((t128 + 255) / 256) * 128.0;
-    const double c64 = (double)((t64 + 255) / 256) * 64.0 * 1.10;
-    return c64 < c128;
-}
-
-static ConvArgs base_args(const iswm_conv_desc* d) {
-    ConvArgs a{};
-    a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin;
-    a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
-    a.ldx = d->ldx; a.ldy = d->ldy;
-    return a;
-}
-
-struct WgradPlan {
-    int bm, bn, MT, NT, nsplit, psplit;
-};
-
-static WgradPlan plan_wgrad(const iswm_conv_desc* d, bool x6) {
-    WgradPlan p;
-    const int Ktot = d->KH * d->KW * d->Cin;
-    p.bm = (d->Cout % 128 == 0) ? 128 : 64;
-    p.bn = (p.bm == 128 && (Ktot % 128 == 0 || Ktot >= 1024)) ? 128 : 64;
-    if (p.bn == 64) p.bm = 64;  // instantiated shapes: 128x128 and 64x64
-    p.MT = (d->Cout + p.bm - 1) / p.bm;
-    p.NT = (Ktot + p.bn - 1) / p.bn;
-    const int64_t P = (int64_t)d->N * d->Ho * d->Wo;
-    const int64_t tiles = (int64_t)p.MT * p.NT;
-    // Split count: minimise  rounds x (chunks per workgroup) x chunk time  +  slab write/read time, where a
-    // round is 512 co-resident workgroups (2 per CU) and a 128x128x32 chunk takes ~4.5 us when two
-    // workgroups share a CU.  tiles*splits just above a multiple of 512 costs a whole extra round.
-    // (Three bf16x6 workgroups per CU fit in LDS and registers but measured no faster than two: r01 notes.)
-    (void)x6;
-    const int64_t slots = 512;
-    const double chunk_us = 4.5 * (double)(p.bm * p.bn) / 16384.0;
-    const double slab_us = (double)d->Cout * Ktot * 8.0 / 4.0e6;   // one slab written + read at ~4 TB/s
-    int64_t maxs = (P + 255) / 256;                                 // at least 256 pixels per split
-    if (maxs > 64) maxs = 64;
-    double best = 1e300;
-    p.psplit = (int)((P + 31) / 32 * 32);
-    p.nsplit = 1;
-    for (int64_t ns = 1; ns <= maxs; ++ns) {
-        int64_t ps = ((P + ns - 1) / ns + 31) / 32 * 32;
-        int64_t nsp = (P + ps - 1) / ps;
-        int64_t rounds = (tiles * nsp + slots - 1) / slots;
-        double t = (double)rounds * (double)(ps / 32 + 3) * chunk_us + (nsp > 1 ? (double)nsp * slab_us + 5.0 : 0.0);
-        if (t < best) {
-            best = t;
-            p.psplit = (int)ps;
-            p.nsplit = (int)nsp;
-        }
-    }
-    return p;
-}
-
-}  // namespace iswm
-
-using namespace iswm;
-
-// 0: exact-fp32 MFMA (v_mfma_f32_32x32x2_f32);  1 (default): bf16x6 split on the bf16 matrix cores;  2: bf16.
-// -1 until the first read, which takes ISWM_CONV_MATH unless iswm_set_conv_math got there first.
-static std::atomic<int> g_conv_math{-1};
-static int conv_math() {
-    int m = g_conv_math.load();
-    if (m < 0) {
-        const char* e = getenv("ISWM_CONV_MATH");
-        const int env = (e && (!strcmp(e, "f32") || !strcmp(e, "0"))) ? 0
-                        : (e && (!strcmp(e, "bf16") || !strcmp(e, "2"))) ? 2 : 1;   // default: bf16x6
-        int unset = -1;
-        g_conv_math.compare_exchange_strong(unset, env);      // a mode stored meanwhile by another thread stands
-        m = g_conv_math.load();
-    }
-    return m;
-}
-extern "C" int iswm_set_conv_math(int mode) {
-    ISWM_REQUIRE(mode >= 0 && mode <= 2, "set_conv_math: mode must be 0 (f32), 1 (bf16x6) or 2 (bf16)");
-    g_conv_math = mode;
-    return 0;
-}
-extern "C" int iswm_get_conv_math(void) { return conv_math(); }
-// bf16 planes per operand of the packed / weight-gradient kernels under the current math: 3 (bf16x6) or 1 (bf16)
-static int math_planes() { return conv_math() == 2 ? 1 : 3; }
-
-// Halo-patch kernel applicability (stride-1 KxK, bf16x6, packed weights)
-static bool patch_plan(const iswm_conv_desc* d, bool dgrad, int* PH, int* PW) {
-    if (d->stride != 1 || d->KH * d->KW <= 1) return false;
-    return dgrad ? conv_patch_plan(d->H, d->W, d->KH, d->KW, d->dil, PH, PW)
-                 : conv_patch_plan(d->Ho, d->Wo, d->KH, d->KW, d->dil, PH, PW);
-}
-
-static PatchArgs patch_args(const iswm_conv_desc* d, bool dgrad, int PH, int PW) {
-    PatchArgs p{};
-    p.N = d->N;
-    p.KH = d->KH; p.KW = d->KW; p.dil = d->dil;
-    p.PH = PH; p.PW = PW;
-    if (!dgrad) {
-        p.RH = d->Ho; p.RW = d->Wo; p.GH = d->H; p.GW = d->W; p.GC = d->Cin; p.NC = d->Cout;
-        p.orgh = -d->pad; p.orgw = -d->pad; p.flip = 0; p.ldg = d->ldx; p.ldo = d->ldy;
-    } else {
-        p.RH = d->H; p.RW = d->W; p.GH = d->Ho; p.GW = d->Wo; p.GC = d->Cout; p.NC = d->Cin;
-        p.orgh = d->pad - d->dil * (d->KH - 1); p.orgw = d->pad - d->dil * (d->KW - 1);
-        p.flip = 1; p.ldg = d->ldy; p.ldo = d->ldx;
-    }
-    return p;
-}
-
-namespace iswm { int wgrad_pl_is_wide(const iswm_conv_desc* d); int wgrad_pl_kernel_kind(const iswm_conv_desc* d); }
-
-// may this geometry run the 256-column planes kernel (conv_mfma_pl2w.hip)?  bf16x6 only; strided data gradients keep the
-// parity-ordered rows of k_conv_pl2
-static bool pl2_wide_ok(const iswm_conv_desc* d, bool dgrad) {
-    if (math_planes() != 3 || (dgrad && d->stride != 1)) return false;
-    return !dgrad || d->KH * d->KW * d->Cout >= 512;          // the data gradient needs 8 stages per tile to pay
-}
-static int pl2_K(const iswm_conv_desc* d, bool dgrad) { return d->KH * d->KW * (dgrad ? d->Cout : d->Cin); }
-
-extern "C" int iswm_conv2d_kernel_name(const iswm_conv_desc* d, int kind, char* buf, int buflen) {
-    ISWM_REQUIRE(d && buf && buflen > 0 && kind >= 0 && kind <= 7, "kernel_name: bad argument");
-    if (kind == 7) {   // iswm_conv2d_wgrad_planes
-        const int kk = wgrad_pl_kernel_kind(d);
-        snprintf(buf, buflen, kk == 2 ? "k_wgrad_pls<%d>" : kk == 1 ? "k_wgrad_plw<%d>" : "k_wgrad_pl<%d>", math_planes());
-        return 0;
-    }
-    if (kind >= 5) {   // 5 / 6: iswm_conv2d_fwd_pl2 / iswm_conv2d_dgrad_pl2
-        const bool dg = kind == 6;
-        const int cols = dg ? d->Cin : d->Cout;
-        int rbw, wide;
-        conv_pl2_plan(dg ? (int64_t)d->N * d->H * d->W : (int64_t)d->N * d->Ho * d->Wo, cols, pl2_K(d, dg), pl2_wide_ok(d, dg), &rbw, &wide);
-        if (wide) snprintf(buf, buflen, "k_conv_pl2w<%d, %d, %s>", rbw, math_planes(), dg ? "true" : "false");
-        else if (cols <= 64) snprintf(buf, buflen, "k_conv_pl2<%d, 2, %d, %s>", rbw / 2, math_planes(), dg ? "true" : "false");
-        else snprintf(buf, buflen, "k_conv_pl2<%d, 1, %d, %s>", rbw, math_planes(), dg ? "true" : "false");
-        return 0;
-    }
-    if (kind >= 3) {   // 3 / 4: iswm_conv2d_fwd_packed / iswm_conv2d_dgrad_packed
-        const bool dg = kind == 4;
-        int pbm, pbn;
-        if (patch_plan(d, dg, &pbm, &pbn)) {
-            snprintf(buf, buflen, "k_conv_x6_patch<%s, %d>", dg ? "true" : "false", math_planes());
-            return 0;
-        }
-        conv_pick_tile_x6(dg ? (int64_t)d->N * d->H * d->W : (int64_t)d->N * d->Ho * d->Wo, dg ? d->Cin : d->Cout,
-                          d->KH * d->KW * (dg ? d->Cout : d->Cin), dg, d->KH * d->KW == 1, &pbm, &pbn);
-        snprintf(buf, buflen, "k_conv_x6<%d, 64, %s, true, %d>", pbm, dg ? "true" : "false", math_planes());
-        return 0;
-    }
-    int bm, bn;
-    if (kind == 0) {
-        const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-        if (d->Cin % 32 == 0) {
-            if (conv_math() == 1) conv_pick_tile_x6(M, d->Cout, d->KH * d->KW * d->Cin, false, d->KH * d->KW == 1, &bm, &bn);
-            else conv_pick_tile(M, d->Cout, &bm, &bn);
-            snprintf(buf, buflen, conv_math() == 1 ? "k_conv_x6<%d, %d, false, false, 3>" : "k_conv_fwd_u<%d, %d>", bm, bn);
-        } else if (conv_math() == 1 && stem_geometry(base_args(d))) {
-            snprintf(buf, buflen, "k_stem_fwd<%d>", stem_tile_rows() / 16);
-        } else {
-            snprintf(buf, buflen, "k_conv_fwd<%d>", use_narrow_tile((M + 127) / 128, d->Cout) ? 64 : 128);
-        }
-    } else if (kind == 1) {
-        const int64_t M = (int64_t)d->N * d->H * d->W;
-        if (d->Cout % 32 == 0) {
-            if (conv_math() == 1) conv_pick_tile_x6(M, d->Cin, d->KH * d->KW * d->Cout, true, d->KH * d->KW == 1, &bm, &bn);
-            else conv_pick_tile(M, d->Cin, &bm, &bn);
-            if (conv_math() == 1) snprintf(buf, buflen, "k_conv_x6<%d, %d, true, false, 3>", bm, bn);
-            else snprintf(buf, buflen, "k_conv_dgrad_u<%d, %d>", bm, bn);
-        } else {
-            snprintf(buf, buflen, "k_conv_dgrad<%d>", use_narrow_tile((M + 127) / 128, d->Cin) ? 64 : 128);
-        }
-    } else {
-        if (conv_math() == 1 && stem_geometry(base_args(d))) {
-            snprintf(buf, buflen, "k_stem_wgrad");
-            return 0;
-        }
-        WgradPlan p = plan_wgrad(d, conv_math() >= 1);
-        const bool same = d->stride == 1 && d->Ho == d->H && d->Wo == d->W;
-        const int mode = (same && d->KH == 1 && d->KW == 1 && d->pad == 0) ? 2 : (same ? 1 : 0);
-        snprintf(buf, buflen, "k_conv_wgrad<%d, %d, %d, %s, %d>", p.bm, p.bn, mode, conv_math() >= 1 ? "true" : "false",
-                 conv_math() == 2 ? 1 : 3);
-    }
-    return 0;
-}
-
-extern "C" int iswm_conv2d_stat_tile_rows(const iswm_conv_desc* d) {
-    if (!d) return 0;
-    if (conv_math() == 1 && stem_geometry(base_args(d))) return stem_tile_rows();
-    if (conv_math() == 1 && d->Cin % 32 == 0) {
-        int bm, bn;
-        conv_pick_tile_x6((int64_t)d->N * d->Ho * d->Wo, d->Cout, d->KH * d->KW * d->Cin, false, d->KH * d->KW == 1, &bm, &bn);
-        return bm;
-    }
-    return conv_fwd_tile_rows((int64_t)d->N * d->Ho * d->Wo, d->Cin, d->Cout);
-}
-
-extern "C" int iswm_conv2d_stat_tiles(const iswm_conv_desc* d) {
-    if (!d) return 0;
-    const int64_t M = (int64_t)d->N * d->Ho * d->Wo, R = iswm_conv2d_stat_tile_rows(d);
-    return (int)((M + R - 1) / R);
-}
-
-extern "C" int iswm_conv2d_fwd(const iswm_conv_desc* d, const float* x, const float* w, const float* bias,
-                               float* y, float* stat_partials, iswm_stream_t stream) {
-    if (int e = validate(d)) return e;
-    ISWM_REQUIRE(x && w && y, "conv_fwd: null pointer");
-    ISWM_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), "conv_fwd: pointers must be 16-byte aligned");
-    ConvArgs a = base_args(d);
-    a.x = x; a.w = w; a.bias = bias; a.y = y; a.stats = stat_partials;
-    a.M = d->N * d->Ho * d->Wo;
-    a.Ktot = d->KH * d->KW * d->Cin;
+// The three launchers the entry points (conv_api.hip) need; the tile width / plan is the caller's.
+void launch_conv_fwd_f32(ConvArgs a, hipStream_t s, int bn) {
     a.MT = (a.M + 127) / 128;
-    hipStream_t s = (hipStream_t)stream;
-    if (conv_math() == 1 && launch_stem_fwd(a, s)) return check_launch("stem_fwd");
-    if (conv_math() == 1 && d->Cin % 32 == 0) {
-        int bm, bn;
-        conv_pick_tile_x6(a.M, d->Cout, a.Ktot, false, d->KH * d->KW == 1, &bm, &bn);
-        if (launch_conv_fwd_x6(a, s, bm, bn)) return check_launch("conv_fwd_x6");
-    }
-    if (launch_conv_fwd_u(a, s)) return check_launch("conv_fwd_u");
-    if (use_narrow_tile(a.MT, d->Cout)) {
-        a.NT = (d->Cout + 63) / 64;
-        hipLaunchKernelGGL(k_conv_fwd<64>, dim3(a.MT * a.NT), dim3(256), 0, s, a);
-    } else {
-        a.NT = (d->Cout + 127) / 128;
-        hipLaunchKernelGGL(k_conv_fwd<128>, dim3(a.MT * a.NT), dim3(256), 0, s, a);
-    }
-    return check_launch("conv_fwd");
+    a.NT = (a.Cout + bn - 1) / bn;
+    if (bn == 64) hipLaunchKernelGGL(k_conv_fwd<64>, dim3(a.MT * a.NT), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_conv_fwd<128>, dim3(a.MT * a.NT), dim3(256), 0, s, a);
 }
 
-extern "C" int iswm_conv2d_dgrad(const iswm_conv_desc* d, const float* dy, const float* w, float* dx,
-                                 int accumulate, iswm_stream_t stream) {
-    if (int e = validate(d)) return e;
-    ISWM_REQUIRE(dy && w && dx, "conv_dgrad: null pointer");
-    ISWM_REQUIRE(aligned16(dy) && aligned16(w) && aligned16(dx), "conv_dgrad: pointers must be 16-byte aligned");
-    ConvArgs a = base_args(d);
-    // kernel naming: a.x = gathered operand (dy, pitch ldy), a.y = output (dx, pitch ldx)
-    a.x = dy; a.w = w; a.y = dx; a.accumulate = accumulate;
-    a.ldx = d->ldy; a.ldy = d->ldx;
-    a.M = d->N * d->H * d->W;
-    a.Ktot = d->KH * d->KW * d->Cout;
+void launch_conv_dgrad_f32(ConvArgs a, hipStream_t s, int bn) {
     a.MT = (a.M + 127) / 128;
-    hipStream_t s = (hipStream_t)stream;
-    if (launch_conv_dgrad_u(a, s)) return check_launch("conv_dgrad_u");
-    if (use_narrow_tile(a.MT, d->Cin)) {
-        a.NT = (d->Cin + 63) / 64;
-        hipLaunchKernelGGL(k_conv_dgrad<64>, dim3(a.MT * a.NT), dim3(256), 0, s, a);
-    } else {
-        a.NT = (d->Cin + 127) / 128;
-        hipLaunchKernelGGL(k_conv_dgrad<128>, dim3(a.MT * a.NT), dim3(256), 0, s, a);
-    }
-    return check_launch("conv_dgrad");
+    a.NT = (a.Cin + bn - 1) / bn;
+    if (bn == 64) hipLaunchKernelGGL(k_conv_dgrad<64>, dim3(a.MT * a.NT), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_conv_dgrad<128>, dim3(a.MT * a.NT), dim3(256), 0, s, a);
 }
 
-extern "C" int iswm_transpose_weights(const iswm_conv_desc* d, const float* w, float* wt, iswm_stream_t stream) {
-    if (int e = validate(d)) return e;
-    ISWM_REQUIRE(w && wt && w != wt, "transpose_weights: bad pointer");
-    launch_transpose_ohwi(w, wt, d->Cout, d->KH * d->KW, d->Cin, (hipStream_t)stream);
-    return check_launch("transpose_weights");
-}
-
-/* 1 when iswm_conv2d_dgrad_wt (bf16x6 data gradient on transposed weights) applies to this geometry under
- * the current conv math */
-extern "C" int iswm_conv2d_dgrad_wants_wt(const iswm_conv_desc* d) {
-    return (d && conv_math() == 1 && d->Cout % 32 == 0) ? 1 : 0;
-}
-
-extern "C" int iswm_conv2d_dgrad_wt(const iswm_conv_desc* d, const float* dy, const float* wt, float* dx,
-                                    int accumulate, iswm_stream_t stream) {
-    if (int e = validate(d)) return e;
-    ISWM_REQUIRE(dy && wt && dx, "conv_dgrad_wt: null pointer");
-    ISWM_REQUIRE(aligned16(dy) && aligned16(wt) && aligned16(dx), "conv_dgrad_wt: pointers must be 16-byte aligned");
-    ISWM_REQUIRE(d->Cout % 32 == 0, "conv_dgrad_wt: Cout must be a multiple of 32");
-    ConvArgs a = base_args(d);
-    a.x = dy; a.w = wt; a.y = dx; a.accumulate = accumulate;
-    a.ldx = d->ldy; a.ldy = d->ldx;
-    a.M = d->N * d->H * d->W;
-    a.Ktot = d->KH * d->KW * d->Cout;
-    int bm, bn;
-    conv_pick_tile_x6(a.M, d->Cin, a.Ktot, true, d->KH * d->KW == 1, &bm, &bn);
-    launch_conv_dgrad_x6(a, (hipStream_t)stream, bm, bn);
-    return check_launch("conv_dgrad_x6");
-}
-
-/* BN-partials layout of iswm_conv2d_fwd_packed: *tile_rows == 0 means the tiles are image patches with varying
- * row counts, stored as floats after the two planes (partials + 2*tiles*Cout). */
-extern "C" int iswm_conv2d_fwd_packed_stat_layout(const iswm_conv_desc* d, int* tiles, int* tile_rows) {
-    ISWM_REQUIRE(d && tiles && tile_rows, "fwd_packed_stat_layout: null pointer");
-    int PH, PW;
-    if (patch_plan(d, false, &PH, &PW)) {
-        *tiles = d->N * ((d->Ho + PH - 1) / PH) * ((d->Wo + PW - 1) / PW);
-        *tile_rows = 0;
-    } else {
-        int bm, bn;     // the tile launch_conv_x6_pk will use
-        const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-        conv_pick_tile_x6(M, d->Cout, d->KH * d->KW * d->Cin, false, d->KH * d->KW == 1, &bm, &bn);
-        *tile_rows = bm;
-        *tiles = (int)((M + bm - 1) / bm);
-    }
-    return 0;
-}
-
-/* ---- bf16x6 with pre-split, fragment-ordered weights ("packed"): kind 0 = forward, 1 = data gradient ---- */
-extern "C" size_t iswm_conv2d_packed_weight_bytes(const iswm_conv_desc* d, int kind) {
-    if (!d || conv_math() < 1 || (kind != 0 && kind != 1)) return 0;
-    const int gc = kind ? d->Cout : d->Cin;
-    if (gc % 32 != 0) return 0;
-    return packed_weight_bytes_x6(d->Cout, d->KH * d->KW, d->Cin, kind == 1, math_planes());
-}
-
-extern "C" int iswm_conv2d_pack_weights(const iswm_conv_desc* d, int kind, const float* w, void* packed,
-                                        iswm_stream_t stream) {
-    if (int e = validate(d)) return e;
-    ISWM_REQUIRE(kind == 0 || kind == 1, "pack_weights: kind must be 0 (forward) or 1 (data gradient)");
-    ISWM_REQUIRE(w && packed && aligned16(packed), "pack_weights: bad pointer");
-    ISWM_REQUIRE((kind ? d->Cout : d->Cin) % 32 == 0, "pack_weights: gathered channel count must be a multiple of 32");
-    launch_pack_weights_x6(w, packed, d->Cout, d->KH * d->KW, d->Cin, kind == 1, math_planes(), (hipStream_t)stream);
-    return check_launch("pack_weights");
-}
-
-/* ---- batched packing: every conv of a model in one launch ---- */
-extern "C" size_t iswm_packed_weight_bytes(int Cout, int taps, int Cin, int kind) {
-    if (Cout <= 0 || taps <= 0 || Cin <= 0 || kind < 0 || kind > 3 || conv_math() < 1) return 0;
-    if (kind >= 2) {        // planes kernels: gathered channel count a multiple of 64
-        if (((kind == 3) ? Cout : Cin) % 64 != 0) return 0;
-        return packed_weight_bytes_pl2(Cout, taps, Cin, kind == 3, math_planes());
-    }
-    if ((kind ? Cout : Cin) % 32 != 0) return 0;
-    return packed_weight_bytes_x6(Cout, taps, Cin, kind == 1, math_planes());
-}
-
-extern "C" int iswm_pack_job_blocks(int Cout, int taps, int Cin, int kind) {
-    if (iswm_packed_weight_bytes(Cout, taps, Cin, kind) == 0) return 0;
-    if (kind >= 2) return pack_job_blocks_pl2(Cout, taps, Cin, kind == 3);
-    return pack_job_blocks_x6(Cout, taps, Cin, kind == 1);
-}
-
-extern "C" int iswm_pack_weights_batch(const iswm_pack_job* jobs_dev, int njobs, int total_blocks,
-                                       iswm_stream_t stream) {
-    ISWM_REQUIRE(jobs_dev && njobs > 0 && total_blocks > 0, "pack_weights_batch: bad argument");
-    static_assert(sizeof(iswm_pack_job) == 40, "iswm_pack_job layout");
-    launch_pack_weights_batch(jobs_dev, njobs, total_blocks, math_planes(), (hipStream_t)stream);
-    return check_launch("pack_weights_batch");
-}
-
-extern "C" int iswm_conv2d_fwd_packed(const iswm_conv_desc* d, const float* x, const void* wpk, const float* bias,
-                                      float* y, float* stat_partials, iswm_stream_t stream) {
-    if (int e = validate(d)) return e;
-    ISWM_REQUIRE(x && wpk && y, "conv_fwd_packed: null pointer");
-    ISWM_REQUIRE(aligned16(x) && aligned16(wpk) && aligned16(y), "conv_fwd_packed: pointers must be 16-byte aligned");
-    ISWM_REQUIRE(d->Cin % 32 == 0, "conv_fwd_packed: Cin must be a multiple of 32");
-    ConvArgs a = base_args(d);
-    a.x = x; a.w = reinterpret_cast<const float*>(wpk); a.bias = bias; a.y = y; a.stats = stat_partials;
-    a.M = d->N * d->Ho * d->Wo;
-    a.Ktot = d->KH * d->KW * d->Cin;
-    int PH, PW;
-    if (patch_plan(d, false, &PH, &PW)) {
-        PatchArgs p = patch_args(d, false, PH, PW);
-        p.x = x; p.wpk = reinterpret_cast<const uint4*>(wpk); p.bias = bias; p.y = y; p.stats = stat_partials;
-        launch_conv_x6_patch(p, false, math_planes(), (hipStream_t)stream);
-        return check_launch("conv_fwd_patch");
-    }
-    int bm, bn;
-    conv_pick_tile_x6(a.M, d->Cout, a.Ktot, false, d->KH * d->KW == 1, &bm, &bn);
-    launch_conv_x6_pk(a, (hipStream_t)stream, false, bm, math_planes());
-    return check_launch("conv_fwd_packed");
-}
-
-extern "C" int iswm_conv2d_dgrad_packed(const iswm_conv_desc* d, const float* dy, const void* wpk, float* dx,
-                                        int accumulate, iswm_stream_t stream) {
-    if (int e = validate(d)) return e;
-    ISWM_REQUIRE(dy && wpk && dx, "conv_dgrad_packed: null pointer");
-    ISWM_REQUIRE(aligned16(dy) && aligned16(wpk) && aligned16(dx), "conv_dgrad_packed: pointers must be 16-byte aligned");
-    ISWM_REQUIRE(d->Cout % 32 == 0, "conv_dgrad_packed: Cout must be a multiple of 32");
-    ConvArgs a = base_args(d);
-    a.x = dy; a.w = reinterpret_cast<const float*>(wpk); a.y = dx; a.accumulate = accumulate;
-    a.ldx = d->ldy; a.ldy = d->ldx;
-    a.M = d->N * d->H * d->W;
-    a.Ktot = d->KH * d->KW * d->Cout;
-    int PH, PW;
-    if (patch_plan(d, true, &PH, &PW)) {
-        PatchArgs p = patch_args(d, true, PH, PW);
-        p.x = dy; p.wpk = reinterpret_cast<const uint4*>(wpk); p.y = dx; p.accumulate = accumulate;
-        launch_conv_x6_patch(p, true, math_planes(), (hipStream_t)stream);
-        return check_launch("conv_dgrad_patch");
-    }
-    int bm, bn;
-    conv_pick_tile_x6(a.M, d->Cin, a.Ktot, true, d->KH * d->KW == 1, &bm, &bn);
-    launch_conv_x6_pk(a, (hipStream_t)stream, true, bm, math_planes());
-    return check_launch("conv_dgrad_packed");
-}
-
-/* ---- activations pre-split into bf16 planes (see include/iswm_hip.h "planes") ---- */
-extern "C" int iswm_split_planes(const float* x, int64_t M, int C, int ldx, void* planes, int ldp, int64_t plane_stride,
-                                 iswm_stream_t stream) {
-    ISWM_REQUIRE(x && planes && M > 0 && C > 0, "split_planes: bad argument");
-    ISWM_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldx >= C && ldp % 4 == 0 && ldp >= C, "split_planes: C %d ldx %d ldp %d", C, ldx, ldp);
-    ISWM_REQUIRE(aligned16(x) && plane_stride % 4 == 0 && plane_stride >= M * ldp,
-                 "split_planes: planes must be 16-byte aligned and disjoint");
-    launch_split_planes(x, M, C, ldx, (unsigned short*)planes, ldp, plane_stride, math_planes(), (hipStream_t)stream);
-    return check_launch("split_planes");
-}
-
-extern "C" int iswm_join_planes(const void* planes, int ldp, int64_t plane_stride, int64_t M, int C, float* x, int ldx,
-                                iswm_stream_t stream) {
-    ISWM_REQUIRE(x && planes && M > 0 && C > 0, "join_planes: bad argument");
-    ISWM_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldx >= C && ldp % 4 == 0 && ldp >= C, "join_planes: C %d ldx %d ldp %d", C, ldx, ldp);
-    ISWM_REQUIRE(plane_stride == -1 || plane_stride >= M * ldp, "join_planes: bad plane stride");
-    launch_join_planes((const unsigned short*)planes, ldp, plane_stride, M, C, x, ldx, (hipStream_t)stream);
-    return check_launch("join_planes");
-}
-
-/* second-generation planes kernels (conv_mfma_pl2.hip): kind 0 forward, 1 data gradient */
-extern "C" size_t iswm_conv2d_pl2_weight_bytes(const iswm_conv_desc* d, int kind) {
-    if (!d || conv_math() < 1 || (kind != 0 && kind != 1)) return 0;
-    const int gc = kind ? d->Cout : d->Cin;
-    if (gc % 64 != 0) return 0;
-    return packed_weight_bytes_pl2(d->Cout, d->KH * d->KW, d->Cin, kind == 1, math_planes());
-}
-
-extern "C" int iswm_conv2d_pl2_pack_weights(const iswm_conv_desc* d, int kind, const float* w, void* packed,
-                                            iswm_stream_t stream) {
-    if (int e = validate(d)) return e;
-    ISWM_REQUIRE(kind == 0 || kind == 1, "pl2_pack_weights: kind must be 0 (forward) or 1 (data gradient)");
-    ISWM_REQUIRE(w && packed && aligned16(packed), "pl2_pack_weights: bad pointer");
-    ISWM_REQUIRE((kind ? d->Cout : d->Cin) % 64 == 0, "pl2_pack_weights: gathered channel count must be a multiple of 64");
-    launch_pack_weights_pl2(w, packed, d->Cout, d->KH * d->KW, d->Cin, kind == 1, math_planes(), (hipStream_t)stream);
-    return check_launch("pl2_pack_weights");
-}
-
-extern "C" int iswm_conv2d_pl2_tile_rows(const iswm_conv_desc* d, int kind) {
-    if (!d) return 0;
-    int rbw, wide;
-    if (kind) conv_pl2_plan((int64_t)d->N * d->H * d->W, d->Cin, pl2_K(d, true), pl2_wide_ok(d, true), &rbw, &wide);
-    else conv_pl2_plan((int64_t)d->N * d->Ho * d->Wo, d->Cout, pl2_K(d, false), pl2_wide_ok(d, false), &rbw, &wide);
-    return 16 * rbw;
-}
-
-extern "C" int iswm_conv2d_fwd_pl2(const iswm_conv_desc* d, const void* xp, int64_t plane_stride, const void* wpk,
-                                   const float* bias, float* y, float* stat_partials, iswm_stream_t stream) {
-    if (int e = validate(d)) return e;
-    ISWM_REQUIRE(xp && wpk && y, "conv_fwd_pl2: null pointer");
-    ISWM_REQUIRE(aligned16(xp) && aligned16(wpk) && aligned16(y), "conv_fwd_pl2: pointers must be 16-byte aligned");
-    ISWM_REQUIRE(d->Cin % 64 == 0 && d->ldx % 8 == 0 && (plane_stride % 8 == 0 || (plane_stride == -1 && math_planes() == 1)),
-                 "conv_fwd_pl2: Cin %% 64, ldx %% 8, plane stride %% 8 (or -1: one rounded plane under conv math bf16)");
-    ConvArgs a = base_args(d);
-    a.x = reinterpret_cast<const float*>(xp); a.w = reinterpret_cast<const float*>(wpk); a.bias = bias; a.y = y;
-    a.stats = stat_partials;
-    a.xps = plane_stride * 2;
-    a.M = d->N * d->Ho * d->Wo;
-    a.Ktot = d->KH * d->KW * d->Cin;
-    int rbw, wide;
-    conv_pl2_plan(a.M, d->Cout, pl2_K(d, false), pl2_wide_ok(d, false), &rbw, &wide);
-    ISWM_REQUIRE(wide ? launch_conv_pl2w(a, (hipStream_t)stream, false, math_planes(), rbw)
-                      : launch_conv_pl2(a, (hipStream_t)stream, false, math_planes(), rbw),
-                 "conv_fwd_pl2: no kernel for this configuration");
-    return check_launch("conv_fwd_pl2");
-}
-
-static int dgrad_pl2_impl(const iswm_conv_desc* d, const void* dyp, int64_t plane_stride, const void* wpk, float* dx,
-                          int accumulate, const BnFuse* f, iswm_stream_t stream) {
-    if (int e = validate(d)) return e;
-    ISWM_REQUIRE(dyp && wpk && dx, "conv_dgrad_pl2: null pointer");
-    ISWM_REQUIRE(aligned16(dyp) && aligned16(wpk) && aligned16(dx), "conv_dgrad_pl2: pointers must be 16-byte aligned");
-    ISWM_REQUIRE(d->Cout % 64 == 0 && d->ldy % 8 == 0 && (plane_stride % 8 == 0 || (plane_stride == -1 && math_planes() == 1)),
-                 "conv_dgrad_pl2: Cout %% 64, ldy %% 8, plane stride %% 8 (or -1: one rounded plane under conv math bf16)");
-    ConvArgs a = base_args(d);
-    a.x = reinterpret_cast<const float*>(dyp); a.w = reinterpret_cast<const float*>(wpk); a.y = dx; a.accumulate = accumulate;
-    a.ldx = d->ldy; a.ldy = d->ldx;
-    a.xps = plane_stride * 2;
-    a.M = d->N * d->H * d->W;
-    a.Ktot = d->KH * d->KW * d->Cout;
-    if (f) a.bnf = *f;
-    int rbw, wide;
-    conv_pl2_plan(a.M, d->Cin, pl2_K(d, true), pl2_wide_ok(d, true), &rbw, &wide);
-    ISWM_REQUIRE(wide ? launch_conv_pl2w(a, (hipStream_t)stream, true, math_planes(), rbw)
-                      : launch_conv_pl2(a, (hipStream_t)stream, true, math_planes(), rbw),
-                 "conv_dgrad_pl2: no kernel for this configuration");
-    return check_launch("conv_dgrad_pl2");
-}
-
-extern "C" int iswm_conv2d_dgrad_pl2(const iswm_conv_desc* d, const void* dyp, int64_t plane_stride, const void* wpk,
-                                     float* dx, int accumulate, iswm_stream_t stream) {
-    return dgrad_pl2_impl(d, dyp, plane_stride, wpk, dx, accumulate, nullptr, stream);
-}
-
-/* tile rows of the planes data gradient = first dimension of the statistics it can emit for the consumer BatchNorm backward */
-extern "C" int iswm_conv2d_dgrad_pl2_stat_tiles(const iswm_conv_desc* d) {
-    if (!d || d->Cin <= 0) return 0;
-    const int64_t M = (int64_t)d->N * d->H * d->W;
-    int rbw, wide;
-    conv_pl2_plan(M, d->Cin, pl2_K(d, true), pl2_wide_ok(d, true), &rbw, &wide);
-    const int wm = d->Cin <= 64 ? 2 : 1;                 // narrow tiles: (rbw / 2) blocks x 2 wave rows
-    const int64_t mt = (M + rbw * 16 - 1) / (rbw * 16);
-    return (int)(mt * wm);
-}
-
-/* iswm_conv2d_dgrad_pl2 that also emits, per tile row and input channel, the two sums the BatchNorm backward of the stage
- * that PRODUCED the conv's input needs over the finished dx (after accumulation):  partials[0][t][c] = sum dz,
- * partials[1][t][c] = sum dz * xhat,  dz = dx * [ReLU pattern], xhat = (y - mean) * invstd.  relu: 0 none, 2 pattern
- * recomputed as (y - mean) * mask_scale + mask_shift > 0 (as iswm_bn_backward does), 3 the producer is a RESIDUAL stage:
- * pattern = (hi plane of its saved output, mask_hi, pitch ld_mask bf16 elements) > 0, and dx is STORED MASKED (dz): that
- * tensor is both the dout of the producer's BatchNorm backward (call it with relu = 0) and the gradient of its identity
- * branch, so neither the reduction pass nor a separate `dres` tensor exists for that stage.  y: the producer's raw conv output
- * [N*H*W][ldy], Cin channels.  partials: 2 * tiles * Cin doubles, tiles = iswm_conv2d_dgrad_pl2_stat_tiles(d).  Feed them to
- * iswm_bn_backward_pl with partial_tiles = tiles: it then skips its own reduction pass over dout and y. */
-extern "C" int iswm_conv2d_dgrad_pl2_bn(const iswm_conv_desc* d, const void* dyp, int64_t plane_stride, const void* wpk,
-                                        float* dx, int accumulate, const float* y, int ldy, const float* mean,
-                                        const float* invstd, const float* mask_scale, const float* mask_shift, int relu,
-                                        const void* mask_hi, int ld_mask, double* partials, int tiles,
-                                        iswm_stream_t stream) {
-    ISWM_REQUIRE(d && y && mean && invstd && partials, "conv_dgrad_pl2_bn: null pointer");
-    ISWM_REQUIRE(relu == 0 || (relu == 2 && mask_scale && mask_shift) ||
-                     (relu == 3 && mask_hi && ld_mask % 4 == 0 && ld_mask >= d->Cin && (((uintptr_t)mask_hi) & 7) == 0),
-                 "conv_dgrad_pl2_bn: relu must be 0, 2 (with mask_scale / mask_shift) or 3 (with the producer's saved output planes)");
-    ISWM_REQUIRE(d->Cin % 4 == 0 && ldy % 4 == 0 && ldy >= d->Cin && aligned16(y) && aligned16(mean) && aligned16(invstd),
-                 "conv_dgrad_pl2_bn: Cin %% 4, ldy %% 4, 16-byte aligned pointers");
-    ISWM_REQUIRE(tiles == iswm_conv2d_dgrad_pl2_stat_tiles(d), "conv_dgrad_pl2_bn: tiles %d != %d", tiles,
-                 iswm_conv2d_dgrad_pl2_stat_tiles(d));
-    BnFuse f{};
-    f.y = y; f.ldy = ldy; f.mean = mean; f.invstd = invstd; f.mscale = mask_scale; f.mshift = mask_shift; f.relu = relu;
-    f.part = partials;
-    f.mask = reinterpret_cast<const unsigned short*>(mask_hi); f.ldm = ld_mask;
-    return dgrad_pl2_impl(d, dyp, plane_stride, wpk, dx, accumulate, &f, stream);
-}
-
-extern "C" size_t iswm_conv2d_wgrad_workspace(const iswm_conv_desc* d) {
-    if (!d) return 0;
-    if (conv_math() == 1 && stem_geometry(base_args(d))) return stem_wgrad_workspace(base_args(d));
-    WgradPlan p = plan_wgrad(d, conv_math() >= 1);
-    if (p.nsplit <= 1) return 0;
-    return (size_t)p.nsplit * d->Cout * d->KH * d->KW * d->Cin * sizeof(float);
-}
-
-extern "C" int iswm_conv2d_wgrad(const iswm_conv_desc* d, const float* x, const float* dy, float* dw,
-                                 float* workspace, size_t workspace_bytes, iswm_stream_t stream) {
-    if (int e = validate(d)) return e;
-    ISWM_REQUIRE(x && dy && dw, "conv_wgrad: null pointer");
-    ISWM_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(dw), "conv_wgrad: pointers must be 16-byte aligned");
-    WgradPlan p = plan_wgrad(d, conv_math() >= 1);
-    const size_t need = iswm_conv2d_wgrad_workspace(d);
-    ISWM_REQUIRE(workspace_bytes >= need && (need == 0 || (workspace && aligned16(workspace))),
-                 "conv_wgrad: workspace too small (%zu < %zu)", workspace_bytes, need);
-    ConvArgs a = base_args(d);
-    a.x = x; a.y = const_cast<float*>(dy);
-    a.M = d->N * d->Ho * d->Wo;
-    a.Ktot = d->KH * d->KW * d->Cin;
-    if (conv_math() == 1 && launch_stem_wgrad(a, dw, workspace, (hipStream_t)stream)) return check_launch("stem_wgrad");
+// a.stats: the slabs (p.nsplit > 1) or dw itself
+void launch_conv_wgrad(ConvArgs a, hipStream_t s, const WgPlan& p) {
     a.MT = p.MT; a.NT = p.NT; a.nsplit = p.nsplit; a.psplit = p.psplit;
-    a.stats = (p.nsplit > 1) ? workspace : dw;
-    hipStream_t s = (hipStream_t)stream;
     dim3 grid(p.MT * p.NT, p.nsplit);
-    const bool same = d->stride == 1 && d->Ho == d->H && d->Wo == d->W;
-    const int mode = (same && d->KH == 1 && d->KW == 1 && d->pad == 0) ? 2 : (same ? 1 : 0);
-    const bool x6 = conv_math() >= 1, one = conv_math() == 2;
+    const int mode = p.mode;
+    const bool x6 = p.x6, one = p.planes == 1;
 #define WLAUNCH(BM_, BN_, X_, NP_)                                                                          \
     do {                                                                                                    \
         if (mode == 2) hipLaunchKernelGGL((k_conv_wgrad<BM_, BN_, 2, X_, NP_>), grid, dim3(256), 0, s, a);      \
@@ -1289,12 +730,6 @@ extern "C" int iswm_conv2d_wgrad(const iswm_conv_desc* d, const float* x, const 
     else if (x6) WLAUNCH(64, 64, true, 3);
     else WLAUNCH(64, 64, false, 3);
 #undef WLAUNCH
-    if (int e = check_launch("conv_wgrad")) return e;
-    if (p.nsplit > 1) {
-        int64_t n4 = (int64_t)d->Cout * a.Ktot / 4;
-        hipLaunchKernelGGL(k_reduce_slabs, dim3(stream_grid(n4, 256)), dim3(256), 0, s, workspace, dw, n4,
-                           p.nsplit);
-        return check_launch("conv_wgrad_reduce");
-    }
-    return 0;
 }
+
+}  // namespace iswm

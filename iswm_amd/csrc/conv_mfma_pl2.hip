@@ -501,12 +501,12 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
 
 // Tile height for a GEMM of M rows x cols columns on 256 CUs (one 128-column workgroup per CU at a time):
 // rbw 16-row blocks, chosen to minimise  rounds x (rows per tile + fixed per-tile cost in row equivalents).
-int conv_pl2_pick_rbw(int64_t M, int cols) {
-    const int64_t NT = cols <= 64 ? 1 : (cols + 127) / 128;
+static int conv_pl2_pick_rbw(int64_t M, int cols, int wm) {
+    const int64_t NT = wm == 2 ? 1 : (cols + 127) / 128;
     int best = PL2_RBWMAX;
     double bestc = 1e300;
     for (int rbw = 8; rbw <= PL2_RBWMAX; ++rbw) {
-        if (cols <= 64 && rbw == 9) continue;        // 64-column tiles: 2 wave rows x 4 or 5 blocks
+        if (wm == 2 && rbw == 9) continue;           // 64-column tiles: 2 wave rows x 4 or 5 blocks
         const int64_t MT = (M + rbw * 16 - 1) / (rbw * 16);
         const int64_t rounds = (MT * NT + 255) / 256;
         const double c = (double)rounds * (rbw * 16 + 24.0);
@@ -518,10 +518,11 @@ int conv_pl2_pick_rbw(int64_t M, int cols) {
     return best;
 }
 
-// Tile plan: height (rbw 16-row blocks) and width.  256-column tiles (k_conv_pl2w: two column blocks per wave, ~15 % less
+// Tile plan: height (rbw 16-row blocks), width and wave rows.  256-column tiles (k_conv_pl2w: two column blocks per wave, ~15 % less
 // time per MFMA) are taken where the tile count still covers the chip:  cost = rounds x (rows + fixed) x (2 x 0.85 if wide).
-void conv_pl2_plan(int64_t M, int cols, int K, bool wide_ok, int* rbw_out, int* wide_out) {
-    *rbw_out = conv_pl2_pick_rbw(M, cols);
+void conv_pl2_plan(int64_t M, int cols, int K, bool wide_ok, int* rbw_out, int* wide_out, int* wm_out) {
+    *wm_out = cols <= 64 ? 2 : 1;                // 64-column tiles: (rbw / 2) blocks x 2 wave rows
+    *rbw_out = conv_pl2_pick_rbw(M, cols, *wm_out);
     *wide_out = 0;
     // short K: a tile is a few stages and then an epilogue of twice the size -- measured slower below 4 stages (forward)
     // / 8 stages (data gradient, whose accumulating epilogue also reads) [profiles/r03_pl2w_ab.txt]
@@ -540,8 +541,8 @@ void conv_pl2_plan(int64_t M, int cols, int K, bool wide_ok, int* rbw_out, int* 
     }
 }
 
-// rbw = 16-row blocks per tile (8..10 instantiated for 128-column tiles; 2 x 4/5 for 64-column tiles)
-bool launch_conv_pl2(ConvArgs a, hipStream_t s, bool dgrad, int planes, int rbw) {
+// rbw = 16-row blocks per tile (8..10 instantiated for 128-column tiles; wm == 2: 2 x 4/5 for 64-column tiles)
+bool launch_conv_pl2(ConvArgs a, hipStream_t s, bool dgrad, int planes, int rbw, int wm) {
     a.psplit = 0;           // strided data gradient: parity-sorted rows
     {   // quarters of the parity-sorted rows, heaviest first (class k = 2 * (row parity) + column parity)
         int wgt[4], ord[4] = {0, 1, 2, 3};
@@ -557,7 +558,7 @@ bool launch_conv_pl2(ConvArgs a, hipStream_t s, bool dgrad, int planes, int rbw)
         a.porder = ord[0] | (ord[1] << 2) | (ord[2] << 4) | (ord[3] << 6);
     }
     const int nc = dgrad ? a.Cin : a.Cout;
-    const bool narrow = nc <= 64;
+    const bool narrow = wm == 2;
     a.MT = (a.M + rbw * 16 - 1) / (rbw * 16);
     a.NT = narrow ? 1 : (nc + 127) / 128;
     const int tiles = a.MT * a.NT, ncu = device_cus();

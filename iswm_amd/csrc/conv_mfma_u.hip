@@ -396,62 +396,49 @@ __global__ __launch_bounds__(256, (TileCfg<BM, BN>::OCC)) void k_conv_dgrad_u(co
 
 // Tile choice: a CU works through ceil(tiles / 256) tiles (co-resident workgroups share its SIMDs), so
 // the estimated time is rounds x tile area / intrinsic efficiency of the shape.
-struct TilePick {
-    int bm, bn;
-};
-
-static TilePick pick_tile(int64_t M, int cols) {
+void conv_pick_tile(int64_t M, int cols, int* bm, int* bn) {
     struct Cand {
         int bm, bn;
         double eff;
     };
     const Cand cands[3] = {{128, 128, 1.00}, {128, 64, 0.92}, {64, 64, 0.80}};
     double best = 1e300;
-    TilePick p{128, 128};
+    *bm = 128;
+    *bn = 128;
     for (const Cand& c : cands) {
         if (c.bn == 128 && (cols <= 64 || (cols % 128 != 0 && cols % 128 <= 64))) continue;
         int64_t tiles = ((M + c.bm - 1) / c.bm) * ((cols + c.bn - 1) / c.bn);
         double cost = (double)((tiles + 255) / 256) * c.bm * c.bn / c.eff;
         if (cost < best) {
             best = cost;
-            p = {c.bm, c.bn};
+            *bm = c.bm;
+            *bn = c.bn;
         }
     }
-    return p;
 }
 
-void conv_pick_tile(int64_t M, int cols, int* bm, int* bn) {
-    TilePick p = pick_tile(M, cols);
-    *bm = p.bm;
-    *bn = p.bn;
-}
-
-int conv_fwd_tile_rows(int64_t M, int Cin, int Cout) {
-    if (Cin % 32 != 0) return 128;          // general-K kernel: 128-row tiles
-    return pick_tile(M, Cout).bm;
-}
-
-bool launch_conv_fwd_u(ConvArgs a, hipStream_t s) {
+// bm x bn from conv_pick_tile; false when there is no such instantiation
+bool launch_conv_fwd_u(ConvArgs a, hipStream_t s, int bm, int bn) {
     if (a.Cin % 32 != 0) return false;
-    TilePick p = pick_tile(a.M, a.Cout);
-    a.MT = (a.M + p.bm - 1) / p.bm;
-    a.NT = (a.Cout + p.bn - 1) / p.bn;
+    a.MT = (a.M + bm - 1) / bm;
+    a.NT = (a.Cout + bn - 1) / bn;
     dim3 grid(a.MT * a.NT), blk(256);
-    if (p.bm == 128 && p.bn == 128) hipLaunchKernelGGL((k_conv_fwd_u<128, 128>), grid, blk, 0, s, a);
-    else if (p.bm == 128) hipLaunchKernelGGL((k_conv_fwd_u<128, 64>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_conv_fwd_u<64, 64>), grid, blk, 0, s, a);
+    if (bm == 128 && bn == 128) hipLaunchKernelGGL((k_conv_fwd_u<128, 128>), grid, blk, 0, s, a);
+    else if (bm == 128 && bn == 64) hipLaunchKernelGGL((k_conv_fwd_u<128, 64>), grid, blk, 0, s, a);
+    else if (bm == 64 && bn == 64) hipLaunchKernelGGL((k_conv_fwd_u<64, 64>), grid, blk, 0, s, a);
+    else return false;
     return true;
 }
 
-bool launch_conv_dgrad_u(ConvArgs a, hipStream_t s) {
+bool launch_conv_dgrad_u(ConvArgs a, hipStream_t s, int bm, int bn) {
     if (a.Cout % 32 != 0) return false;
-    TilePick p = pick_tile(a.M, a.Cin);
-    a.MT = (a.M + p.bm - 1) / p.bm;
-    a.NT = (a.Cin + p.bn - 1) / p.bn;
+    a.MT = (a.M + bm - 1) / bm;
+    a.NT = (a.Cin + bn - 1) / bn;
     dim3 grid(a.MT * a.NT), blk(256);
-    if (p.bm == 128 && p.bn == 128) hipLaunchKernelGGL((k_conv_dgrad_u<128, 128>), grid, blk, 0, s, a);
-    else if (p.bm == 128) hipLaunchKernelGGL((k_conv_dgrad_u<128, 64>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_conv_dgrad_u<64, 64>), grid, blk, 0, s, a);
+    if (bm == 128 && bn == 128) hipLaunchKernelGGL((k_conv_dgrad_u<128, 128>), grid, blk, 0, s, a);
+    else if (bm == 128 && bn == 64) hipLaunchKernelGGL((k_conv_dgrad_u<128, 64>), grid, blk, 0, s, a);
+    else if (bm == 64 && bn == 64) hipLaunchKernelGGL((k_conv_dgrad_u<64, 64>), grid, blk, 0, s, a);
+    else return false;
     return true;
 }
 

@@ -357,13 +357,15 @@ bool launch_conv_fwd_x6(ConvArgs a, hipStream_t s, int bm, int bn) {
     a.NT = (a.Cout + bn - 1) / bn;
     dim3 grid(a.MT * a.NT), blk(256);
     if (bm == 128 && bn == 128) hipLaunchKernelGGL((k_conv_x6<128, 128, false, false>), grid, blk, 0, s, a);
-    else if (bm == 128) hipLaunchKernelGGL((k_conv_x6<128, 64, false, false>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_conv_x6<64, 64, false, false>), grid, blk, 0, s, a);
+    else if (bm == 128 && bn == 64) hipLaunchKernelGGL((k_conv_x6<128, 64, false, false>), grid, blk, 0, s, a);
+    else if (bm == 64 && bn == 64) hipLaunchKernelGGL((k_conv_x6<64, 64, false, false>), grid, blk, 0, s, a);
+    else return false;
     return true;
 }
 
-// packed-weight ("B direct") launchers: a.w = k_pack_weights_x6 output.  Tiles: 128x64 or 64x64.
+// packed-weight ("B direct") launchers: a.w = k_pack_weights_x6 output.  Tiles: 128x64 or 64x64; false for any other.
 bool launch_conv_x6_pk(ConvArgs a, hipStream_t s, bool dgrad, int bm, int planes) {
+    if ((bm != 128 && bm != 64) || (planes != 1 && planes != 3)) return false;
     a.nsplit = 0;           // strided data gradient: parity-sorted rows
     const int nc = dgrad ? a.Cin : a.Cout;
     a.MT = (a.M + bm - 1) / bm;
@@ -507,8 +509,9 @@ bool launch_conv_dgrad_x6(ConvArgs a, hipStream_t s, int bm, int bn) {
     a.NT = (a.Cin + bn - 1) / bn;
     dim3 grid(a.MT * a.NT), blk(256);
     if (bm == 128 && bn == 128) hipLaunchKernelGGL((k_conv_x6<128, 128, true, false>), grid, blk, 0, s, a);
-    else if (bm == 128) hipLaunchKernelGGL((k_conv_x6<128, 64, true, false>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_conv_x6<64, 64, true, false>), grid, blk, 0, s, a);
+    else if (bm == 128 && bn == 64) hipLaunchKernelGGL((k_conv_x6<128, 64, true, false>), grid, blk, 0, s, a);
+    else if (bm == 64 && bn == 64) hipLaunchKernelGGL((k_conv_x6<64, 64, true, false>), grid, blk, 0, s, a);
+    else return false;
     return true;
 }
 

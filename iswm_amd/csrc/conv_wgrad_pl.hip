@@ -12,6 +12,7 @@
 // matrix pipe busy while the other issues its DMA.  One workgroup per CU; the pixel axis is split across workgroups
 // (slabs summed in a fixed order by k_reduce_slabs: bit-reproducible).
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <type_traits>
@@ -845,13 +846,9 @@ static int wgrad_pl_wide(int Ktot, int taps, int64_t P) {
     return pad256 * 10 <= pad128 * 14;
 }
 
-int wgrad_pl_is_wide(const iswm_conv_desc* d) {
-    return wgrad_pl_wide(d->KH * d->KW * d->Cin, d->KH * d->KW, (int64_t)d->N * d->Ho * d->Wo);
-}
-
-// pixels per split (multiple of 32) and split count: minimise  rounds x (steps per workgroup + fixed cost) + slab traffic
-void plan_wgrad_pl(int Cout, int Ktot, int taps, int64_t P, int* nsplit, int* psplit) {
-    const int wide = wgrad_pl_wide(Ktot, taps, P);
+// pixels per split (multiple of 32) and split count over P pixels per tile: minimise  rounds x (steps per workgroup + fixed
+// cost) + slab traffic
+static void wgrad_pl_split(int Cout, int Ktot, int wide, int64_t P, int* nsplit, int* psplit) {
     const int tn = wide ? 256 : 128;
     const int64_t tiles = (int64_t)((Cout + 127) / 128) * ((Ktot + tn - 1) / tn);
     const double step_us = wide ? 1.45 : 0.75;                    // one 128 x tn x 32 step of a CU
@@ -874,16 +871,68 @@ void plan_wgrad_pl(int Cout, int Ktot, int taps, int64_t P, int* nsplit, int* ps
     }
 }
 
-void launch_wgrad_pl(const WgArgs& a, int planes, int wide, hipStream_t s) {
+// Tap-rectangle mode of k_wgrad_pls (WgArgs::rect): bf16x6, deep padding, stride 1, whole taps per 256-column tile (Cin % 256 == 0
+// with more than one tap is always a wide geometry).  Returns the mean number of pixels a tile walks (what the split planner
+// balances), the taps by descending rectangle size and whether the rectangles are of similar size.
+static bool wgrad_rect_mode(const iswm_conv_desc* d, int math, int64_t* p_eff, unsigned char* order, bool* similar) {
+    const int taps = d->KH * d->KW;
+    if (d->pad < 4 || d->stride != 1 || d->Cin % 256 != 0 || taps <= 1 || taps > 32 || math != 1) return false;
+    int64_t area[32], sum = 0;
+    for (int t = 0; t < taps; ++t) {
+        const int dh = (t / d->KW) * d->dil - d->pad, dw = (t % d->KW) * d->dil - d->pad;
+        const int h = std::max(0, std::min(d->Ho, d->H - dh) - std::max(0, -dh));
+        const int w = std::max(0, std::min(d->Wo, d->W - dw) - std::max(0, -dw));
+        area[t] = (int64_t)d->N * h * w;
+        sum += area[t];
+    }
+    for (int t = 0; t < taps; ++t) order[t] = (unsigned char)t;
+    for (int i = 0; i < taps; ++i)
+        for (int j = i + 1; j < taps; ++j)
+            if (area[order[j]] > area[order[i]]) std::swap(order[i], order[j]);
+    *p_eff = std::max<int64_t>(32, sum / taps);
+    *similar = 100 * area[order[taps - 1]] >= 35 * area[order[0]];      // the smallest >= 35 % of the largest
+    return true;
+}
+
+// The one place where a planes weight gradient is decided: tile width, kernel, culling, splits and workspace.
+WgPlan plan_wgrad_pl(const iswm_conv_desc* d, int math) {
+    WgPlan p{};
+    const int taps = d->KH * d->KW, Ktot = taps * d->Cin;
+    const int64_t P = (int64_t)d->N * d->Ho * d->Wo;
+    p.planes = math_planes(math);
+    p.wide = wgrad_pl_wide(Ktot, taps, P);
+    p.bm = 128;
+    p.bn = p.wide ? 256 : 128;
+    p.MT = (d->Cout + p.bm - 1) / p.bm;
+    p.NT = (Ktot + p.bn - 1) / p.bn;
+    int64_t p_plan = P;                               // the split planner balances what the tiles really walk
+    bool similar = false;
+    p.rect = (p.wide && wgrad_rect_mode(d, math, &p_plan, p.tap_order, &similar)) ? 1 : 0;
+    // one column block per XCD (k_wgrad_pls) where the taps walk their rectangles at a similar pace (rates 6 and 12 on the
+    // 33 x 33 map: fabric fetch -43 % / -27 %, kernel -4.6 % / -2.2 %; at rate 18 the corner taps are a fifth of the centre
+    // tap, the XCD's taps drift apart by images and the order only unbalances the rounds: +3 %) -- profiles/r03_rect_xcd.txt
+    if (p.rect && (d->Cin >> 8) == 8 && similar) p.rect = 2;
+    wgrad_pl_split(d->Cout, Ktot, p.wide, p_plan, &p.nsplit, &p.psplit);
+    p.vote = (d->pad >= 4 && !p.rect) ? 1 : 0;        // rect: nothing to vote on, the tile walks in-bounds pixels only
+    p.always = (d->KH == 1 && d->KW == 1 && d->pad == 0 && d->stride == 1) ? 1 : 0;
+    // k_wgrad_plw: all waves load and multiply, culling vote;  k_wgrad_pls: loader / multiplier waves
+    p.kernel = !p.wide ? 0 : p.vote ? 1 : 2;
+    if (p.nsplit > 1)                                 // wide: whole 128 x 256 tiles in accumulator order
+        p.workspace = p.wide ? (size_t)p.nsplit * p.MT * p.NT * 32768 * sizeof(float)
+                             : (size_t)p.nsplit * d->Cout * Ktot * sizeof(float);
+    return p;
+}
+
+static void launch_wgrad_pl(const WgArgs& a, const WgPlan& p, hipStream_t s) {
     dim3 grid(a.MT * a.NT * a.nsplit), blk(512);
-    if (wide && !a.vote) {
-        if (planes == 1) hipLaunchKernelGGL(k_wgrad_pls<1>, grid, blk, 0, s, a);
+    if (p.kernel == 2) {
+        if (p.planes == 1) hipLaunchKernelGGL(k_wgrad_pls<1>, grid, blk, 0, s, a);
         else hipLaunchKernelGGL(k_wgrad_pls<3>, grid, blk, 0, s, a);
-    } else if (wide) {
-        if (planes == 1) hipLaunchKernelGGL(k_wgrad_plw<1>, grid, blk, 0, s, a);
+    } else if (p.kernel == 1) {
+        if (p.planes == 1) hipLaunchKernelGGL(k_wgrad_plw<1>, grid, blk, 0, s, a);
         else hipLaunchKernelGGL(k_wgrad_plw<3>, grid, blk, 0, s, a);
     } else {
-        if (planes == 1) hipLaunchKernelGGL(k_wgrad_pl<1>, grid, blk, 0, s, a);
+        if (p.planes == 1) hipLaunchKernelGGL(k_wgrad_pl<1>, grid, blk, 0, s, a);
         else hipLaunchKernelGGL(k_wgrad_pl<3>, grid, blk, 0, s, a);
     }
 }
@@ -891,10 +940,6 @@ void launch_wgrad_pl(const WgArgs& a, int planes, int wide, hipStream_t s) {
 }  // namespace iswm
 
 using namespace iswm;
-
-namespace iswm {
-void launch_reduce_slabs(const float* slabs, float* dst, int64_t n4, int nsplit, hipStream_t s);
-}
 
 // every precondition of the planes weight gradient in ONE place: iswm_conv2d_wgrad_planes_ok() answers with it (callers
 // fall back to the fp32-input weight gradient) and the entry point refuses with its message.  nullptr = acceptable.
@@ -923,67 +968,18 @@ extern "C" int iswm_conv2d_wgrad_planes_ok(const iswm_conv_desc* d) {
     return (wg_refusal(d) == nullptr && iswm_get_conv_math() >= 1) ? 1 : 0;
 }
 
-// Tap-rectangle mode of k_wgrad_pls (WgArgs::rect): deep padding, stride 1, whole taps per 256-column tile.  Returns the mean
-// number of pixels a tile walks (what the split planner balances) and fills the taps by descending rectangle size.
-static bool wgrad_rect_mode(const iswm_conv_desc* d, int64_t* p_eff, unsigned char* order, bool* similar = nullptr) {
-    const int taps = d->KH * d->KW;
-    if (d->pad < 4 || d->stride != 1 || d->Cin % 256 != 0 || taps <= 1 || taps > 32 || iswm_get_conv_math() != 1) return false;
-    int64_t area[32], sum = 0;
-    for (int t = 0; t < taps; ++t) {
-        const int dh = (t / d->KW) * d->dil - d->pad, dw = (t % d->KW) * d->dil - d->pad;
-        const int h = std::max(0, std::min(d->Ho, d->H - dh) - std::max(0, -dh));
-        const int w = std::max(0, std::min(d->Wo, d->W - dw) - std::max(0, -dw));
-        area[t] = (int64_t)d->N * h * w;
-        sum += area[t];
-    }
-    if (order) {
-        for (int t = 0; t < taps; ++t) order[t] = (unsigned char)t;
-        for (int i = 0; i < taps; ++i)
-            for (int j = i + 1; j < taps; ++j)
-                if (area[order[j]] > area[order[i]]) std::swap(order[i], order[j]);
-    }
-    if (p_eff) *p_eff = std::max<int64_t>(32, sum / taps);
-    if (similar) {              // are the taps' rectangles of similar size (smallest >= 35 % of the largest)?
-        int64_t lo = area[0], hi = area[0];
-        for (int t = 1; t < taps; ++t) {
-            lo = std::min(lo, area[t]);
-            hi = std::max(hi, area[t]);
-        }
-        *similar = 100 * lo >= 35 * hi;
-    }
-    return true;
-}
-
-// which kernel iswm_conv2d_wgrad_planes launches for this geometry (iswm_conv2d_kernel_name): 0 k_wgrad_pl (128 x 128 tiles),
-// 1 k_wgrad_plw (128 x 256, all waves load and multiply, culling vote), 2 k_wgrad_pls (loader / multiplier waves)
-namespace iswm {
-int wgrad_pl_kernel_kind(const iswm_conv_desc* d) {
-    if (!wgrad_pl_is_wide(d)) return 0;
-    const bool rect = wgrad_rect_mode(d, nullptr, nullptr);
-    const bool vote = d->pad >= 4 && !rect;
-    return vote ? 1 : 2;
-}
-}  // namespace iswm
-
 extern "C" size_t iswm_conv2d_wgrad_planes_workspace(const iswm_conv_desc* d) {
-    if (!d) return 0;
-    int ns, ps;
-    const int Ktot = d->KH * d->KW * d->Cin;
-    int64_t P = (int64_t)d->N * d->Ho * d->Wo;
-    wgrad_rect_mode(d, &P, nullptr);                  // the planner balances what the tiles really walk
-    plan_wgrad_pl(d->Cout, Ktot, d->KH * d->KW, P, &ns, &ps);
-    if (ns <= 1) return 0;
-    if (wgrad_pl_wide(Ktot, d->KH * d->KW, (int64_t)d->N * d->Ho * d->Wo))      // whole 128 x 256 tiles in accumulator order
-        return (size_t)ns * ((d->Cout + 127) / 128) * ((Ktot + 255) / 256) * 32768 * sizeof(float);
-    return (size_t)ns * d->Cout * Ktot * sizeof(float);
+    return d ? plan_wgrad_pl(d, iswm_get_conv_math()).workspace : 0;
 }
 
 extern "C" int iswm_conv2d_wgrad_planes(const iswm_conv_desc* d, const void* xp, int64_t x_ps, const void* dyp, int64_t dy_ps,
                                         float* dw, float* workspace, size_t workspace_bytes, iswm_stream_t stream) {
     if (int e = wg_validate(d)) return e;
     ISWM_REQUIRE(xp && dyp && dw && aligned16(xp) && aligned16(dyp) && aligned16(dw), "wgrad_planes: bad pointer");
-    const int planes = iswm_get_conv_math() == 2 ? 1 : 3;
-    ISWM_REQUIRE(planes == 1 || (x_ps % 8 == 0 && dy_ps % 8 == 0 && x_ps > 0 && dy_ps > 0), "wgrad_planes: bad plane stride");
+    const WgPlan p = plan_wgrad_pl(d, iswm_get_conv_math());
+    ISWM_REQUIRE(p.planes == 1 || (x_ps % 8 == 0 && dy_ps % 8 == 0 && x_ps > 0 && dy_ps > 0), "wgrad_planes: bad plane stride");
+    ISWM_REQUIRE(workspace_bytes >= p.workspace && (p.workspace == 0 || (workspace && aligned16(workspace))),
+                 "wgrad_planes: workspace too small (%zu < %zu)", workspace_bytes, p.workspace);
     WgArgs a{};
     a.dy = (const unsigned short*)dyp; a.x = (const unsigned short*)xp;
     a.dyps = dy_ps * 2; a.xps = x_ps * 2;
@@ -991,36 +987,20 @@ extern "C" int iswm_conv2d_wgrad_planes(const iswm_conv_desc* d, const void* xp,
     a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil; a.ldx = d->ldx; a.ldy = d->ldy;
     a.P = d->N * d->Ho * d->Wo;
     a.Ktot = d->KH * d->KW * d->Cin;
-    a.MT = (d->Cout + 127) / 128;
-    const int wide = wgrad_pl_wide(a.Ktot, d->KH * d->KW, a.P);
-    a.NT = wide ? (a.Ktot + 255) / 256 : (a.Ktot + 127) / 128;
-    int64_t p_plan = a.P;
-    bool similar = false;
-    a.rect = (wide && wgrad_rect_mode(d, &p_plan, a.tap_order, &similar)) ? 1 : 0;
-    {
-        // one column block per XCD (k_wgrad_pls) where the taps walk their rectangles at a similar pace (rates 6 and 12 on the
-        // 33 x 33 map: fabric fetch -43 % / -27 %, kernel -4.6 % / -2.2 %; at rate 18 the corner taps are a fifth of the centre
-        // tap, the XCD's taps drift apart by images and the order only unbalances the rounds: +3 %) -- profiles/r03_rect_xcd.txt
-        if (a.rect && (d->Cin >> 8) == 8 && similar) a.rect = 2;
-    }
-    plan_wgrad_pl(d->Cout, a.Ktot, d->KH * d->KW, p_plan, &a.nsplit, &a.psplit);
-    // rect: nothing to vote on, the tile walks in-bounds pixels only
-    a.vote = (d->pad >= 4 && !a.rect) ? 1 : 0;
-    a.always = (d->KH == 1 && d->KW == 1 && d->pad == 0 && d->stride == 1) ? 1 : 0;
-    const size_t need = iswm_conv2d_wgrad_planes_workspace(d);
-    ISWM_REQUIRE(workspace_bytes >= need && (need == 0 || (workspace && aligned16(workspace))),
-                 "wgrad_planes: workspace too small (%zu < %zu)", workspace_bytes, need);
-    a.out = a.nsplit > 1 ? workspace : dw;
-    launch_wgrad_pl(a, planes, wide, (hipStream_t)stream);
+    a.MT = p.MT; a.NT = p.NT; a.nsplit = p.nsplit; a.psplit = p.psplit;
+    a.rect = p.rect; a.vote = p.vote; a.always = p.always;
+    memcpy(a.tap_order, p.tap_order, sizeof(a.tap_order));
+    a.out = p.nsplit > 1 ? workspace : dw;
+    launch_wgrad_pl(a, p, (hipStream_t)stream);
     if (int e = check_launch("wgrad_planes")) return e;
-    if (a.nsplit > 1) {
-        if (wide) {
-            const int tiles = a.MT * a.NT;
+    if (p.nsplit > 1) {
+        if (p.wide) {
+            const int tiles = p.MT * p.NT;
             hipLaunchKernelGGL(k_reduce_slabs_frag, dim3(stream_grid((int64_t)tiles * 8192, 256)), dim3(256), 0,
-                               (hipStream_t)stream, reinterpret_cast<const float4*>(workspace), dw, tiles, a.NT, a.nsplit,
+                               (hipStream_t)stream, reinterpret_cast<const float4*>(workspace), dw, tiles, p.NT, p.nsplit,
                                d->Cout, a.Ktot);
         } else {
-            launch_reduce_slabs(workspace, dw, (int64_t)d->Cout * a.Ktot / 4, a.nsplit, (hipStream_t)stream);
+            launch_reduce_slabs(workspace, dw, (int64_t)d->Cout * a.Ktot / 4, p.nsplit, (hipStream_t)stream);
         }
         return check_launch("wgrad_planes_reduce");
     }
