@@ -51,13 +51,16 @@ ROUTE = dict((rt.id, rt) for rt in FWD_ROUTES)
 ONE_ROW_LAST = ("pl_1x1", "x6_1x1", "f32_u", "bf16_1x1")             # 385 rows: the last tile holds ONE row
 SHORT_LAST = tuple(rt.id for rt in EXTRA)                            # the last tile holds tile_rows - 1 rows
 PATCH = ("x6_patch", "x6_patch_d2", "bf16_patch")                    # layout tile_rows == 0: merge-level checks
-RAGGED = ("pl_c200_d2", "pl_c320_fwd")                               # Cout no multiple of the 128-column block
+# Cout no multiple of the 128-column block (MobileNetV2's 96 / 160 columns, and 32 on the 64-column layout)
+RAGGED = ("pl_c200_d2", "pl_c320_fwd", "mb_384_96", "mb_576_160", "mb_960_320", "mb_576_160_r9", "mb_192_32", "mb_192_32_r5",
+          "mb_960_320_w9")
 # the pair-merge identity (+ DW_IDENTITY).  pl_3x3 (a padded border: |mean| / sigma 5) and the depthwise case (K = 9: 9) keep the
 # terms of the identity below the bound, so there the check adds little beyond M2_t's; the three 1 x 1 routes (no border, K = 64:
 # |mean| / sigma ~ 130) are where leaving the terms out fails it (tests/test_bn_partials_cpu.py)
 IDENTITY = ("pl_3x3", "pl_1x1", "x6_1x1", "f32_u")
 # the bias convention: conv_ref.SLICE_ROUTES and one route of every forward kernel family they lack
-BIAS_ROUTES = list(R.SLICE_ROUTES) + ["stem_even", "f32_narrow", "pl_wide"]
+# (mb_192_32: k_conv_pl2<4, 2, 3, false> writing 32 of its 64 columns)
+BIAS_ROUTES = list(R.SLICE_ROUTES) + ["stem_even", "f32_narrow", "pl_wide", "mb_192_32"]
 ASPP_TILE_ROWS = 144
 
 
@@ -189,14 +192,19 @@ def identity_terms(y, s_pub, tile_rows):
 
 
 # ---- depthwise 3 x 3 ---------------------------------------------------------------------------------------------------------------
-# (N, H, W, C, Cw, stride, dil, sliced): tests/test_dwconv3_gpu.CASES plus a last tile of tile_rows - 1 = 63 rows
+# (N, H, W, C, Cw, stride, dil, sliced): the first eight cases of tests/dw3_ref.CASES, a last tile of tile_rows - 1 = 63 rows, the
+# two fallback-layout cases (idle quad lanes) and the two shapes of dw3_ref.BIG_FWD, whose statistic tiles are the 8-pixel
+# ones production uses: 128 rows at 144 channels, 256 rows at 32 (4169 tiles: more than 2048, from a real producer)
 def dw_cases():
-    from tests.test_dwconv3_gpu import CASES
-    return list(CASES) + [(1, 1, 127, 96, 96, 1, 1, False)]
+    from tests import dw3_ref as D
+    return list(D.CASES[:8]) + [(1, 1, 127, 96, 96, 1, 1, False)] + [D.CASES[i] for i in D.FALLBACK] + list(D.BIG_FWD)
 
 
 DW_SINGLE_ROW, DW_SHORT, DW_IDENTITY = 3, 8, 1               # indices into dw_cases()
+DW_FALLBACK, DW_BIG = (9, 10), (11, 12)
 DW_KINDS = ["dense", "int", "offset"]
+# a ~100 MB shape runs once: the offset kind (the only one that sees a tile centred about a wrong count, NEEDS_MEAN)
+DW_CASE_KINDS = [(i, k) for i in range(13) for k in (["offset"] if i in DW_BIG else DW_KINDS)]
 
 
 def dw_inputs(i, kind):
@@ -551,6 +559,14 @@ FLOOR = {
     "dw3_7.S": 2.4e-07,
     "dw3_8.M2": 1.1e-06,
     "dw3_8.S": 2.4e-07,
+    "dw3_9.M2": 5.5e-07,
+    "dw3_9.S": 3.1e-07,
+    "dw3_10.M2": 8.6e-07,
+    "dw3_10.S": 2.6e-07,
+    "dw3_11.M2": 7.6e-07,
+    "dw3_11.S": 6.2e-07,
+    "dw3_12.M2": 1.2e-06,
+    "dw3_12.S": 9.1e-07,
     "f32_narrow.M2": 1.3e-06,
     "f32_narrow.S": 3.0e-07,
     "f32_short.M2": 1.4e-06,
@@ -574,6 +590,42 @@ FLOOR = {
     "fin.rvar.m1": 5.6e-08,
     "fin.scale": 8.0e-08,
     "fin.var": 5.7e-08,
+    "mb_144_24.M2": 1.5e-06,
+    "mb_144_24.S": 6.6e-07,
+    "mb_144_32.M2": 1.4e-06,
+    "mb_144_32.S": 3.3e-07,
+    "mb_160_960.M2": 1.2e-06,
+    "mb_160_960.S": 3.5e-07,
+    "mb_16_96.M2": 1.7e-06,
+    "mb_16_96.S": 3.2e-07,
+    "mb_16_96_m128.M2": 2.2e-06,
+    "mb_16_96_m128.S": 6.8e-07,
+    "mb_192_32.M2": 1.4e-06,
+    "mb_192_32.S": 5.0e-07,
+    "mb_192_32_r5.M2": 2.6e-06,
+    "mb_192_32_r5.S": 7.7e-07,
+    "mb_24_144.M2": 1.9e-06,
+    "mb_24_144.S": 3.8e-07,
+    "mb_32_16.M2": 9.8e-07,
+    "mb_32_16.S": 4.9e-07,
+    "mb_32_192.M2": 8.2e-07,
+    "mb_32_192.S": 3.5e-07,
+    "mb_32_192_m128.M2": 2.0e-06,
+    "mb_32_192_m128.S": 6.1e-07,
+    "mb_384_96.M2": 1.4e-06,
+    "mb_384_96.S": 3.9e-07,
+    "mb_576_160.M2": 1.8e-06,
+    "mb_576_160.S": 4.7e-07,
+    "mb_576_160_r9.M2": 2.2e-06,
+    "mb_576_160_r9.S": 6.6e-07,
+    "mb_960_320.M2": 1.3e-06,
+    "mb_960_320.S": 6.0e-07,
+    "mb_96_576.M2": 9.1e-07,
+    "mb_96_576.S": 3.4e-07,
+    "mb_stem.M2": 1.7e-06,
+    "mb_stem.S": 3.8e-07,
+    "mb_960_320_w9.M2": 1.9e-06,
+    "mb_960_320_w9.S": 8.0e-07,
     "pl_1x1.M2": 1.5e-06,
     "pl_1x1.S": 4.6e-07,
     "pl_1x1.identity": 2.7e-07,

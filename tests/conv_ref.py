@@ -77,6 +77,48 @@ ROUTES = [
     # -- the fp32 fallbacks bf16x6 keeps: data gradients that gather 48 / 4 channels
     _r("pl_c48", "pl", (2, 13, 13, 256, 48, 1, 1, 0, 1), "k_conv_pl2<4, 2, 3, false>", "k_conv_dgrad<64>", "k_wgrad_pls<3>"),
     _r("pl_c4", "pl", (2, 13, 13, 256, 4, 1, 1, 0, 1), "k_conv_pl2<4, 2, 3, false>", "k_conv_dgrad<64>", "k_wgrad_pls<3>"),
+    # -- MobileNetV2's 1 x 1 channel pairs and its 3 x 3 stem, as the network runs them (planes where the gathered channels are
+    #    a multiple of 64, fp32 otherwise): column counts below one column block (16, 24, 32), ragged ones (96, 144, 160),
+    #    3 / 6 / 9 / 15 K chunks, K below one 32-wide step or no multiple of 32 on the general-K fp32 kernels under bf16x6 math.
+    #    2 x 13 x 11 = 286 rows = two 128-row tiles + 30 rows (four 64-row tiles + 30)
+    _r("mb_32_16", "pl", (2, 13, 11, 32, 16, 1, 1, 0, 1), "k_conv_x6<64, 64, false, true, 3>", "k_conv_dgrad<64>",
+       "k_conv_wgrad<64, 64, 2, true, 3>"),
+    _r("mb_16_96", "pl", (2, 13, 11, 16, 96, 1, 1, 0, 1), "k_conv_fwd<64>", "k_conv_x6<64, 64, true, true, 3>",
+       "k_conv_wgrad<64, 64, 2, true, 3>"),
+    _r("mb_24_144", "pl", (2, 13, 11, 24, 144, 1, 1, 0, 1), "k_conv_fwd<64>", "k_conv_dgrad<64>", "k_conv_wgrad<64, 64, 2, true, 3>"),
+    _r("mb_144_24", "pl", (2, 13, 11, 144, 24, 1, 1, 0, 1), "k_conv_fwd<64>", "k_conv_dgrad<64>", "k_conv_wgrad<64, 64, 2, true, 3>"),
+    _r("mb_144_32", "pl", (2, 13, 11, 144, 32, 1, 1, 0, 1), "k_conv_fwd<64>", "k_conv_x6<64, 64, true, true, 3>",
+       "k_conv_wgrad<64, 64, 2, true, 3>"),
+    _r("mb_32_192", "pl", (2, 13, 11, 32, 192, 1, 1, 0, 1), "k_conv_x6<64, 64, false, true, 3>", "k_conv_pl2<4, 2, 3, true>",
+       "k_conv_wgrad<64, 64, 2, true, 3>"),
+    _r("mb_192_32", "pl", (2, 13, 11, 192, 32, 1, 1, 0, 1), "k_conv_pl2<4, 2, 3, false>", "k_conv_x6<64, 64, true, true, 3>",
+       "k_wgrad_pls<3>"),
+    _r("mb_384_96", "pl", (2, 13, 11, 384, 96, 1, 1, 0, 1), "k_conv_pl2<8, 1, 3, false>", "k_conv_x6<64, 64, true, true, 3>",
+       "k_wgrad_pls<3>"),
+    _r("mb_96_576", "pl", (2, 13, 11, 96, 576, 1, 1, 0, 1), "k_conv_x6<64, 64, false, true, 3>", "k_conv_pl2<8, 1, 3, true>",
+       "k_conv_wgrad<64, 64, 2, true, 3>"),
+    _r("mb_576_160", "pl", (2, 13, 11, 576, 160, 1, 1, 0, 1), "k_conv_pl2<8, 1, 3, false>", "k_conv_x6<64, 64, true, true, 3>",
+       "k_wgrad_pls<3>"),
+    _r("mb_160_960", "pl", (2, 13, 11, 160, 960, 1, 1, 0, 1), "k_conv_x6<64, 64, false, true, 3>", "k_conv_pl2<8, 1, 3, true>",
+       "k_conv_wgrad<64, 64, 2, true, 3>"),
+    _r("mb_960_320", "pl", (2, 13, 11, 960, 320, 1, 1, 0, 1), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<8, 1, 3, true>",
+       "k_wgrad_pls<3>"),
+    _r("mb_stem", "pl", (1, 37, 41, 4, 32, 3, 2, 1, 1), fwd="k_conv_fwd<64>", wgrad="k_conv_wgrad<64, 64, 0, true, 3>"),
+    # -- the same pairs at the smallest maps where the planner hands them to another tile (found through the host queries;
+    #    tests/test_conv_ref_cpu.py::test_mobilenet_tile_thresholds holds the row one below each to the 286-row answer):
+    #    16 385 rows for k_conv_fwd<128> / k_conv_dgrad<128> / k_conv_pl2<9, 1> at 160 columns, 16 257 for the 128-row
+    #    k_conv_x6 at 192 columns, 32 769 for k_conv_pl2<5, 2> at 32 columns
+    _r("mb_16_96_m128", "pl", (1, 73, 225, 16, 96, 1, 1, 0, 1), fwd="k_conv_fwd<128>", sub=8),
+    _r("mb_96_24_m128", "pl", (1, 127, 130, 96, 24, 1, 1, 0, 1), dgrad="k_conv_dgrad<128>", sub=8),
+    _r("mb_32_192_m128", "pl", (1, 100, 163, 32, 192, 1, 1, 0, 1), fwd="k_conv_x6<128, 64, false, true, 3>", sub=8),
+    _r("mb_576_160_r9", "pl", (1, 127, 130, 576, 160, 1, 1, 0, 1), fwd="k_conv_pl2<9, 1, 3, false>", sub=8),
+    _r("mb_192_32_r5", "pl", (1, 181, 182, 192, 32, 1, 1, 0, 1), fwd="k_conv_pl2<5, 2, 3, false>", sub=8),
+    _r("mb_32_192_r5", "pl", (1, 181, 182, 32, 192, 1, 1, 0, 1), dgrad="k_conv_pl2<5, 2, 3, true>", sub=8),
+    #    two tiles no other row names and the bench geometries reach (tools/route_table.py, mbv2_*): the 128-row k_conv_x6 data
+    #    gradient (16 -> 96 from 49 025 rows) and the 144-row wide kernel at ragged columns (960 -> 320 at 16 385 .. 21 760 rows,
+    #    among them the 16 x 33 x 33 of the bench input)
+    _r("mb_16_96_dg128", "pl", (1, 221, 222, 16, 96, 1, 1, 0, 1), dgrad="k_conv_x6<128, 64, true, true, 3>", sub=8),
+    _r("mb_960_320_w9", "pl", (1, 127, 130, 960, 320, 1, 1, 0, 1), fwd="k_conv_pl2w<9, 3, false>", sub=8, half=True),
     # -- planes off: k_conv_x6 (64- and 128-row tiles), k_conv_x6_patch, k_conv_wgrad, the stem at an even and an odd map
     _r("x6_1x1", "x6", (5, 7, 11, 64, 128, 1, 1, 0, 1), "k_conv_x6<64, 64, false, true, 3>", "k_conv_x6<64, 64, true, true, 3>",
        "k_conv_wgrad<64, 64, 2, true, 3>"),
@@ -107,6 +149,13 @@ ROUTES = [
        "k_wgrad_pls<1>"),
 ]
 ROUTE = {r.id: r for r in ROUTES}
+# MobileNetV2's 1 x 1 channel pairs (Cin, Cout) over the maps of the bench input (16 x 513 x 513: stride 2, 4, 8, 16) and its stem:
+# tools/route_table.py records what the planner answers for them (tests/golden/conv_routes.json, tests/test_conv_routes_cpu.py)
+MOBILENET_PAIRS = [(32, 16), (16, 96), (24, 144), (144, 24), (144, 32), (32, 192), (192, 32), (384, 96), (96, 576), (576, 160),
+                   (160, 960), (960, 320)]
+BENCH_MOBILENET = collections.OrderedDict(
+    [("mbv2_n16_%dx%d_c%d-%d" % (m, m, ci, co), (16, m, m, ci, co, 1, 1, 0, 1)) for m in (257, 129, 65, 33) for ci, co in MOBILENET_PAIRS] +
+    [("mbv2_n16_513x513_stem", (16, 513, 513, 4, 32, 3, 2, 1, 1))])
 # routes whose dense K is too long for the bound to see a lost term (5 x 5 x 64 = 1600; a 3 x 3 on the wide tiles): they run the
 # exact-integer and the stage-isolating kinds only (a dense 5 x 5 has K >= 800 on any bf16x6 kernel, where torch's floor is
 # 8e-7 .. 9.5e-7 and the weakest single-term mutant 2.4 x the bound)
@@ -683,6 +732,67 @@ FLOOR = {
     "pl_c4.dx": 9.4e-08,
     "pl_c4.dx_acc": 1.1e-07,
     "pl_c4.dw": 4.0e-07,
+    "mb_32_16.y": 1.4e-07,
+    "mb_32_16.dx": 2.2e-07,
+    "mb_32_16.dx_acc": 1.7e-07,
+    "mb_32_16.dw": 3.5e-07,
+    "mb_16_96.y": 1.2e-07,
+    "mb_16_96.dx": 2.9e-07,
+    "mb_16_96.dx_acc": 1.9e-07,
+    "mb_16_96.dw": 3.6e-07,
+    "mb_24_144.y": 1.7e-07,
+    "mb_24_144.dx": 4.1e-07,
+    "mb_24_144.dx_acc": 2.8e-07,
+    "mb_24_144.dw": 3.2e-07,
+    "mb_144_24.y": 3.5e-07,
+    "mb_144_24.dx": 1.8e-07,
+    "mb_144_24.dx_acc": 1.2e-07,
+    "mb_144_24.dw": 3.1e-07,
+    "mb_144_32.y": 4.2e-07,
+    "mb_144_32.dx": 2.1e-07,
+    "mb_144_32.dx_acc": 1.7e-07,
+    "mb_144_32.dw": 4.7e-07,
+    "mb_32_192.y": 1.9e-07,
+    "mb_32_192.dx": 6.1e-07,
+    "mb_32_192.dx_acc": 4.3e-07,
+    "mb_32_192.dw": 3.0e-07,
+    "mb_192_32.y": 4.3e-07,
+    "mb_192_32.dx": 2.2e-07,
+    "mb_192_32.dx_acc": 1.6e-07,
+    "mb_192_32.dw": 3.1e-07,
+    "mb_384_96.y": 6.3e-07,
+    "mb_384_96.dx": 4.6e-07,
+    "mb_384_96.dx_acc": 3.2e-07,
+    "mb_384_96.dw": 4.5e-07,
+    "mb_96_576.y": 3.3e-07,
+    "mb_96_576.dx": 4.5e-07,
+    "mb_96_576.dx_acc": 3.5e-07,
+    "mb_96_576.dw": 4.5e-07,
+    "mb_576_160.y": 4.5e-07,
+    "mb_576_160.dx": 4.6e-07,
+    "mb_576_160.dx_acc": 3.3e-07,
+    "mb_576_160.dw": 4.0e-07,
+    "mb_160_960.y": 5.6e-07,
+    "mb_160_960.dx": 5.3e-07,
+    "mb_160_960.dx_acc": 3.6e-07,
+    "mb_160_960.dw": 6.0e-07,
+    "mb_960_320.y": 5.5e-07,
+    "mb_960_320.dx": 7.5e-07,
+    "mb_960_320.dx_acc": 5.8e-07,
+    "mb_960_320.dw": 3.9e-07,
+    "mb_stem.y": 2.3e-07,
+    "mb_stem.dw": 2.9e-07,
+    "mb_16_96_m128.y": 1.6e-07,
+    "mb_96_24_m128.dx": 1.9e-07,
+    "mb_96_24_m128.dx_acc": 1.4e-07,
+    "mb_32_192_m128.y": 2.3e-07,
+    "mb_576_160_r9.y": 5.9e-07,
+    "mb_192_32_r5.y": 5.6e-07,
+    "mb_32_192_r5.dx": 6.2e-07,
+    "mb_32_192_r5.dx_acc": 4.6e-07,
+    "mb_16_96_dg128.dx": 4.2e-07,
+    "mb_16_96_dg128.dx_acc": 3.1e-07,
+    "mb_960_320_w9.y": 5.0e-07,
     "x6_1x1.y": 2.6e-07,
     "x6_1x1.dx": 5.0e-07,
     "x6_1x1.dx_acc": 2.7e-07,

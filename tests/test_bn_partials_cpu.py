@@ -3,8 +3,9 @@ claims, the fp32 floors, and the condition that makes its bounds meaningful.
 
 Tile structure: through the library's host queries (iswm_conv2d_stat_tiles / _stat_tile_rows, iswm_conv2d_fwd_packed_stat_layout,
 iswm_conv2d_pl2_tile_rows, iswm_dwconv3x3_stat_tile_rows / _stat_tiles, iswm_conv2d_dgrad_pl2_stat_tiles): the one-row and the
-tile_rows - 1 last tiles, the patch layout, the tile of a strided 1 x 1 data gradient that no tap reaches, and more than 2048
-tiles only in the synthetic finalize cases.
+tile_rows - 1 last tiles, the patch layout, the tile of a strided 1 x 1 data gradient that no tap reaches, the depthwise
+kernel's 8-pixel tiles on the two production shapes only, and more than 2048 tiles only in the synthetic finalize cases and
+in the larger of those two shapes.
 
 Sensitivity condition: for every case, each plausible wrong epilogue (bn_partials_ref.fwd_mutants, the backward mutants
 below) must miss at least one assertion of the GPU file by 3 x its bound (an equality assertion: differ at all).  It is a
@@ -68,10 +69,18 @@ def test_forward_tile_structure():
 
 
 def test_depthwise_tile_structure():
+    from tests import dw3_ref as D
     lay = [B.dw_layout(i) for i in range(len(B.dw_cases()))]
-    assert set(tr for _, _, tr in lay) == set((64, 128))                    # the <4> and the <8> pixel forms
-    for m, t, tr in lay:
-        assert t == (m + tr - 1) // tr and t <= 2048
+    assert set(tr for _, _, tr in lay) == set((64, 128, 256))              # the <4> and the <8> pixel forms at 16 and 32 pixel lanes
+    for i, (m, t, tr) in enumerate(lay):
+        c = B.dw_cases()[i][3]
+        assert t == (m + tr - 1) // tr and (t <= 2048 or i == B.DW_BIG[1])
+        assert tr == D.layout(c)[1] * (8 if i in B.DW_BIG else 4)           # 8 pixels per thread on the two production shapes only
+    for i in B.DW_BIG:
+        m, t, tr = lay[i]
+        assert 0 < m % tr < tr - 1                                          # a short last tile
+    assert lay[B.DW_BIG[1]][1] > 2048 and 2 * lay[B.DW_BIG[1]][1] * 32 + 2 * B.PAD <= 1 << 19      # (fits the GPU file's sentinel buffer)
+    assert all(D.layout(B.dw_cases()[i][3])[3] for i in B.DW_FALLBACK)      # idle quad lanes
     assert lay[B.DW_SINGLE_ROW][:2] == (9, 1)
     m, t, tr = lay[B.DW_SHORT]
     assert t == 2 and m % tr == tr - 1
@@ -233,7 +242,16 @@ def measure_dw(i, kind):
         put(key + ".identity", identity_residual(y, f32[0], f32[1], tr))
     cw = B.dw_cases()[i][4]
     bs, bq = (None if kind == "int" else B.bound(key + ".S")), B.bound(key + ".M2")
-    for name_, (ms, mq) in B.fwd_mutants(y[:, :cw], tr).items():       # (channels past Cw are zero: asserted equal to zero)
+    muts = B.fwd_mutants(y[:, :cw], tr)
+    if i in B.DW_BIG:
+        # the 4-pixel kernel launched on the 8-pixel layout: a tile's statistics cover its first tile_rows / 2 rows only (the
+        # other rows of y are never written either, which the convolution tests see)
+        v, n_t, valid = B._tiled(y[:, :cw].double(), tr)
+        half = valid & (torch.arange(tr) < tr // 2).view(1, tr, 1)
+        s_h = (v * half).sum(1)
+        dev_h = (v - (s_h / half.sum(1).clamp_min(1))[:, None]) * half
+        muts["statistics cut at the 4-pixel tile"] = (s_h, (dev_h * dev_h).sum(1))
+    for name_, (ms, mq) in muts.items():                                # (channels past Cw are zero: asserted equal to zero)
         ratio = caught([(B.tile_err(ms, ref[0][:, :cw]), bs), (B.tile_err(mq, ref[1][:, :cw]), bq)])
         ex = B.exempt(name_, kind, i == B.DW_SHORT)
         print("sens dw3_%d-%s %-26s %.1f x bound%s" % (i, kind, name_, ratio, " (exempt: NEEDS_MEAN)" if ex else ""))
@@ -241,12 +259,12 @@ def measure_dw(i, kind):
     DONE.add(("dw", i, kind))
 
 
-DW = [(i, k) for i in range(9) for k in B.DW_KINDS]
+DW = B.DW_CASE_KINDS
 
 
 @pytest.mark.parametrize("i,kind", DW, ids=["dw3_%d-%s" % c for c in DW])
 def test_depthwise_floor_and_sensitivity(i, kind):
-    assert len(B.dw_cases()) == 9
+    assert len(B.dw_cases()) == 13 and set(i for i, _ in DW) == set(range(13))
     measure_dw(i, kind)
 
 

@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 FAILED = []
 PART_ARG = {"iswm_conv2d_fwd_pl2": 6, "iswm_conv2d_fwd_packed": 5, "iswm_conv2d_fwd": 5, "iswm_dwconv3x3_fwd_stats": 5,
             "iswm_conv2d_dgrad_pl2_bn": 15}
-BUF = 1 << 18
+BUF = 1 << 19                                      # (the 4169 tiles x 32 channels of the largest depthwise case: 266 816)
 
 
 def note(tag, key, err, bound):
@@ -216,7 +216,7 @@ def test_aspp_partials_merge_to_the_stored_outputs(cid, kind, monkeypatch):
 
 
 # ---- depthwise 3 x 3 ---------------------------------------------------------------------------------------------------------------------
-DW = [(i, k) for i in range(9) for k in B.DW_KINDS]
+DW = B.DW_CASE_KINDS
 
 
 @pytest.mark.parametrize("i,kind", DW, ids=["dw3_%d-%s" % c for c in DW])

@@ -80,12 +80,14 @@ def test_route_table(rt):
         assert plan[op][1] == name, (rt.id, op, plan[op])
     if rt.mode in ("pl", "bf16pl"):                # a planes route takes the planes entry points wherever the network would
         cin, cout = rt.geom[3], rt.geom[4]
-        if "fwd" in plan and cin % 64 == 0:
+        if "fwd" in plan and R.planes_operand(rt, cin):
             assert plan["fwd"][0] == "iswm_conv2d_fwd_pl2"
         if "dgrad" in plan:
-            assert (plan["dgrad"][0] == "iswm_conv2d_dgrad_pl2") == (cout % 64 == 0)
-        if "wgrad" in plan:
-            assert plan["wgrad"][0] == "iswm_conv2d_wgrad_planes"
+            assert (plan["dgrad"][0] == "iswm_conv2d_dgrad_pl2") == R.planes_operand(rt, cout)
+        if "wgrad" in plan:                        # x travels as planes exactly when its channels are a multiple of 64
+            assert (plan["wgrad"][0] == "iswm_conv2d_wgrad_planes") == R.planes_operand(rt, cin)
+        if not rt.id.startswith("mb_"):            # every row from before the MobileNetV2 ones: planes x, the planes weight gradient
+            assert cin % 64 == 0 and plan.get("wgrad", ("iswm_conv2d_wgrad_planes",))[0] == "iswm_conv2d_wgrad_planes"
 
 
 def test_route_table_reaches_every_listed_kernel():
@@ -96,7 +98,8 @@ def test_route_table_reaches_every_listed_kernel():
              "k_stem_fwd<6>", "k_stem_wgrad", "k_conv_x6<64, 64, false, true, 3>", "k_conv_x6<64, 64, true, true, 3>",
              "k_conv_x6_patch<false, 3>", "k_conv_x6_patch<true, 3>", "k_conv_wgrad<64, 64, 2, true, 3>", "k_conv_fwd_u<64, 64>",
              "k_conv_dgrad_u<64, 64>", "k_conv_fwd<64>", "k_conv_fwd<128>", "k_conv_dgrad<64>", "k_conv_dgrad<128>",
-             "k_conv_x6<64, 64, false, true, 1>", "k_conv_pl2<8, 1, 1, false>", "k_wgrad_pls<1>"]
+             "k_conv_x6<64, 64, false, true, 1>", "k_conv_pl2<8, 1, 1, false>", "k_wgrad_pls<1>",
+             "k_conv_x6<128, 64, false, true, 3>", "k_conv_x6<128, 64, true, true, 3>", "k_conv_pl2w<9, 3, false>"]
     assert not [n for n in want if n not in names]
     assert set(("k_conv_pl2w<8, 3, false>", "k_conv_pl2<8, 1, 3, false>")) <= set(
         v for rt in R.ROUTES if rt.id not in R.NO_DENSE for v in rt.names.values())       # a dense case reaches them too
@@ -109,6 +112,50 @@ def test_route_table_reaches_every_listed_kernel():
         n, h, w, cin, cout, rates = R.ASPP[cid]
         assert R.aspp_plan_bytes(cid, 0) > 0 and R.aspp_plan_bytes(cid, 1) > 0
     assert max(R.ASPP["aspp_small"][1:3]) < 18 and min(R.ASPP["aspp_large"][1:3]) > 18
+    # the channel situations of MobileNetV2: (kernel, columns it writes, K chunks of 64, K) per operation of every row
+    sit = set()
+    for rt in R.ROUTES:
+        cin, cout, k = rt.geom[3], rt.geom[4], rt.geom[5]
+        for op, name in rt.names.items():
+            cols, kk = {"fwd": (cout, cin), "dgrad": (cin, cout), "wgrad": (cout, 0)}[op]
+            sit.add((name, cols, (kk + 63) // 64, k * k * kk))
+    has = lambda name, pred: any(s[0] == name and pred(*s[1:]) for s in sit)
+    for name in ("k_conv_pl2<4, 2, 3, false>", "k_conv_pl2<4, 2, 3, true>", "k_conv_x6<64, 64, false, true, 3>",
+                 "k_conv_x6<64, 64, true, true, 3>", "k_conv_pl2<5, 2, 3, false>", "k_conv_pl2<5, 2, 3, true>"):
+        assert has(name, lambda cols, ch, kk: cols < 64), name                 # fewer columns than a column block
+    for name in ("k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<8, 1, 3, true>"):
+        assert has(name, lambda cols, ch, kk: ch >= 9 and ch % 2 == 1), name   # an odd chunk count >= 9 (9 and 15)
+        assert has(name, lambda cols, ch, kk: cols in (96, 160)), name         # ragged columns below / above one block
+    assert has("k_conv_pl2<9, 1, 3, false>", lambda cols, ch, kk: cols == 160 and ch == 9)
+    assert has("k_conv_pl2<4, 2, 3, false>", lambda cols, ch, kk: ch == 3) and has("k_conv_pl2<8, 1, 3, false>", lambda cols, ch, kk: ch == 6)
+    for name in ("k_conv_fwd<64>", "k_conv_dgrad<64>", "k_conv_fwd<128>"):       # general-K kernels below one 32-wide K step
+        assert has(name, lambda cols, ch, kk: 0 < kk < 32), name
+    assert has("k_conv_fwd<64>", lambda cols, ch, kk: kk in (36, 144)) and has("k_conv_dgrad<64>", lambda cols, ch, kk: kk == 144)
+    for rows in (16, 24, 144):                                                 # output rows of k_conv_wgrad
+        assert has("k_conv_wgrad<64, 64, 2, true, 3>", lambda cols, ch, kk: cols == rows), rows
+    for cols_ in (24, 32, 96, 160):                                             # the accumulating data gradient of the residual blocks
+        assert any(rt.geom[3] == cols_ and "dgrad" in rt.names for rt in R.ROUTES if rt.id.startswith("mb_")), cols_
+
+
+def test_mobilenet_tile_thresholds():
+    """each mb_*_m128 / _r9 / _r5 row sits at the SMALLEST map where the planner leaves the tile of the 286-row rows: one row
+    fewer (a 1 x 1 x M map) still gets the small tile, the threshold itself the row's kernel.  A planner change that moves a
+    threshold fails here instead of silently un-covering a tile."""
+    at = {"mb_16_96_m128": ("fwd", 16385, "k_conv_fwd<64>"), "mb_96_24_m128": ("dgrad", 16385, "k_conv_dgrad<64>"),
+          "mb_32_192_m128": ("fwd", 16257, "k_conv_x6<64, 64, false, true, 3>"),
+          "mb_576_160_r9": ("fwd", 16385, "k_conv_pl2<8, 1, 3, false>"), "mb_192_32_r5": ("fwd", 32769, "k_conv_pl2<4, 2, 3, false>"),
+          "mb_32_192_r5": ("dgrad", 32769, "k_conv_pl2<4, 2, 3, true>"),
+          "mb_16_96_dg128": ("dgrad", 49025, "k_conv_x6<64, 64, true, true, 3>"),
+          "mb_960_320_w9": ("fwd", 16385, "k_conv_pl2w<8, 3, false>")}
+    assert set(at) == set(rt.id for rt in R.ROUTES if rt.id.startswith("mb_") and rt.sub)
+    for rid, (op, m, small) in at.items():
+        rt = R.ROUTE[rid]
+        n, h, w = rt.geom[:3]
+        assert m <= n * h * w < m + 1024, rid
+        flat = lambda rows: rt._replace(geom=(1, 1, rows) + tuple(rt.geom[3:]))
+        assert R.planned(flat(m))[op][1] == rt.names[op], rid
+        below = R.planned(flat(m - 1))[op][1]
+        assert below != rt.names[op] and below == small, (rid, below)
 
 
 def test_every_route_has_every_operand_kind():

@@ -10,7 +10,13 @@ iswm_packed_weight_bytes / iswm_pack_job_blocks kinds 0-3 over the (Cout, taps, 
 
 tests/golden/conv_routes.json is this table recorded from the commit BEFORE the route planner (csrc/conv_api.hip) existed;
 tests/test_conv_routes_cpu.py regenerates it from the current library and compares entry by entry.  --lib points the run at
-another build of the library (the recording run)."""
+another build of the library (the recording run).
+
+The MobileNetV2 rows (the mb_* routes of tests/conv_ref.py, the depthwise shapes dw9 .. dw12 and the mbv2_* geometries of
+conv_ref.BENCH_MOBILENET) were added later and recorded from the planner itself (the file's "recorded_later" names the commit): they pin
+what the planner answers today from here on and prove nothing by themselves -- what they select is checked against float64 in
+tests/test_conv_kernels_gpu.py.  --keep FILE copies "recorded_from" and every row FILE already has from FILE (after checking
+that the queried library still gives them) and records only the rows FILE lacks."""
 import argparse
 import collections
 import ctypes
@@ -64,8 +70,8 @@ EDGES = collections.OrderedDict([
 
 def geometries():
     """{id: (n, h, w, cin, cout, k, stride, pad, dil[, ldx, ldy])}: the routes of tests/conv_ref.py, the producer cases of
-    tests/bn_partials_ref.py (forward extras, ASPP branches, depthwise shapes as dense descriptors), the production shapes
-    and the edge list"""
+    tests/bn_partials_ref.py (forward extras, ASPP branches, depthwise shapes as dense descriptors), the production shapes,
+    the edge list and MobileNetV2's bench geometries"""
     from tests import bn_partials_ref as B
     from tests import conv_ref as R
     from tests.test_production_shapes import PROD
@@ -77,6 +83,9 @@ def geometries():
     for c in PROD:
         out["prod_n%d_%dx%d_c%d-%d_k%d_s%d_d%d" % (c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[8])] = tuple(c)
     out.update(EDGES)
+    # MobileNetV2 at the maps of the bench input.  Like the routes, the list lives with the tests (conv_ref.BENCH_MOBILENET), so
+    # that this tool and a tests tree always agree on the geometry list -- also a tests tree from before that list existed
+    out.update(getattr(R, "BENCH_MOBILENET", {}))
     return out
 
 
@@ -155,11 +164,13 @@ def table(lib):
 
 
 # ---- the file form: one line per geometry, rows in QUERIES order, kernel names as indices into one sorted list ---------------------
-def pack(tab, recorded_from=None):
-    names = sorted(set(q[k] for per in tab["routes"].values() for q in per.values() for k in QUERIES[:8] if q[k] is not None))
+def pack(tab, recorded_from=None, recorded_later=None, names=()):
+    """names: a kernel list to keep (its indices stay; names it lacks are appended, sorted)"""
+    found = set(q[k] for per in tab["routes"].values() for q in per.values() for k in QUERIES[:8] if q[k] is not None)
+    names = list(names) + sorted(found - set(names))
     row = lambda q: [None if q[k] is None else names.index(q[k]) for k in QUERIES[:8]] + [q[k] for k in QUERIES[8:]]
     return collections.OrderedDict([
-        ("recorded_from", recorded_from), ("queries", QUERIES), ("kernels", names),
+        ("recorded_from", recorded_from), ("recorded_later", recorded_later), ("queries", QUERIES), ("kernels", names),
         ("routes", collections.OrderedDict((gid, [tab["geometries"][gid]] + [row(per[m]) for m in "012"])
                                            for gid, per in tab["routes"].items())),
         ("packing", collections.OrderedDict((k, [per[m] for m in "012"]) for k, per in tab["packing"].items()))])
@@ -179,8 +190,10 @@ def unpack(packed):
 def dumps(packed):
     """JSON with one line per geometry / weight shape"""
     j = lambda v: json.dumps(v, separators=(",", ":"))
-    out = ["{", '"recorded_from":%s,' % j(packed["recorded_from"]), '"queries":%s,' % j(packed["queries"]),
-           '"kernels":%s,' % j(packed["kernels"])]
+    out = ["{", '"recorded_from":%s,' % j(packed["recorded_from"])]
+    if packed.get("recorded_later"):
+        out.append('"recorded_later":%s,' % j(packed["recorded_later"]))
+    out += ['"queries":%s,' % j(packed["queries"]), '"kernels":%s,' % j(packed["kernels"])]
     for key in ("routes", "packing"):
         out.append('"%s":{' % key)
         items = list(packed[key].items())
@@ -193,12 +206,28 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--lib", help="libiswm_hip.so to query instead of this tree's")
     ap.add_argument("--recorded-from", help="commit the queried library was built from (stored in the output)")
+    ap.add_argument("--keep", help="an earlier recording: its rows and its recorded_from stay, only the rows it lacks are recorded")
     ap.add_argument("-o", "--output", help="file to write (default: stdout)")
     a = ap.parse_args()
     from iswm_amd import _lib
     if a.lib:
         _lib.LIB_PATH = os.path.abspath(a.lib)
-    text = dumps(pack(table(_lib.load()), a.recorded_from))
+    tab = table(_lib.load())
+    if a.keep:
+        with open(a.keep) as f:
+            old = json.load(f)
+        packed = pack(tab, old["recorded_from"], None, old["kernels"])
+        for key in ("routes", "packing"):
+            stale = [k for k, v in old[key].items() if json.loads(json.dumps(packed[key].get(k))) != v]
+            assert not stale, "the queried library no longer gives the kept rows: %s" % stale[:8]
+        later = dict(old.get("recorded_later") or {})
+        new = [k for k in packed["routes"] if k not in old["routes"]]
+        if new:
+            later[a.recorded_from or "unknown"] = later.get(a.recorded_from or "unknown", []) + new
+        packed["recorded_later"] = later or None
+    else:
+        packed = pack(tab, a.recorded_from)
+    text = dumps(packed)
     if a.output:
         with open(a.output, "w") as f:
             f.write(text)
