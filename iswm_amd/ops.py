@@ -783,7 +783,9 @@ def bn_backward(dout, out, y, coef, gamma, relu, training, dgamma, dbeta, want_d
                 stats=None):
     """Returns (dy, dres|None); writes dgamma / dbeta (length-C fp32 tensors).  `out` (the saved activation, for the
     ReLU pattern) may be Planes; dy is written as Planes when dy_planes (the conv's data / weight gradient kernels
-    take it pre-split).  stats: a filled BnStats from the data gradient that produced dout -- the reduction pass is skipped."""
+    take it pre-split).  stats: a filled BnStats from the data gradient that produced dout -- the reduction pass is skipped.
+    want_dres also tells whether the stage added a residual: with ReLU and want_dres=False the pattern is recomputed from y alone,
+    which is the forward's only if it added none -- a residual stage's backward must ask for dres."""
     m, c, ldy = rows(y)
     _, _, ldd = rows(dout)
     po, ldo, pso = None, 0, 0

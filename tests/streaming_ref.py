@@ -13,6 +13,12 @@ measures every floor again and fails if a recorded figure is above 1.25 x or bel
 One exception to "torch's own": the focal modes (loss.value / loss.grad .m1, .m2).  Autograd through pow gives nan at the
 ce == 0 pixels that logits of magnitude 30 produce, so their floor is loss_ref's closed form evaluated in fp32 on torch's fp32
 log_softmax -- an fp32 evaluation of the same formula, not an independent kernel.  Mode 0 is F.cross_entropy with autograd.
+Two more, both in the second BatchNorm table (bn2.*).  (1) bn2.dgamma / bn2.dbeta where the reduce pass adds fp32 runs (more than
+8192 rows: rows8193, rows8193_plain, runs, tilecap): ATen accumulates these sums in double, which is no fp32 floor for such a kernel, so the floor
+is tests/bn_partials_ref.bwd_sums(dtype=float32) on the same inputs -- products in fp32, runs of at most RUN rows added in fp32,
+the runs in double.  (2) bn2.dy.* of the cases whose statistics are GIVEN (walk*, fallback, grid): the training-mode dy on
+statistics that are not the batch's is the derivative of nothing autograd can be handed, so the floor is bn_dy_train_fp32, the
+closed form in fp32; their out, eval-mode dy_eval, dgamma and dbeta are F.batch_norm(training=False) with autograd.
 """
 import numpy as np
 import torch
@@ -354,9 +360,10 @@ def pool_inputs(n, hw, c):
 # ======================================================================================================================
 BN_STATS = [(100.0, 0.05), (1000.0, 0.5), (30.0, 0.01)]          # (mean, std): |mean| >> std
 BN_SHAPES = [(2, 8, 17, 19), (2, 64, 17, 19)]                    # NCHW
-# (relu, residual); the last two are MobileNetV2's: ReLU6 after the expand / depthwise BatchNorm, and the projection BatchNorm
-# plus the block's identity with no activation
-BN_ACTS = [(True, False), (6, True), (6, False), (False, True)]
+# (relu, residual); the second is the last BatchNorm of a ResNet bottleneck (the one ReLU case whose backward reads the pattern
+# from the saved output); the last two are MobileNetV2's: ReLU6 after the expand / depthwise BatchNorm, and the projection
+# BatchNorm plus the block's identity with no activation
+BN_ACTS = [(True, False), (True, True), (6, True), (6, False), (False, True)]
 BN_CASES = [(st, sh, act) for st in BN_STATS for sh in BN_SHAPES for act in BN_ACTS]
 BN_IDS = ["mean%g_std%g_c%d_relu%d_res%d" % (st[0], st[1], sh[1], int(act[0]), int(act[1])) for st, sh, act in BN_CASES]
 BN_EPS = 1e-5
@@ -425,6 +432,179 @@ def naive_var_fp32(x):
 
 
 # ======================================================================================================================
+# BatchNorm, second table ("bn2"): the row / column structure of the passes, the planes forms and the one-plane mode, all at
+# ordinary statistics (mean about 0.5, std about 2) -- the large-mean floors above are 2.7e-5 .. 9.9e-5, too wide to see a lost plane
+# ======================================================================================================================
+BN2_STATS = (0.5, 2.0)
+SENTINEL = 7.0                  # every output buffer of a bn2 check holds this (in every plane) before the kernel runs
+BN_DBL_ROWS = 8192              # bn.hip, bn_backward_impl: the reduce pass works in double throughout for M <= 8192 ...
+BN_RUN = 8                      # ... and above adds fp32 runs of 8 of a thread's rows, each flushed into double
+COLSTAT_TILE_CAP = 1024         # iswm_colstat_tiles: min(1024, ceil(M / 32))
+BN_FINALIZE16_TILES = 32        # k_bn_bwd_finalize<double, 16> up to 32 tiles, <double, 4> above
+
+
+def plan_rows(m, c, fixed=0):
+    """rowmap.h plan_rows(M, C, fixed_rowblocks), restated; last_groups = float4 groups of the last column block"""
+    c4 = c // 4
+    cq = min(c4, 256)
+    rl = 256 // cq
+    colblocks = -(-c4 // cq)
+    rowblocks = fixed if fixed > 0 else max(1, min(-(-m // (4 * rl)), max(1, 8192 // colblocks)))
+    return dict(C4=c4, CQ=cq, RL=rl, colblocks=colblocks, rowblocks=rowblocks, last_groups=c4 - (colblocks - 1) * cq)
+
+
+def colstat_tiles(m):
+    return max(1, min(COLSTAT_TILE_CAP, -(-m // 32)))
+
+
+def walk(m, plan, block, lane):
+    """the rows of thread (blockIdx.x = block, row lane = lane): from block * RL + lane in steps of rowblocks * RL"""
+    return list(range(block * plan["RL"] + lane, m, plan["rowblocks"] * plan["RL"]))
+
+
+def walk_lengths(m, plan):
+    """the set of row counts over all threads of one column block"""
+    step = plan["rowblocks"] * plan["RL"]
+    return sorted({max(0, -(-(m - s) // step)) for s in range(step)})
+
+
+def reduce_structure(m, c):
+    """what bn_backward's first pass does at [M, C]: (double throughout?, tiles, plan, row counts per thread, runs of 8 per thread)"""
+    tiles = colstat_tiles(m)
+    plan = plan_rows(m, c, tiles)
+    rows = walk_lengths(m, plan)
+    return dict(dbl=m <= BN_DBL_ROWS, tiles=tiles, plan=plan, rows=rows, runs=sorted({-(-r // BN_RUN) for r in rows}),
+                finalize=16 if tiles <= BN_FINALIZE16_TILES else 4)
+
+
+def bn_apply_form(c, ldy, out, res=None):
+    """channels per thread of iswm_bn_apply_pl, the dispatch condition of bn.hip restated.  out / res = (planes 0 | 1 | 3, row pitch,
+    channel offset of the slice in a 16-byte aligned buffer, plane stride): 8 (k_bn_apply8) needs a planes output, C, every pitch
+    and every three-plane stride a multiple of 8, and 16-byte aligned slices; everything else runs the 4-channel k_bn_apply"""
+    def wide(op):
+        planes, ld, off, ps = op
+        return ld % 8 == 0 and (off * (2 if planes else 4)) % 16 == 0 and (planes != 3 or ps % 8 == 0)
+    ok = out[0] != 0 and c % 8 == 0 and ldy % 8 == 0 and wide(out) and (res is None or wide(res))
+    return 8 if ok else 4
+
+
+# statistics from the batch (colstat + bn_finalize).  id -> ((N, H, W), C, (relu, residual), planes); planes: bn_apply writes
+# Planes, the backward reads the saved output from them and writes dy as Planes.  What each reaches: BN2_CLAIMS below.
+BN2_BATCH = {
+    "rows8192": ((1, 64, 128), 16, (True, False), False),
+    "rows8193": ((1, 3, 2731), 16, (True, False), False),
+    "rows8193_plain": ((1, 3, 2731), 16, (False, True), False),      # no activation + residual (MobileNetV2's projection BatchNorm)
+    "runs": ((1, 91, 91), 512, (True, True), True),
+    "tilecap": ((1, 182, 182), 256, (6, True), False),
+    "cols2": ((1, 1, 37), 1032, (6, False), False),
+    "cols2_pl": ((1, 1, 37), 2056, (True, True), True),
+}
+# given statistics (M = 7 cannot be a training batch): 64 channels, planes out, ReLU + Planes residual; id -> rows
+BN2_WALK = {"walk7": 7, "walk33": 33, "walk100": 100}
+BN2_WALK_C = 64
+# the 4-channel kernel with plane loads and stores next to the 8-channel one, at M = 35 rows, given statistics.
+# id -> (C, (out buffer channels, offset), (residual buffer channels, offset), expected channels per thread)
+BN2_FALLBACK_ROWS = (1, 5, 7)
+BN2_FALLBACK = {
+    "c12": (12, (12, 0), (12, 0), 4),                # C % 8 == 4
+    "off4": (64, (72, 4), (64, 0), 4),               # output slice 8 bytes past a 16-byte boundary
+    "off8": (64, (72, 8), (64, 0), 8),               # the same buffer, aligned slice: the 8-channel kernel
+    "ldo76": (64, (76, 8), (64, 0), 4),              # output pitch 76 (and a plane stride of 35 x 76) is no multiple of 8
+    "res76": (64, (64, 0), (76, 8), 4),              # residual pitch 76
+    "res_off4": (64, (64, 0), (72, 4), 4),           # residual slice misaligned
+}
+
+
+def fallback_tag(fid):
+    """the floor keys of a fallback case: one set per channel count -- the five C = 64 geometries run the same inputs"""
+    return "fallback_c%d" % BN2_FALLBACK[fid][0]
+
+
+def grid_tag(relu, res):
+    """the floor keys of a grid combination: one set per activation and per residual present / absent"""
+    return "grid_relu%d_res%d" % (6 if (relu == 6 and relu is not True) else int(bool(relu)), int(res is not None))
+
+
+BN2_GRID_SHAPE = (3, 72, 9, 11)                      # NCHW; channels 0..7 are the identity (scale 1, mean 0, beta 0)
+BN2_RELUS = [False, True, 6]
+# values a bf16 store or a pattern read can get wrong: ties in both parities of the kept bit (1 + 2^-8 rounds down to 1, 1 + 2^-7 + 2^-8
+# up to 1.015625; 5.953125 down to 5.9375, 5.984375 up to 6), values in the bf16 ulp below 6 (which round UP to 6.0 but truncate
+# to 5.96875), values just above 0, and the clamps' own edges
+BF16_EDGE = [1.00390625, 1.01171875, -1.00390625, -1.01171875, 5.953125, 5.984375, 5.99, 5.9999995, 5.97, 5.96875, 6.0, 6.5,
+             1e-30, 2.0 ** -126, 1e-3, 0.0, 3.00390625, 3.01171875]
+
+
+def bf16_trunc(t):
+    """the hi plane: fp32 with the low 16 bits cleared"""
+    return (t.contiguous().view(torch.int32) & -65536).view(torch.float32)
+
+
+def bf16_rne(t):
+    """the one plane of conv math "bf16": round to nearest even (torch's own conversion), back in fp32"""
+    return t.to(torch.bfloat16).float()
+
+
+def split3(t):
+    """(hi, mid, lo) of planes.h: hi + mid + lo == t exactly"""
+    hi = bf16_trunc(t)
+    r1 = t - hi
+    mid = bf16_trunc(r1)
+    return hi, mid, bf16_trunc(r1 - mid)
+
+
+def bn2_batch_inputs(cid):
+    (n, h, w), c, (relu, res), planes = BN2_BATCH[cid]
+    return bn_inputs(BN2_STATS, (n, c, h, w), True)
+
+
+def given_stats(c, identity=0):
+    """(mean, invstd) fp32 [C] of an eval-mode BatchNorm (the restatement's variance is given_var(invstd)); the first `identity`
+    channels are mean 0, invstd 1"""
+    g = gen(900 + c)
+    mean, var = torch.randn(c, generator=g) * 0.1 + 0.5, torch.rand(c, generator=g) + 3.5
+    invstd = 1.0 / torch.sqrt(var)
+    mean[:identity], invstd[:identity] = 0.0, 1.0
+    return mean, invstd
+
+
+def given_var(invstd):
+    """the float64 variance whose 1 / sqrt(var + eps) is the fp32 invstd the kernels are handed"""
+    return 1.0 / invstd.double() ** 2 - BN_EPS
+
+
+def bn_coef(gamma, beta, mean, invstd):
+    """coef [4, C] = (scale, beta, mean, invstd) as iswm_bn_eval_coeffs forms it: scale = fp32(gamma * invstd)"""
+    return torch.stack([gamma * invstd, beta, mean, invstd])
+
+
+def bn2_given_inputs(shape, identity=0):
+    """NCHW inputs + given statistics; with `identity` > 0 (the grid) those channels have gamma 1, beta 0, residual 0, x spread
+    over [-1, 7] and BF16_EDGE planted, so their output IS act(x) exactly"""
+    n, c, h, w = shape
+    x, gamma, beta, resid, dout = bn_inputs(BN2_STATS, shape, True)
+    mean, invstd = given_stats(c, identity)
+    if identity:
+        gamma[:identity], beta[:identity] = 1.0, 0.0
+        resid[:, :identity] = 0.0
+        x[:, :identity] = torch.rand(n, identity, h, w, generator=gen(77)) * 8 - 1
+        edge = torch.tensor(BF16_EDGE)
+        for k in range(identity):
+            flat = x[:, k].reshape(-1)
+            flat[k:k + 3 * edge.numel():3] = edge.roll(k)
+            x[:, k] = flat.view(n, h, w)
+    return x, gamma, beta, resid, dout, mean, invstd
+
+
+def bn_dy_train_fp32(x, mean, invstd, gamma, dz, dgamma64, dbeta64):
+    """the training-mode dy of bn_bwd_ref evaluated in fp32 on GIVEN statistics and fp32-rounded sums: the floor where the
+    statistics are not the batch's, so that autograd has no such function"""
+    m = x.numel() // x.shape[1]
+    b = lambda t: t.float()[None, :, None, None]
+    xhat = (x - b(mean)) * b(invstd)
+    return b(gamma) * b(invstd) * (dz - b(dbeta64 / m) - xhat * b(dgamma64 / m))
+
+
+# ======================================================================================================================
 # fp32 floors (see the module docstring); measured by tests/test_streaming_ref_cpu.py
 # ======================================================================================================================
 FLOOR = {
@@ -454,6 +634,89 @@ FLOOR = {
     "bn.var.mean100": 7.4e-8,
     "bn.var.mean1000": 7.3e-8,
     "bn.var.mean30": 9.0e-8,
+    "bn2.dbeta.cols2": 1.2e-7,
+    "bn2.dbeta.cols2_pl": 6.8e-8,
+    "bn2.dbeta.fallback_c12": 1.8e-7,
+    "bn2.dbeta.fallback_c64": 1.5e-7,
+    "bn2.dbeta.grid_relu0_res0": 9.7e-8,
+    "bn2.dbeta.grid_relu0_res1": 9.7e-8,
+    "bn2.dbeta.grid_relu1_res0": 1.1e-7,
+    "bn2.dbeta.grid_relu1_res1": 8.6e-8,
+    "bn2.dbeta.grid_relu6_res0": 8.7e-8,
+    "bn2.dbeta.grid_relu6_res1": 7.0e-8,
+    "bn2.dbeta.rows8192": 3.0e-7,
+    "bn2.dbeta.rows8193": 3.2e-8,
+    "bn2.dbeta.rows8193_plain": 4.0e-8,
+    "bn2.dbeta.runs": 5.7e-8,
+    "bn2.dbeta.tilecap": 5.9e-8,
+    "bn2.dbeta.walk100": 1.2e-7,
+    "bn2.dbeta.walk33": 6.6e-8,
+    "bn2.dbeta.walk7": 6.4e-8,
+    "bn2.dgamma.cols2": 1.7e-7,
+    "bn2.dgamma.cols2_pl": 2.4e-7,
+    "bn2.dgamma.fallback_c12": 9.4e-8,
+    "bn2.dgamma.fallback_c64": 3.4e-8,
+    "bn2.dgamma.grid_relu0_res0": 8.3e-8,
+    "bn2.dgamma.grid_relu0_res1": 8.3e-8,
+    "bn2.dgamma.grid_relu1_res0": 7.8e-8,
+    "bn2.dgamma.grid_relu1_res1": 7.8e-8,
+    "bn2.dgamma.grid_relu6_res0": 5.9e-8,
+    "bn2.dgamma.grid_relu6_res1": 5.4e-8,
+    "bn2.dgamma.rows8192": 4.5e-7,
+    "bn2.dgamma.rows8193": 1.8e-7,
+    "bn2.dgamma.rows8193_plain": 2.0e-7,
+    "bn2.dgamma.runs": 2.2e-7,
+    "bn2.dgamma.tilecap": 1.1e-7,
+    "bn2.dgamma.walk100": 1.1e-7,
+    "bn2.dgamma.walk33": 9.5e-8,
+    "bn2.dgamma.walk7": 3.7e-8,
+    "bn2.dy.cols2": 1.2e-7,
+    "bn2.dy.cols2_pl": 9.3e-8,
+    "bn2.dy.fallback_c12": 7.8e-8,
+    "bn2.dy.fallback_c64": 1.2e-7,
+    "bn2.dy.grid_relu0_res0": 8.6e-8,
+    "bn2.dy.grid_relu0_res1": 8.6e-8,
+    "bn2.dy.grid_relu1_res0": 8.6e-8,
+    "bn2.dy.grid_relu1_res1": 8.6e-8,
+    "bn2.dy.grid_relu6_res0": 1.1e-7,
+    "bn2.dy.grid_relu6_res1": 8.1e-8,
+    "bn2.dy.rows8192": 1.1e-7,
+    "bn2.dy.rows8193": 1.4e-7,
+    "bn2.dy.rows8193_plain": 1.6e-7,
+    "bn2.dy.runs": 1.5e-7,
+    "bn2.dy.tilecap": 1.5e-7,
+    "bn2.dy.walk100": 7.6e-8,
+    "bn2.dy.walk33": 1.1e-7,
+    "bn2.dy.walk7": 1.4e-7,
+    "bn2.dy_eval.fallback_c12": 5.6e-8,
+    "bn2.dy_eval.fallback_c64": 5.5e-8,
+    "bn2.dy_eval.grid_relu0_res0": 6.1e-8,
+    "bn2.dy_eval.grid_relu0_res1": 6.1e-8,
+    "bn2.dy_eval.grid_relu1_res0": 6.1e-8,
+    "bn2.dy_eval.grid_relu1_res1": 6.1e-8,
+    "bn2.dy_eval.grid_relu6_res0": 6.1e-8,
+    "bn2.dy_eval.grid_relu6_res1": 6.1e-8,
+    "bn2.dy_eval.walk100": 6.8e-8,
+    "bn2.dy_eval.walk33": 6.2e-8,
+    "bn2.dy_eval.walk7": 4.4e-8,
+    "bn2.out.cols2": 1.3e-7,
+    "bn2.out.cols2_pl": 1.5e-7,
+    "bn2.out.fallback_c12": 5.5e-8,
+    "bn2.out.fallback_c64": 1.0e-7,
+    "bn2.out.grid_relu0_res0": 5.3e-8,
+    "bn2.out.grid_relu0_res1": 7.2e-8,
+    "bn2.out.grid_relu1_res0": 6.2e-8,
+    "bn2.out.grid_relu1_res1": 9.9e-8,
+    "bn2.out.grid_relu6_res0": 7.9e-8,
+    "bn2.out.grid_relu6_res1": 1.2e-7,
+    "bn2.out.rows8192": 7.5e-8,
+    "bn2.out.rows8193": 9.7e-8,
+    "bn2.out.rows8193_plain": 1.3e-7,
+    "bn2.out.runs": 1.1e-7,
+    "bn2.out.tilecap": 2.3e-7,
+    "bn2.out.walk100": 5.7e-8,
+    "bn2.out.walk33": 7.1e-8,
+    "bn2.out.walk7": 9.0e-8,
     "bn_eval.dbeta": 1.5e-7,
     "bn_eval.dgamma": 7.0e-8,
     "bn_eval.dy": 7.8e-8,

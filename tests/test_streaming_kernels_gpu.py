@@ -6,6 +6,18 @@ gather window, every filter shape of the general depthwise kernels, the optimize
 ragged channel blocks and pitched operands of the pooling kernels, and BatchNorm inputs whose mean is thousands of standard
 deviations from zero.
 
+The second BatchNorm table ("bn2", ordinary statistics: the large-mean floors are too wide to see a lost plane) adds the forms
+every training step of the default configuration runs: both sides of the reduce pass's `M <= 8192` switch, a thread that walks
+two fp32 runs of 8 rows (the second ragged), the 1024-tile cap of iswm_colstat_tiles with k_bn_bwd_finalize<double, 4> at 259 and
+1024 tiles (also on ready partials, iswm_bn_backward_stats_pl), a ragged second column block in the 4-channel kernels and in
+k_bn_apply8, k_bn_apply8's pair loop and tail row at 0 - 4 rows per thread, the 4-channel kernel with plane loads and stores where
+the dispatch of iswm_bn_apply_pl refuses the 8-channel one, and every activation x residual x format combination of the dispatch
+macros (ReLU + residual reads the pattern from the saved output: fp32, or the hi plane).  The same passes, split / join, and
+max-pool, global pool, broadcast and bilinear resize into Planes also run in the one-plane mode of conv math "bf16": a one-plane
+store must be torch's round-to-nearest-even bfloat16 of the fp32-format result bit for bit, a one-plane read is exact (the
+restatement is fed the rounded tensor, the bounds stay).  Which path each case reaches is asserted on the CPU from the restated
+plan (tests/test_streaming_ref_cpu.py), never from a kernel's name or code.
+
 The bound rule.  Every float comparison is rel_err = max|a - b| / max|b| against the float64 restatement and must be within
 4 x FLOOR[check].  FLOOR[check] (tests/streaming_ref.py, measured again by tests/test_streaming_ref_cpu.py) is the error of
 torch's own fp32 implementation of the same operation against the same restatement on the same inputs, the largest over the
@@ -36,18 +48,31 @@ def dev():
     return torch.device("cuda:0")
 
 
-def check(key, actual, expected, what=""):
-    """rel_err(actual, float64 restatement) <= 4 x FLOOR[key]"""
+def emit(line):
+    print(line)
+    if os.environ.get("ISWM_TEST_REPORT"):
+        with open(os.environ["ISWM_TEST_REPORT"], "a") as f:
+            f.write(line + "\n")
+
+
+def check(key, actual, expected, what="", worst=None):
+    """rel_err(actual, float64 restatement) <= 4 x FLOOR[key].  `worst` (a dict): the caller loops over many combinations of one
+    check and reports only the largest figure per key (report_worst); every figure is still asserted here"""
     floor = R.FLOOR[key]
     bound = 4 * floor
     a = actual.detach().cpu() if torch.is_tensor(actual) else actual
     err = rel_err(a.reshape(expected.shape) if torch.is_tensor(a) else a, expected)
     line = "%-20s floor %.1e  bound %.1e  measured %.2e  %s" % (key, floor, bound, err, what)
-    print(line)
-    if os.environ.get("ISWM_TEST_REPORT"):
-        with open(os.environ["ISWM_TEST_REPORT"], "a") as f:
-            f.write(line + "\n")
+    if worst is None:
+        emit(line)
+    elif err >= worst.get(key, (-1.0, ""))[0]:
+        worst[key] = (err, line)
     assert err <= bound, line
+
+
+def report_worst(worst, what):
+    for key in sorted(worst):
+        emit(worst[key][1] + "  (largest of " + what + ")")
 
 
 def bits(t):
@@ -531,3 +556,377 @@ def test_batchnorm_eval_backward():
     check("bn_eval.dy", nchw(dy), dy_ref)
     check("bn_eval.dgamma", dg, dg_ref)
     check("bn_eval.dbeta", db, db_ref)
+
+
+# ======================================================================================================================
+# BatchNorm, second table (streaming_ref "bn2"): the row / column structure of the passes, the planes forms, one-plane mode
+# ======================================================================================================================
+@pytest.fixture
+def conv_math(request):
+    """conv math 1 (bf16x6: activations held as three exact bf16 planes) or 2 ("bf16": one plane, rounded to nearest even)"""
+    from iswm_amd import _lib
+    lib = _lib.load()
+    old = lib.iswm_get_conv_math()
+    lib.iswm_set_conv_math(request.param)
+    yield request.param
+    lib.iswm_set_conv_math(old)
+
+
+BOTH_MATHS = pytest.mark.parametrize("conv_math", [1, 2], ids=["planes3", "plane1"], indirect=True)
+
+
+def relu_code(relu):
+    return 6 if (relu == 6 and relu is not True) else int(bool(relu))
+
+
+def fp32_buf(shape):
+    return torch.full(tuple(shape), R.SENTINEL, device=dev())
+
+
+def planes_view(shape, width=None, off=0):
+    """(view, buffer): a Planes view of channels [off, off + C) of a buffer `width` channels wide that holds SENTINEL in every
+    plane"""
+    from iswm_amd import ops
+    n, h, w, c = shape
+    buf = ops.new_planes(n, h, w, width or c, dev())
+    buf.t.fill_(R.SENTINEL)
+    return (buf if (width or c) == c else buf[..., off:off + c]), buf
+
+
+def rest_untouched(buf, off, c):
+    """the channels of the buffer outside [off, off + c) keep the sentinel in every plane"""
+    return bool((buf.t[..., :off] == R.SENTINEL).all()) and bool((buf.t[..., off + c:] == R.SENTINEL).all())
+
+
+def as_planes(t, width=None, off=0):
+    from iswm_amd import ops
+    view, _ = planes_view(tuple(t.shape), width, off)
+    return ops.split_planes(t, out=view)
+
+
+def bf16_bits(t):
+    return t.detach().cpu().contiguous().view(torch.int16)
+
+
+def one_plane_is_rne(p, fp32_form):
+    """the single plane holds torch's round-to-nearest-even bfloat16 of the fp32-format result, bit for bit"""
+    return p.t.shape[0] == 1 and torch.equal(bf16_bits(p.t[0]), bf16_bits(fp32_form.detach().cpu().to(torch.bfloat16)))
+
+
+def stored_equal(p, fp32_form):
+    """a Planes result of data movement: three planes join to the fp32 form's bits, one plane is its rounding"""
+    return same_bits(p.f32(), fp32_form) if p.t.shape[0] == 3 else one_plane_is_rne(p, fp32_form)
+
+
+class Bn2:
+    """the inputs of one bn2 case on both sides: NCHW on the CPU for the restatement, NHWC on the GPU for the kernels.  With
+    (mean, invstd) the statistics are given (eval-mode coefficients), without they are the batch's, from colstat + bn_finalize"""
+
+    def __init__(self, x, gamma, beta, resid, dout, mean=None, invstd=None):
+        self.x, self.gamma, self.beta, self.resid, self.dout, self.mean, self.invstd = x, gamma, beta, resid, dout, mean, invstd
+        self.var = None if mean is None else R.given_var(invstd)
+        self.yh, self.rh, self.dh, self.gd = nhwc(x), nhwc(resid), nhwc(dout), gamma.to(dev())
+        self.shape = tuple(self.yh.shape)
+        self._coef, self._fwd = None, {}
+
+    def coef(self):
+        if self._coef is None:
+            self._coef = (bn_statistics(self.x, self.gamma, self.beta)[0] if self.mean is None else
+                          R.bn_coef(self.gamma, self.beta, self.mean, self.invstd).to(dev()))
+        return self._coef
+
+    def fwd(self, relu, res):
+        """the float64 forward; res: None, "exact", or "bf16" (the residual as one plane holds it: a one-plane READ is exact, so
+        the restatement is fed the rounded tensor).  Kept only for the small cases."""
+        k = (relu_code(relu), res)
+        if k in self._fwd:
+            return self._fwd[k]
+        resid = None if res is None else (R.bf16_rne(self.resid) if res == "bf16" else self.resid)
+        f = R.bn_fwd_ref(self.x, self.gamma, self.beta, resid, relu, self.mean, self.var)
+        if self.x.numel() < (1 << 20):
+            self._fwd[k] = f
+        return f
+
+
+# the seeded CPU inputs are built once; a Bn2 (its GPU tensors, its float64 results) lives for one test only
+_bn2_batch_inputs = functools.lru_cache(maxsize=None)(R.bn2_batch_inputs)
+_bn2_given_inputs = functools.lru_cache(maxsize=None)(R.bn2_given_inputs)
+
+
+def bn2_batch_case(cid):
+    return Bn2(*_bn2_batch_inputs(cid))
+
+
+def bn2_given_case(shape, identity=0):
+    return Bn2(*_bn2_given_inputs(shape, identity))
+
+
+def bn2_forward(case, tag, relu, res=None, out="f32", what="", worst=None):
+    """bn_apply into an fp32 tensor and, with out = ("planes", [buffer channels, offset]), into a Planes tensor or channel slice;
+    res: None, "f32" or ("planes", [buffer channels, offset]).  The fp32 form goes to float64; three planes go to float64 as
+    well, one plane must be the rounding of the fp32 form.  Returns (float64 forward, fp32 output, Planes output or None)"""
+    from iswm_amd import ops
+    one = ops.nplanes() == 1
+    rop, kind = None, None
+    if res == "f32":
+        rop, kind = case.rh, "exact"
+    elif res is not None:
+        rop, kind = as_planes(case.rh, *res[1:]), ("bf16" if one else "exact")
+    f = case.fwd(relu, kind)
+    key, c = "bn2.out." + tag, case.shape[3]
+    o32 = ops.bn_apply(case.yh, case.coef(), relu, rop, out=fp32_buf(case.shape))
+    check(key, nchw(o32), f["out"], what + " fp32 out", worst)
+    op = None
+    if out != "f32":
+        op, buf = planes_view(case.shape, *out[1:])
+        ops.bn_apply(case.yh, case.coef(), relu, rop, out=op)
+        assert rest_untouched(buf, out[2] if len(out) > 2 else 0, c), what
+        if one:
+            assert one_plane_is_rne(op, o32), what
+        else:
+            check(key, nchw(op.f32()), f["out"], what + " planes out", worst)
+    return f, o32, op
+
+
+def bn2_backward(case, tag, f, relu, saved, training, want_dres, dy_planes, what="", worst=None, stats=None):
+    """bn_backward on the saved output `saved` (fp32 or Planes), dy as fp32 and, with dy_planes, as Planes too.  The pattern is the
+    kernel's own: that of the saved output as handed over (one plane: of the STORED, rounded value), which may differ from the
+    float64 one only at ties -- except for a one-plane saved output, whose rounding moves the pattern by design and whose bits
+    bn2_forward has tied to the fp32 form"""
+    from iswm_amd import ops
+    one = ops.nplanes() == 1
+    c = case.shape[3]
+    recomputed = relu_code(relu) == 1 and not want_dres
+    if recomputed:
+        # the contract of ops.bn_backward: want_dres says whether the stage had a residual.  ReLU without it never reads the saved
+        # output: the pattern is recomputed from y as (y - mean) * scale + beta > 0 -- for a stage that did add a residual that is
+        # the pattern of the forward WITHOUT it, and that is what is held here (the models ask for dres whenever they add one)
+        src, ftie = ops.bn_apply(case.yh, case.coef(), True, out=fp32_buf(case.shape)), case.fwd(True, None)
+    else:
+        src, ftie = (saved.f32() if ops.is_planes(saved) else saved), f
+    mask = R.bn_act_mask(nchw(src), relu)
+    if recomputed or not (one and ops.is_planes(saved)):
+        assert pattern_differs_only_at_ties(mask, ftie, relu, "bn2.out." + tag), what
+    dy_ref, dg_ref, db_ref, dres_ref = R.bn_bwd_ref(f, case.gamma, case.dout, mask, training)
+    kdy = "bn2.%s.%s" % ("dy" if training else "dy_eval", tag)
+
+    def run(dy_buf):
+        dg, db = fp32_buf((c,)), fp32_buf((c,))
+        dy, dres = ops.bn_backward(case.dh, saved if relu else None, case.yh, case.coef(), case.gd, relu, training, dg, db,
+                                   want_dres=want_dres, dy=dy_buf, stats=stats)
+        if want_dres:
+            assert torch.equal(nchw(dres).double(), dres_ref), what + ": dres is not dout under the pattern"
+        return dy, dg, db
+
+    dy, dg, db = run(fp32_buf(case.shape))
+    check("bn2.dgamma." + tag, dg, dg_ref, what, worst)
+    check("bn2.dbeta." + tag, db, db_ref, what, worst)
+    check(kdy, nchw(dy), dy_ref, what + " fp32 dy", worst)
+    if dy_planes:
+        view, _ = planes_view(case.shape)
+        dyp, dgp, dbp = run(view)
+        assert same_bits(dgp, dg) and same_bits(dbp, db), what
+        if one:
+            assert one_plane_is_rne(dyp, dy), what
+        else:
+            check(kdy, nchw(dyp.f32()), dy_ref, what + " planes dy", worst)
+
+
+BN2_BATCH_RUNS = [(cid, 1) for cid in R.BN2_BATCH] + [("cols2_pl", 2)]
+
+
+@pytest.mark.parametrize("cid,conv_math", BN2_BATCH_RUNS, ids=["%s_math%d" % r for r in BN2_BATCH_RUNS], indirect=["conv_math"])
+def test_bn2_rows_and_columns(cid, conv_math):
+    """bn_apply and bn_backward on the kernels' own batch statistics at the row and channel counts where the passes change shape
+    (what each case reaches: BN2_CLAIMS of tests/test_streaming_ref_cpu.py, asserted there from the restated plan): both sides of
+    the reduce pass's `M <= 8192` (above it with the recomputed ReLU pattern and with no activation + residual: the reduce and
+    apply kernels' RELU == 0 forms), a thread with two fp32 runs of 8 rows (the second ragged), the 1024-tile cap with the finalize
+    at 259 and 1024 tiles, a ragged second column block in the 4-channel kernels and in k_bn_apply8"""
+    (n, h, w), c, (relu, res), planes = R.BN2_BATCH[cid]
+    case = bn2_batch_case(cid)
+    fmt = ("planes",) if planes else "f32"
+    f, o32, op = bn2_forward(case, cid, relu, res=fmt if res else None, out=fmt, what=cid)
+    for saved in (o32, op)[:2 if planes else 1]:
+        bn2_backward(case, cid, f, relu, saved, True, res, planes, "%s saved %s" % (cid, "planes" if saved is op else "fp32"))
+
+
+@pytest.mark.parametrize("conv_math", [1], ids=["planes3"], indirect=True)
+@pytest.mark.parametrize("cid", ["runs", "tilecap"])
+def test_bn2_backward_on_ready_partials(cid, conv_math):
+    """ops.bn_backward(stats=...) -- iswm_bn_backward_stats_pl: finalize + apply on partials [2][tiles][C] that a producer wrote --
+    with the partials the reduce pass of iswm_bn_backward_pl leaves in its workspace for the same inputs, tiles ==
+    iswm_colstat_tiles(M): k_bn_bwd_finalize<double, 4> at 259 and at 1024 tiles on ready partials"""
+    import ctypes
+    from iswm_amd import _lib, ops
+    lib = _lib.load()
+    (n, h, w), c, (relu, res), planes = R.BN2_BATCH[cid]
+    case = bn2_batch_case(cid)
+    f, o32, _ = bn2_forward(case, cid, relu, res="f32", what=cid)
+    m, tiles = n * h * w, lib.iswm_colstat_tiles(n * h * w)
+    need = lib.iswm_bn_bwd_workspace(m, c)
+    assert need == (2 * tiles * c + 2 * c) * 8
+    ws = torch.zeros(need // 8, dtype=torch.float64, device=dev())
+    coef, p = case.coef(), ops._p
+    dg, db, dy, dres = fp32_buf((c,)), fp32_buf((c,)), fp32_buf(case.shape), fp32_buf(case.shape)
+    ops.call("iswm_bn_backward_pl", p(case.dh), c, p(o32), c, 0, p(case.yh), c, m, c, p(coef[2]), p(coef[3]), p(case.gd), None, None,
+             relu_code(relu), 1, p(dg), p(db), p(dy), c, 0, p(dres), c, p(ws), need, ops._stream())
+    st = ops.BnStats(case.yh, coef, relu)
+    st.partials, st.tiles = ws[:2 * tiles * c].clone(), tiles
+    bn2_backward(case, cid, f, relu, o32, True, True, planes, cid + " ready partials", stats=st)
+
+
+BN2_WALK_RUNS = [(wid, 1) for wid in R.BN2_WALK] + [("walk33", 2)]
+
+
+@pytest.mark.parametrize("wid,conv_math", BN2_WALK_RUNS, ids=["%s_math%d" % r for r in BN2_WALK_RUNS], indirect=["conv_math"])
+def test_bn2_apply8_pair_walk(wid, conv_math):
+    """k_bn_apply8 at 64 channels (32 row lanes) with 7, 33 and 100 rows: threads with no row or the tail row only, with the tail
+    row only or one pair, with a pair and the tail row or two pairs; ReLU, a Planes residual through ld8x, given statistics, the
+    backward in training and in eval form on the fp32 and on the Planes saved output"""
+    case = bn2_given_case((1, R.BN2_WALK_C, 1, R.BN2_WALK[wid]))
+    f, o32, op = bn2_forward(case, wid, True, res=("planes",), out=("planes",), what=wid)
+    for training in (True, False):
+        for saved in (o32, op):
+            bn2_backward(case, wid, f, True, saved, training, True, True,
+                         "%s training %d saved %s" % (wid, training, "planes" if saved is op else "fp32"))
+
+
+@BOTH_MATHS
+@pytest.mark.parametrize("fid", list(R.BN2_FALLBACK))
+def test_bn2_four_channel_kernel_on_planes(fid, conv_math):
+    """bn_apply with a Planes output where the dispatch of iswm_bn_apply_pl must take the 4-channel kernel (8-byte plane loads and
+    stores): C % 8 == 4, an output slice that is not 16-byte aligned, a pitch of 76, a residual of pitch 76 or misaligned -- and
+    "off8", the aligned slice of the same buffer, which takes the 8-channel kernel.  The expected form of each case is in
+    streaming_ref.BN2_FALLBACK and is asserted from the restated condition on the CPU (test_bn2_fallback_forms)"""
+    c, (ow, oo), (rw, ro), form = R.BN2_FALLBACK[fid]
+    n, h, w = R.BN2_FALLBACK_ROWS
+    case = bn2_given_case((n, c, h, w))
+    what = "%s (%d-channel kernel)" % (fid, form)
+    tag = R.fallback_tag(fid)
+    f, o32, op = bn2_forward(case, tag, True, res=("planes", rw, ro), out=("planes", ow, oo), what=what)
+    for training in (True, False):
+        bn2_backward(case, tag, f, True, op, training, True, True, "%s training %d" % (what, training))
+
+
+BN2_GRID_RES = {"none": None, "f32": "f32", "planes": ("planes",), "slice": ("planes", 96, 16)}
+
+
+@BOTH_MATHS
+@pytest.mark.parametrize("res", list(BN2_GRID_RES))
+@pytest.mark.parametrize("relu", R.BN2_RELUS, ids=["none", "relu", "relu6"])
+def test_bn2_activation_residual_format_grid(relu, res, conv_math):
+    """every combination the dispatch macros of bn.hip instantiate, at 3 x 9 x 11 x 72: activation x residual (none, fp32, Planes,
+    a Planes slice of a 96-channel buffer) x output (fp32, Planes, a Planes slice of a 128-channel buffer); the backward with the
+    saved output as fp32 and as Planes (the pattern through ld4x_hi), dy as fp32 and as Planes, with and without dres, in training
+    and in eval form.  Channels 0..7 are the identity and carry streaming_ref.BF16_EDGE: bf16 ties of both parities, values in the
+    bf16 ulp below 6 and just above 0.
+
+    Convention of the one-plane mode (conv math "bf16"): a stored activation IS its rounding to nearest even, and the ReLU6 pattern
+    is that of the stored value -- an output of 5.99 is stored as 6.0 and passes no gradient.  The restatement takes its pattern
+    from the joined output, so both agree; the three-plane mode reads the pattern from the hi plane, whose truncation decides
+    0 < x < 6 as the fp32 value does."""
+    from iswm_amd import ops
+    case = bn2_given_case(R.BN2_GRID_SHAPE, 8)
+    worst, tag = {}, R.grid_tag(relu, BN2_GRID_RES[res])
+    for out in (("planes",), ("planes", 128, 40)):
+        what = "relu %d res %s out %s" % (relu_code(relu), res, "slice" if len(out) > 1 else "planes")
+        f, o32, op = bn2_forward(case, tag, relu, BN2_GRID_RES[res], out, what, worst)
+    if relu_code(relu) == 6:
+        rounded_up = (op.f32() == 6) & (o32 < 6)
+        assert bool(rounded_up.any()) == (conv_math == 2)              # the case the convention is about is in the data
+    for saved in (o32, op):
+        for training in (True, False):
+            for want_dres in (False, True):
+                bn2_backward(case, tag, f, relu, saved, training, want_dres, True, "%s saved %s training %d dres %d" % (
+                    what, "planes" if saved is op else "fp32", training, want_dres), worst)
+    report_worst(worst, "relu %d res %s math %d" % (relu_code(relu), res, conv_math))
+
+
+@BOTH_MATHS
+def test_split_join_ties_and_second_grid_trip(conv_math):
+    """split_planes then f32(): the identity under bf16x6, torch's .to(bfloat16).float() under conv math "bf16" -- on bf16 ties of
+    both parities and on the 33 124 x 256 tensor of `tilecap`, whose 2.1 M float4 groups take the grid-stride loop of both kernels
+    (2048 blocks x 256 threads) round more than once"""
+    from iswm_amd import ops
+    edge = torch.tensor(R.BF16_EDGE + [-v for v in R.BF16_EDGE] + [65504.0, -3e38, 1.0, -1.0]).view(1, 1, 5, 8)
+    big = bn2_batch_case("tilecap").yh
+    assert big.numel() // 4 > 2048 * 256
+    for x in (edge.to(dev()), big):
+        p = ops.split_planes(x)
+        assert p.t.shape[0] == (3 if conv_math == 1 else 1)
+        if conv_math == 1:                  # the identity of tests/test_planes.py: equal as values (the join of -0.0 is +0.0)
+            assert torch.equal(p.f32().cpu(), x.cpu())
+        else:
+            want = x.cpu().to(torch.bfloat16).float()
+            assert same_bits(p.f32(), want)
+            assert one_plane_is_rne(p, x)
+            assert not torch.equal(want, R.bf16_trunc(x.cpu()))        # truncation would differ
+
+
+# ======================================================================================================================
+# pooling, broadcast and resize into Planes, in both plane counts
+# ======================================================================================================================
+@BOTH_MATHS
+@pytest.mark.parametrize("h,w,c", R.MAXPOOL_CASES)
+def test_maxpool_into_planes(h, w, c, conv_math):
+    """maxpool_fwd(planes=True): values and indices equal to the fp32 form's and to ATen's (tap kh * 3 + kw -> ATen's flat input
+    index); the stored planes are the fp32 values (three planes) or their rounding (one plane)"""
+    import torch.nn.functional as F
+    from iswm_amd import ops
+    x = torch.relu(torch.randn(2, c, h, w, generator=R.gen(h * w)))
+    x.view(-1)[:len(R.BF16_EDGE)] = torch.tensor(R.BF16_EDGE)
+    y_ref, i_ref = F.max_pool2d(x.double(), 3, 2, 1, return_indices=True)
+    xh = x.permute(0, 2, 3, 1).contiguous().to(dev())
+    y_f, i_f = ops.maxpool_fwd(xh)
+    y_p, i_p = ops.maxpool_fwd(xh, planes=True)
+    assert torch.equal(nchw(y_f).double(), y_ref) and torch.equal(i_f, i_p) and stored_equal(y_p, y_f)
+    ho, wo = y_ref.shape[2:]
+    tap = nchw(i_f).long()
+    flat = (torch.arange(ho)[:, None] * 2 - 1 + tap // 3) * w + (torch.arange(wo)[None, :] * 2 - 1 + tap % 3)
+    assert torch.equal(flat, i_ref)
+
+
+@BOTH_MATHS
+@pytest.mark.parametrize("c", [48, 304])
+@pytest.mark.parametrize("hw", [(1, 7), (33, 33)], ids=["hw7", "hw1089"])
+def test_gap_fwd_from_planes(hw, c, conv_math):
+    """gap_fwd through ld4x from a Planes tensor and from a pitched Planes slice: the four-rows-in-flight loop and its tail.  One
+    plane: the read is exact, so the restatement is the mean of the rounded tensor"""
+    from iswm_amd import ops
+    x = R.pool_inputs(3, hw, c)
+    held = x if conv_math == 1 else R.bf16_rne(x)
+    want = held.double().mean((1, 2), keepdim=True)
+    xd = x.to(dev())
+    check("gap.fwd", ops.gap_fwd(ops.split_planes(xd)), want, "planes")
+    check("gap.fwd", ops.gap_fwd(as_planes(xd, c + 16, 8)), want, "planes slice, pitch %d" % (c + 16))
+
+
+@BOTH_MATHS
+@pytest.mark.parametrize("hw", [(1, 1), (1, 7), (33, 33)], ids=["hw1", "hw7", "hw1089"])
+def test_bcast_fwd_into_a_planes_slice(hw, conv_math):
+    from iswm_amd import ops
+    n, c = 3, 48
+    v = R.pool_inputs(n, (1, 1), c)
+    v.view(-1)[:len(R.BF16_EDGE)] = torch.tensor(R.BF16_EDGE)
+    view, buf = planes_view((n, hw[0], hw[1], c), c + 24, 8)
+    ops.bcast_fwd(v.to(dev()), view)
+    assert stored_equal(view, v.expand(n, hw[0], hw[1], c).contiguous()) and rest_untouched(buf, 8, c)
+
+
+@BOTH_MATHS
+@pytest.mark.parametrize("shape", R.RESIZE_SMALLEST + [R.RESIZE_SHAPES[1]], ids=lambda s: "%dx%d_to_%dx%d" % (s[0] + s[1]))
+def test_bilinear_fwd_into_a_planes_slice(shape, conv_math):
+    from iswm_amd import ops
+    c = 48
+    (hi, wi), (ho, wo) = shape
+    x, _ = R.resize_inputs(shape, c)
+    ref = R.bilinear_fwd_ref(x, ho, wo)
+    dense = ops.bilinear_fwd(x.to(dev()), ho, wo)
+    check("bilinear.fwd", dense, ref, "fp32 form")
+    view, buf = planes_view((R.RESIZE_N, ho, wo, c), c + 48, 32)
+    ops.bilinear_fwd(x.to(dev()), ho, wo, out=view)
+    assert rest_untouched(buf, 32, c)
+    if conv_math == 2:
+        assert one_plane_is_rne(view, dense)
+    else:
+        check("bilinear.fwd", view.f32(), ref, "planes slice")

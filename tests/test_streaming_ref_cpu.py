@@ -8,7 +8,13 @@ F.conv2d(groups) in float64; it is tied to a direct tap loop here.)
 Floors: for every float comparison of the GPU tests, torch's own fp32 implementation of the operation is compared with the
 float64 restatement on the same inputs (single-threaded, so the figures do not depend on the machine's core count); the
 largest figure over a check's cases must lie in [FLOOR / 2, 1.25 FLOOR] of the recorded streaming_ref.FLOOR entry, so the
-table can neither rot nor be inflated.  `pytest -s` prints the measured figures."""
+table can neither rot nor be inflated.  `pytest -s` prints the measured figures.
+
+For the second BatchNorm table (streaming_ref "bn2") this file also asserts, from plan_rows and the dispatch thresholds of bn.hip
+restated in Python and the library's own tile count and workspace size, which path every case reaches (rows and fp32 runs per
+thread, column blocks, groups in the last block, 4- or 8-channel apply kernel), and shows on the restatement alone that the
+faults those cases are there for -- a row, a run, a column block, a tile slot, a plane or a pattern lost -- miss the GPU
+assertions by at least 3 x the bound."""
 import contextlib
 import functools
 
@@ -390,3 +396,317 @@ def test_naive_variance_misses_the_bound_by_100x(stats):
         bound = 4 * R.FLOOR["bn.var.mean%g" % stats[0]]
         print("naive fp32 variance rel err %.3e, bound %.3e" % (err, bound))
         assert err >= 100 * bound
+
+
+# ---- BatchNorm, second table (bn2): path claims, floors, mutants ---------------------------------------------------------
+# what each case of streaming_ref.BN2_BATCH / BN2_WALK reaches, asserted below from the restated plan_rows and thresholds.
+#   reduce: (double throughout, tiles, RL, column blocks, groups in the last block, rows per thread, runs of 8 per thread, finalize CPB)
+#   apply:  (channels per thread of bn_apply, column blocks, groups in the last block, rows per thread)
+BN2_CLAIMS = {
+    "rows8192": dict(reduce=(True, 256, 64, 1, 4, [0, 1], [0, 1], 4), apply=(4, 1, 4, [4])),
+    "rows8193": dict(reduce=(False, 257, 64, 1, 4, [0, 1], [0, 1], 4), apply=(4, 1, 4, [3, 4])),
+    "rows8193_plain": dict(reduce=(False, 257, 64, 1, 4, [0, 1], [0, 1], 4), apply=(4, 1, 4, [3, 4])),
+    "runs": dict(reduce=(False, 259, 2, 1, 128, [15, 16], [2], 4), apply=(8, 1, 64, [3, 4])),
+    "tilecap": dict(reduce=(False, 1024, 4, 1, 64, [8, 9], [1, 2], 4), apply=(4, 1, 64, [3, 4])),
+    "cols2": dict(reduce=(True, 2, 1, 2, 2, [18, 19], [3], 16), apply=(4, 2, 2, [3, 4])),
+    "cols2_pl": dict(reduce=(True, 2, 1, 3, 2, [18, 19], [3], 16), apply=(8, 2, 1, [3, 4])),
+    "walk7": dict(reduce=(True, 1, 16, 1, 16, [0, 1], [0, 1], 16), apply=(8, 1, 8, [0, 1])),
+    "walk33": dict(reduce=(True, 2, 16, 1, 16, [1, 2], [1], 16), apply=(8, 1, 8, [1, 2])),
+    "walk100": dict(reduce=(True, 4, 16, 1, 16, [1, 2], [1], 16), apply=(8, 1, 8, [3, 4])),
+}
+
+
+def bn2_shape(cid):
+    """(rows, channels, planes) of a batch or walk case"""
+    if cid in R.BN2_BATCH:
+        (n, h, w), c, _, planes = R.BN2_BATCH[cid]
+        return n * h * w, c, planes
+    return R.BN2_WALK[cid], R.BN2_WALK_C, True
+
+
+@pytest.mark.parametrize("cid", list(BN2_CLAIMS))
+def test_bn2_cases_reach_the_paths_they_claim(cid):
+    """plan_rows, `dbl = M <= 8192`, the finalize's `tiles > 32` and the 1024-tile cap restated in streaming_ref; the tile count and
+    the workspace size are the library's own"""
+    from iswm_amd import _lib
+    lib = _lib.load()
+    m, c, planes = bn2_shape(cid)
+    s = R.reduce_structure(m, c)
+    assert s["tiles"] == lib.iswm_colstat_tiles(m)
+    assert lib.iswm_bn_bwd_workspace(m, c) == (2 * s["tiles"] * c + 2 * c) * 8           # double [2][tiles][C] + [2][C]
+    p = s["plan"]
+    got = (s["dbl"], s["tiles"], p["RL"], p["colblocks"], p["last_groups"], s["rows"], s["runs"], s["finalize"])
+    assert got == BN2_CLAIMS[cid]["reduce"], got
+    dense = (3 if planes else 0, c, 0, m * c)
+    form = R.bn_apply_form(c, c, dense, dense)
+    p = R.plan_rows(m, c // 2 if form == 8 else c)
+    got = (form, p["colblocks"], p["last_groups"], R.walk_lengths(m, p))
+    assert got == BN2_CLAIMS[cid]["apply"], got
+    if cid == "tilecap":
+        assert -(-m // 32) == 1036 and m * c // 4 > 2048 * 256                           # uncapped tiles; a second grid-stride trip
+    if cid == "runs":                                                                    # the second run is ragged for SOME threads
+        assert {len(R.walk(m, s["plan"], b, l)) % R.BN_RUN for b in range(s["tiles"]) for l in range(2)} == {7, 0}
+    if form == 8:                                       # k_bn_apply8: rows // 2 pair iterations, rows % 2 tail rows
+        pairs_tail = {(r // 2, r % 2) for r in got[3]}
+        want = {"runs": {(1, 1), (2, 0)}, "cols2_pl": {(1, 1), (2, 0)}, "walk7": {(0, 0), (0, 1)}, "walk33": {(0, 1), (1, 0)},
+                "walk100": {(1, 1), (2, 0)}}[cid]
+        assert pairs_tail == want, pairs_tail
+
+
+def test_bn2_fallback_forms():
+    """the dispatch of iswm_bn_apply_pl restated (streaming_ref.bn_apply_form), in both plane counts"""
+    n, h, w = R.BN2_FALLBACK_ROWS
+    m = n * h * w
+    for fid, (c, (ow, oo), (rw, ro), want) in R.BN2_FALLBACK.items():
+        for planes in (3, 1):
+            assert R.bn_apply_form(c, c, (planes, ow, oo, m * ow), (planes, rw, ro, m * rw)) == want, (fid, planes)
+    assert R.bn_apply_form(64, 64, (0, 64, 0, 0)) == 4                                   # an fp32 output: always the 4-channel kernel
+    assert R.bn_apply_form(64, 64, (3, 64, 0, m * 64), (0, 64, 0, 0)) == 8               # an fp32 residual does not matter
+
+
+def test_bf16_restatements():
+    x = torch.cat([torch.randn(4096, generator=R.gen(5)) * 3, torch.tensor(R.BF16_EDGE)])
+    hi, mid, lo = R.split3(x)
+    assert torch.equal(hi + mid + lo, x) and torch.equal((hi.double() + mid.double() + lo.double()).float(), x)
+    for p in (hi, mid, lo):
+        assert torch.equal(p.to(torch.bfloat16).float(), p)
+    e = dict(zip(R.BF16_EDGE, R.bf16_rne(torch.tensor(R.BF16_EDGE)).tolist()))
+    assert e[1.00390625] == 1.0 and e[1.01171875] == 1.015625 and e[5.953125] == 5.9375 and e[5.984375] == 6.0 and e[5.99] == 6.0
+    assert float(R.bf16_trunc(torch.tensor([5.99]))) == 5.96875
+
+
+def torch_bn_fp32(x, gamma, beta, resid, dout, relu, mean=None, var=None, eps=R.BN_EPS):
+    """torch's fp32 F.batch_norm (+ residual, activation) and autograd; batch statistics, or the given ones in eval mode"""
+    xr, gr, br = x.clone().requires_grad_(True), gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    rr = resid.clone().requires_grad_(True) if resid is not None else None
+    z = F.batch_norm(xr, mean, var, gr, br, mean is None, 0.1, eps)
+    out = R.bn_act(z + rr if rr is not None else z, relu)
+    out.backward(dout)
+    return dict(out=out.detach(), dy=xr.grad, dgamma=gr.grad, dbeta=br.grad)
+
+
+def bn2_floor_batch(cid, round_resid=False):
+    from tests.bn_partials_ref import bwd_sums
+    (n, h, w), c, (relu, res), _ = R.BN2_BATCH[cid]
+    x, gamma, beta, resid, dout = R.bn2_batch_inputs(cid)
+    resid = (R.bf16_rne(resid) if round_resid else resid) if res else None
+    t = torch_bn_fp32(x, gamma, beta, resid, dout, relu)
+    f = R.bn_fwd_ref(x, gamma, beta, resid, relu)
+    mask = R.bn_act_mask(t["out"], relu)
+    dy, dg, db, _ = R.bn_bwd_ref(f, gamma, dout, mask, True)
+    if n * h * w > R.BN_DBL_ROWS:                      # the kernel adds fp32 runs: the sequential-fp32 restatement is the floor
+        nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous()
+        b = dict(y=nhwc(x), mean=f["mean"].float(), invstd=(1.0 / torch.sqrt(f["var"] + R.BN_EPS)).float())
+        s0, s1 = bwd_sums(nhwc(dout), nhwc(mask).float(), b, torch.float32)
+        t["dbeta"], t["dgamma"] = s0, s1
+    figs = {k: rel_err(t[k], v) for k, v in (("out", f["out"]), ("dy", dy), ("dgamma", dg), ("dbeta", db))}
+    return figs, dict(f=f, dy=dy, dgamma=dg, dbeta=db, mask=mask, dout=dout, gamma=gamma, resid=resid, relu=relu)
+
+
+def bn2_floor_given(inputs, relu, res):
+    """res: None, "exact" or "bf16" (the residual as a one-plane tensor holds it)"""
+    x, gamma, beta, resid, dout, mean, invstd = inputs
+    resid = None if res is None else (R.bf16_rne(resid) if res == "bf16" else resid)
+    var = R.given_var(invstd)
+    t = torch_bn_fp32(x, gamma, beta, resid, dout, relu, mean, var.float())
+    f = R.bn_fwd_ref(x, gamma, beta, resid, relu, mean, var)
+    mask = R.bn_act_mask(t["out"], relu)
+    dy_eval, dg, db, _ = R.bn_bwd_ref(f, gamma, dout, mask, False)
+    dy = R.bn_bwd_ref(f, gamma, dout, mask, True)[0]
+    dy32 = R.bn_dy_train_fp32(x, mean, invstd, gamma, dout * mask, dg, db)
+    figs = dict(out=rel_err(t["out"], f["out"]), dy_eval=rel_err(t["dy"], dy_eval), dy=rel_err(dy32, dy),
+                dgamma=rel_err(t["dgamma"], dg), dbeta=rel_err(t["dbeta"], db))
+    return figs, dict(f=f, dy=dy, dy_eval=dy_eval, dgamma=dg, dbeta=db, mask=mask, dout=dout, gamma=gamma, resid=resid, relu=relu)
+
+
+def bn2_walk_inputs(wid):
+    return R.bn2_given_inputs((1, R.BN2_WALK_C, 1, R.BN2_WALK[wid]))
+
+
+def bn2_fallback_inputs(fid):
+    n, h, w = R.BN2_FALLBACK_ROWS
+    return R.bn2_given_inputs((n, R.BN2_FALLBACK[fid][0], h, w))
+
+
+@functools.lru_cache(maxsize=None)
+def bn2_measured():
+    """({floor key: figure}, {check tag: the float64 results the mutants are applied to})"""
+    m, refs = {}, {}
+    with one_thread():
+        for cid in R.BN2_BATCH:
+            for rounded in ((False, True) if cid == "cols2_pl" else (False,)):
+                figs, ref = bn2_floor_batch(cid, rounded)
+                for k, v in figs.items():
+                    put(m, "bn2.%s.%s" % (k, cid), v)
+                refs[cid + ("/bf16res" if rounded else "")] = ref
+        for wid in R.BN2_WALK:
+            for res in (("exact", "bf16") if wid == "walk33" else ("exact",)):
+                figs, ref = bn2_floor_given(bn2_walk_inputs(wid), True, res)
+                for k, v in figs.items():
+                    put(m, "bn2.%s.%s" % (k, wid), v)
+                refs["%s/%s" % (wid, res)] = ref
+        for fid in R.BN2_FALLBACK:
+            for res in ("exact", "bf16"):
+                figs, ref = bn2_floor_given(bn2_fallback_inputs(fid), True, res)
+                for k, v in figs.items():
+                    put(m, "bn2.%s.%s" % (k, R.fallback_tag(fid)), v)
+                refs["%s/%s/%s" % (R.fallback_tag(fid), fid, res)] = ref
+        grid = R.bn2_given_inputs(R.BN2_GRID_SHAPE, 8)
+        for relu in R.BN2_RELUS:
+            for res in (None, "exact", "bf16"):
+                figs, ref = bn2_floor_given(grid, relu, res)
+                for k, v in figs.items():
+                    put(m, "bn2.%s.%s" % (k, R.grid_tag(relu, res)), v)
+                refs["%s/%s" % (R.grid_tag(relu, res), res)] = ref
+    return m, refs
+
+
+def test_floors_bn2():
+    check_floors(bn2_measured()[0])
+
+
+def bn2_key(tag, quantity):
+    return "bn2.%s.%s" % (quantity, tag.split("/")[0])
+
+
+def test_bn2_store_mutants():
+    """every float check of a bn2 store (out, dy, dgamma, dbeta) against the faults a store can have, on the restatement alone; each
+    must miss its assertion by >= 3 x the bound (12 x floor):
+      - an element left at the buffer's initial value (a dropped last row, the tail row of a pair walk, an unprocessed second
+        column block): every buffer starts at SENTINEL in every plane, so the joined value is SENTINEL or 3 x SENTINEL;
+      - the lo or the mid plane of a stored output or of dy dropped;
+      - a one-plane store by truncation: the check is bit equality with round-to-nearest-even, so one differing element is a miss"""
+    _, refs = bn2_measured()
+    for tag, r in refs.items():
+        for q in ("out", "dy", "dy_eval", "dgamma", "dbeta"):
+            ref = r["f"]["out"] if q == "out" else r.get(q)
+            if ref is None:
+                continue
+            need = 12 * R.FLOOR[bn2_key(tag, q)]
+            scale = float(ref.abs().max())
+            for s in (R.SENTINEL, 3 * R.SENTINEL):
+                assert float((ref - s).abs().min()) / scale >= need, (tag, q, s)
+            if q in ("out", "dy", "dy_eval"):
+                hi, mid, lo = R.split3(ref.float())
+                assert float(lo.abs().max()) / scale >= need and float(mid.abs().max()) / scale >= need, (tag, q)
+                assert not torch.equal(R.bf16_trunc(ref.float()), R.bf16_rne(ref.float())), (tag, q)
+
+
+def test_bn2_residual_plane_mutants():
+    """the lo or the mid plane of a three-plane residual not read: out moves by that plane wherever the activation passes"""
+    _, refs = bn2_measured()
+    seen = 0
+    for tag, r in refs.items():
+        if r["resid"] is None or "bf16" in tag:
+            continue
+        f = r["f"]
+        need = 12 * R.FLOOR[bn2_key(tag, "out")]
+        for plane in R.split3(r["resid"])[1:]:
+            err = rel_err(R.bn_act(f["z"] - plane.double(), r["relu"]), f["out"])
+            assert err >= need, (tag, err, need)
+        seen += 1
+    assert seen >= 10
+
+
+def bn2_sum_errors(r, tag, drop):
+    """(dgamma, dbeta, dy) errors over their bounds when the NHWC rows x channels of `drop` (a bool [M, C] mask) are missing from
+    the sums of the backward"""
+    f = r["f"]
+    dz = (r["dout"].double() * r["mask"].double())
+    c = dz.shape[1]
+    keep = (~drop).t().double()                                      # [C, M]; M runs over (n, h, w) as the NHWC rows do
+    dzr, xh = dz.permute(1, 0, 2, 3).reshape(c, -1), f["xhat"].permute(1, 0, 2, 3).reshape(c, -1)
+    db, dg = (dzr * keep).sum(1), (dzr * xh * keep).sum(1)
+    m = dzr.shape[1]
+    k = (r["gamma"].double() / torch.sqrt(f["var"] + R.BN_EPS))[None, :, None, None]
+    dy = k * (dz - db[None, :, None, None] / m - f["xhat"] * dg[None, :, None, None] / m)
+    return (rel_err(dg, r["dgamma"]) / (4 * R.FLOOR[bn2_key(tag, "dgamma")]), rel_err(db, r["dbeta"]) / (4 * R.FLOOR[bn2_key(tag, "dbeta")]),
+            rel_err(dy, r["dy"]) / (4 * R.FLOOR[bn2_key(tag, "dy")]))
+
+
+BN2_SUM_MUTANT_TAGS = list(R.BN2_BATCH) + ["%s/exact" % w for w in R.BN2_WALK] + [
+    "%s/%s/exact" % (R.fallback_tag(f), f) for f in ("c12", "off4")] + [
+    "%s/%s" % (R.grid_tag(relu, res), res) for relu in R.BN2_RELUS for res in (None, "exact")]
+
+
+@pytest.mark.parametrize("tag", BN2_SUM_MUTANT_TAGS)
+def test_bn2_sum_mutants(tag):
+    """faults of the reduce pass, on the restatement alone, for every case whose dgamma / dbeta / dy is checked (the batch cases,
+    the walks, both fallback channel counts, the grid per activation with and without a residual); dgamma, dbeta AND dy must each
+    miss by >= 3 x their bound:
+      - the last row of one thread's walk is not added;
+      - one whole run of 8 rows of one thread is missing (where a thread has a run);
+      - tilecap: the partial of one block goes to another block's slot.  A block is blockIdx.x of a strided walk (gridDim.x ==
+        tiles == 1024, rows b * RL + lane + k * 1024 * RL), and the finalize sums slots 0 .. tiles - 1: if block 1023 writes slot
+        1022, the finalize reads block 1023's sums once, never block 1022's, and slot 1023 keeps the workspace's zeros -- all rows
+        of block 1022 are missing;
+      - the second column block is not reduced: its sums stay at SENTINEL (test_bn2_store_mutants)"""
+    _, refs = bn2_measured()
+    r = refs[tag]
+    m, c = r["dout"].numel() // r["dout"].shape[1], r["dout"].shape[1]
+    s = R.reduce_structure(m, c)
+    block, lane, group = s["tiles"] // 2, s["plan"]["RL"] - 1, s["plan"]["C4"] - 1
+    rows = R.walk(m, s["plan"], block, lane)
+    if not rows:
+        block, lane = 0, 0
+        rows = R.walk(m, s["plan"], block, lane)
+    muts = {"last_row": rows[-1:]}
+    if len(rows) >= R.BN_RUN:
+        muts["run"] = rows[:R.BN_RUN]
+    for name, rr in muts.items():
+        drop = torch.zeros(m, c, dtype=torch.bool)
+        drop[rr, 4 * group:4 * group + 4] = True
+        errs = bn2_sum_errors(r, tag, drop)
+        print(tag, name, "miss / bound: dgamma %.1f dbeta %.1f dy %.1f" % errs)
+        assert min(errs) >= 3, (tag, name, errs)
+    if tag == "tilecap":
+        lost = sorted(q for lane in range(s["plan"]["RL"]) for q in R.walk(m, s["plan"], s["tiles"] - 2, lane))
+        assert len(lost) == 32 and lost[-1] - lost[0] > 28000                       # 4 lanes x 8 strided rows, no block of 32 rows
+        drop = torch.zeros(m, c, dtype=torch.bool)
+        drop[lost] = True
+        errs = bn2_sum_errors(r, tag, drop)
+        print(tag, "block 1023 into slot 1022: miss / bound: dgamma %.1f dbeta %.1f dy %.1f" % errs)
+        assert min(errs) >= 3, errs
+
+
+def test_planes_pool_resize_mutants():
+    """the float checks of the pooling / resize passes on Planes (gap.fwd read through ld4x, bilinear.fwd stored through st4x) with
+    the lo or the mid plane lost, on the restatement alone, at every shape of the GPU tests: >= 3 x the bound"""
+    for c in (48, 304):
+        for hw in ((1, 7), (33, 33)):
+            x = R.pool_inputs(3, hw, c)
+            want = x.double().mean((1, 2))
+            for name, plane in zip(("mid", "lo"), R.split3(x)[1:]):
+                err = rel_err((x.double() - plane.double()).mean((1, 2)), want)
+                print("gap.fwd hw %d c %d without %s: %.2e (bound %.1e)" % (hw[0] * hw[1], c, name, err, 4 * R.FLOOR["gap.fwd"]))
+                assert err >= 12 * R.FLOOR["gap.fwd"], (hw, c, name, err)
+    for shape in R.RESIZE_SMALLEST + [R.RESIZE_SHAPES[1]]:
+        x, _ = R.resize_inputs(shape, 48)
+        ref = R.bilinear_fwd_ref(x, *shape[1])
+        for name, plane in zip(("mid", "lo"), R.split3(ref.float())[1:]):
+            err = rel_err(ref - plane.double(), ref)
+            print("bilinear.fwd %s without %s: %.2e" % (shape, name, err))
+            assert err >= 12 * R.FLOOR["bilinear.fwd"], (shape, name, err)
+        assert not torch.equal(R.bf16_trunc(ref.float()), R.bf16_rne(ref.float()))          # one plane: truncation is not the rounding
+
+
+@pytest.mark.parametrize("res", [None, "exact"])
+def test_bn2_pattern_mutants(res):
+    """the ReLU6 pattern read from the wrong value, on the grid's planted values in the bf16 ulp below 6.  Three planes: the
+    pattern is that of the hi plane (truncation: the same as the fp32 value's); a read of the value rounded to nearest sees 6.0
+    there.  One plane: the pattern is that of the STORED value, which is the rounded one; a truncating read sees 5.96875.  dres is
+    held to equality, dy to its bound"""
+    _, refs = bn2_measured()
+    r = refs["%s/%s" % (R.grid_tag(6, res), res)]
+    f = r["f"]
+    out32 = f["out"].float()
+    right3, wrong3 = R.bn_act_mask(R.bf16_trunc(out32), 6), R.bn_act_mask(R.bf16_rne(out32), 6)
+    assert torch.equal(right3, R.bn_act_mask(out32, 6))
+    right1, wrong1 = wrong3, right3
+    for right, wrong in ((right3, wrong3), (right1, wrong1)):
+        diff = (right != wrong) & (r["dout"] != 0)
+        assert int(diff.sum()) >= 8
+        for training, q in ((True, "dy"), (False, "dy_eval")):
+            a = R.bn_bwd_ref(f, r["gamma"], r["dout"], wrong, training)[0]
+            b = R.bn_bwd_ref(f, r["gamma"], r["dout"], right, training)[0]
+            assert rel_err(a, b) >= 12 * R.FLOOR["bn2.%s.%s" % (q, R.grid_tag(6, res))]
