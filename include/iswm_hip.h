@@ -498,6 +498,32 @@ int iswm_predict_maps(const float* yl, int N, int Hi, int Wi, int ldx, int C, in
                       int band_lo, int band_hi, unsigned char* pred, unsigned char* conf, unsigned char* band,
                       float* prob, double* stats, void* workspace, size_t workspace_bytes, iswm_stream_t stream);
 
+/* ---- sliding-window prediction of whole scenes (predict.hip) -------------------------------
+ * A scene of H x W is predicted in nty x ntx windows of th x tw and the overlaps are blended.
+ * scene_plan_make (pure host): per axis of length L, t = min(tile, L); one window when L <= t, else windows every
+ * s = t - overlap, n = ceil((L - t) / s) + 1 of them, window k starting at min(k * s, L - t).  Needs tile >= 1,
+ * 0 <= overlap <= 1024 and overlap <= t / 2 on an axis with more than one window.  ramp = max(overlap, 1); an axis
+ * with one window has s = t.  Windows are numbered k = ty * ntx + tx.
+ * scene_tiles_normalize: uint8 HWC RGB scene [H][W][3] -> windows first_tile .. first_tile + count - 1 as fp32 NCHW
+ * [count][3][th][tw], iswm_predict_normalize's arithmetic.  mean3 / std3 are HOST arrays of 3 floats.
+ * scene_maps: the low-resolution NHWC logits of ALL windows yl [nty * ntx][Hi][Wi][ldx] -> the maps of
+ * iswm_predict_maps for the one [H][W] scene.  Per pixel, over the windows that cover it (ascending ty, then tx):
+ * p_t = iswm_predict_maps's probability at the in-window coordinate, w_t = w1d(y - oy, th) * w1d(x - ox, tw) with
+ * w1d(i, len) = min(i + 1, len - i, ramp), p = min(sum_t fma(w_t / sum w, p_t), 1).  A gather: no canvas, no
+ * atomics, bit-reproducible; a pixel under one window gets that window's p_t exactly, and a plan of one window is
+ run as iswm_predict_maps (the same bytes for every C).  Outputs, stats [5] and
+ * alignment as iswm_predict_maps with N = 1; workspace: iswm_scene_maps_workspace. */
+typedef struct iswm_scene_plan {
+    int H, W, th, tw, sy, sx, nty, ntx, ramp;
+} iswm_scene_plan;
+int iswm_scene_plan_make(int H, int W, int tile, int overlap, iswm_scene_plan* out);
+int iswm_scene_tiles_normalize(const unsigned char* scene, const iswm_scene_plan* plan, int first_tile, int count,
+                               const float* mean3, const float* std3, float* out_nchw, iswm_stream_t stream);
+size_t iswm_scene_maps_workspace(int H, int W);
+int iswm_scene_maps(const float* yl, const iswm_scene_plan* plan, int Hi, int Wi, int ldx, int C, int fg, float thr,
+                    int band_lo, int band_hi, unsigned char* pred, unsigned char* conf, unsigned char* band,
+                    float* prob, double* stats, void* workspace, size_t workspace_bytes, iswm_stream_t stream);
+
 /* ---- INT8 post-training quantized inference (qconv.hip, quant.hip) ----------------------
  * Activations are int8 NHWC with a pixel pitch in bytes; one symmetric scale s per tensor (value = q * s).
  * qconv: implicit-GEMM convolution on v_mfma_i32_16x16x64_i8, forward only.  x int8 [N][H][W][ldx] (first Cin

@@ -24,6 +24,25 @@ class QConvDesc(Structure):
                                      "dil", "ldx", "ldy", "ldr", "relu", "lo", "out_f32", "cstore")]
 
 
+class ScenePlan(Structure):
+    """iswm_scene_plan: nty x ntx windows of th x tw every (sy, sx) pixels over an H x W scene, the last window of an
+    axis pulled back inside it; ramp = the blending ramp.  Windows are numbered k = ty * ntx + tx."""
+    _fields_ = [(n, c_int) for n in ("H", "W", "th", "tw", "sy", "sx", "nty", "ntx", "ramp")]
+
+    @property
+    def ntiles(self):
+        return self.nty * self.ntx
+
+    def origins_y(self):
+        return [min(k * self.sy, self.H - self.th) for k in range(self.nty)]
+
+    def origins_x(self):
+        return [min(k * self.sx, self.W - self.tw) for k in range(self.ntx)]
+
+    def astuple(self):
+        return tuple(getattr(self, n) for n, _ in self._fields_)
+
+
 P = c_void_p
 _SIGS = {
     # name: (restype, [argtypes])
@@ -151,6 +170,11 @@ _SIGS = {
     "iswm_predict_maps_workspace": (c_size_t, [c_int, c_int, c_int]),
     "iswm_predict_maps": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P, P,
                                   P, P, P, P, c_size_t, P]),
+    "iswm_scene_plan_make": (c_int, [c_int, c_int, c_int, c_int, POINTER(ScenePlan)]),
+    "iswm_scene_tiles_normalize": (c_int, [P, POINTER(ScenePlan), c_int, c_int, POINTER(c_float), POINTER(c_float), P, P]),
+    "iswm_scene_maps_workspace": (c_size_t, [c_int, c_int]),
+    "iswm_scene_maps": (c_int, [P, POINTER(ScenePlan), c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P, P, P, P,
+                                P, P, c_size_t, P]),
     "iswm_qconv_weight_bytes": (c_size_t, [POINTER(QConvDesc)]),
     "iswm_qconv_fwd": (c_int, [POINTER(QConvDesc), P, P, P, P, P, c_double, c_double, P, P]),
     "iswm_absmax_workspace": (c_size_t, [c_int64, c_int]),

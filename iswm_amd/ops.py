@@ -1222,6 +1222,59 @@ def predict_maps(yl, num_classes, fg, H, W, thr, min_prob, max_prob, want_prob=F
     return PredictMaps((pred, conf, band, prob, stats, packed))
 
 
+def scene_plan(H, W, tile, overlap):
+    """the sliding-window plan of an H x W scene (iswm_scene_plan_make, a pure host function): a _lib.ScenePlan.
+    Raises IswmError for tile < 1, overlap outside [0, 1024] or above half a window"""
+    plan = _lib.ScenePlan()
+    call("iswm_scene_plan_make", int(H), int(W), int(tile), int(overlap), ctypes.byref(plan))
+    return plan
+
+
+def scene_tiles_normalize(scene_u8, plan, first, count, mean, std):
+    """windows first .. first + count - 1 of a uint8 [H, W, 3] RGB scene on the device -> normalised fp32 NCHW
+    [count, 3, th, tw], bit-identical to predict_normalize of the cropped windows"""
+    if scene_u8.dim() != 3 or scene_u8.shape[2] != 3 or scene_u8.dtype != torch.uint8 or not scene_u8.is_cuda:
+        raise ValueError("expected a uint8 CUDA [H, W, 3] scene, got %s %s" % (tuple(scene_u8.shape), scene_u8.dtype))
+    if tuple(scene_u8.shape[:2]) != (plan.H, plan.W):
+        raise ValueError("scene %s does not match the plan's %d x %d" % (tuple(scene_u8.shape), plan.H, plan.W))
+    if first < 0 or count < 1 or first + count > plan.ntiles:
+        raise ValueError("windows [%d, %d) outside the plan's %d" % (first, first + count, plan.ntiles))
+    scene_u8 = scene_u8.contiguous()
+    out = torch.empty((count, 3, plan.th, plan.tw), dtype=torch.float32, device=scene_u8.device)
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    call("iswm_scene_tiles_normalize", _p(scene_u8), ctypes.byref(plan), int(first), int(count), m, s, _p(out),
+         _stream())
+    return out
+
+
+def scene_maps(yl_tiles, num_classes, fg, plan, thr, min_prob, max_prob, want_prob=False):
+    """low-resolution NHWC logits of all windows of one scene [plan.ntiles, hl, wl, ld] -> PredictMaps at
+    [1, H, W]: every pixel blends the windows that cover it (a gather; weights ramp over the overlap), then
+    predict_maps's outputs.  A scene of one window gives predict_maps's bytes.  Enqueues only."""
+    yl = as_f32(yl_tiles)
+    n, hl, wl, c, ld = geom(yl)
+    if n != plan.ntiles:
+        raise ValueError("logits %s do not hold the plan's %d windows" % (tuple(yl.shape), plan.ntiles))
+    if ld % 4 or ld < (num_classes + 3) // 4 * 4 or num_classes > c:
+        raise ValueError("logits %s (pitch %d) do not hold %d classes" % (tuple(yl.shape), ld, num_classes))
+    if not 0 <= fg < num_classes:
+        raise ValueError("foreground class %d outside [0, %d)" % (fg, num_classes))
+    dev = yl.device
+    H, W = plan.H, plan.W
+    lay = predict_maps_layout(1, H, W)
+    packed = torch.empty(lay["end"], dtype=torch.uint8, device=dev)
+    stats = packed[:40].view(torch.float64).view(1, 5)
+    pred, conf, band = (packed[lay[k]:lay[k] + H * W].view(1, H, W) for k in ("pred", "conf", "band"))
+    prob = torch.empty((1, H, W), dtype=torch.float32, device=dev) if want_prob else None
+    lo, hi = band_bounds(min_prob, max_prob)
+    nbytes = _lib.load().iswm_scene_maps_workspace(H, W)
+    ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=dev)
+    call("iswm_scene_maps", _p(yl), ctypes.byref(plan), hl, wl, ld, int(num_classes), int(fg), float(thr), lo, hi,
+         _p(pred), _p(conf), _p(band), _p(prob), _p(stats), _p(ws), nbytes, _stream())
+    return PredictMaps((pred, conf, band, prob, stats, packed))
+
+
 def sgd_step(p, g, buf, lr_dev, momentum, weight_decay, nesterov):
     call("iswm_sgd_step", _p(p), _p(g), _p(buf), p.numel(), _p(lr_dev), float(momentum), float(weight_decay),
          int(bool(nesterov)), _stream())

@@ -1,7 +1,7 @@
 """Inference entry point -- runnable counterpart of the reference's predict.py.
 
     python -m iswm_amd.predict --input <dir> --ckpt <checkpoint> --save_val_results_to <out> \\
-        [--save_confidence] [--save_binary] [--batch_size B] [--workers W]
+        [--save_confidence] [--save_binary] [--batch_size B] [--workers W] [--tile_size T [--tile_overlap O]]
 
 Every subfolder of ``--input`` is walked (process_images, predict.py:292-368) and each frame gets
 ``<out>/<subfolder>/<name>_predict.png`` (0/255 foreground mask), plus ``_confidence.png`` (uint8(p * 255), p = the
@@ -19,6 +19,11 @@ Same flags and defaults as the reference's get_argparser (predict.py:19-67).  Di
     CUDA_VISIBLE_DEVICES;
   * new ``--batch_size`` (default 1): consecutive frames of one subfolder with the same size share a batch;
   * new ``--workers`` (default 4): host threads for PNG decoding and encoding;
+  * new ``--tile_size T`` (default 0: every frame goes through the network whole) and ``--tile_overlap O`` (default
+    -1: T // 8): a frame larger than T is predicted in T x T windows every T - O pixels, the last window of each axis
+    pulled back inside the frame, and the overlaps are blended with weights that ramp over O pixels (ScenePredictor;
+    DESIGN.md section 13).  ``--batch_size`` then counts windows per device batch and frames are handed over one at
+    a time.  A frame no larger than T is one window and gives the whole-frame path's bytes;
   * ``--binary_threshold`` is accepted and unused, as in the reference (predict.py:223);
   * ``--enable_wave_processing`` is refused: its synthetic "broken area" generator is random and draws with
     OpenCV, which is not a dependency here.  Its flags still parse;
@@ -98,7 +103,27 @@ def get_argparser():
     parser.add_argument("--batch_size", type=int, default=1,
                         help="frames per device batch (consecutive frames of one subfolder with the same size)")
     parser.add_argument("--workers", type=int, default=4, help="host threads for PNG decoding and encoding")
+    parser.add_argument("--tile_size", type=int, default=0,
+                        help="predict frames in windows of this size and blend the overlaps (0: whole frames); "
+                             "--batch_size then counts windows per device batch")
+    parser.add_argument("--tile_overlap", type=int, default=-1,
+                        help="overlap of neighbouring windows in pixels (default: tile_size // 8)")
     return parser
+
+
+def tile_options(parser, opts):
+    """(tile_size, tile_overlap) with the default overlap filled in; bad combinations are argparse errors"""
+    if opts.tile_size < 0:
+        parser.error("--tile_size %d must not be negative" % opts.tile_size)
+    if opts.tile_size == 0:
+        if opts.tile_overlap != -1:
+            parser.error("--tile_overlap %d needs --tile_size" % opts.tile_overlap)
+        return 0, 0
+    overlap = opts.tile_size // 8 if opts.tile_overlap == -1 else opts.tile_overlap
+    if overlap < 0 or overlap > 1024 or overlap > opts.tile_size // 2:
+        parser.error("--tile_overlap %d must lie in [0, min(1024, tile_size // 2 = %d)] for --tile_size %d" %
+                     (overlap, opts.tile_size // 2, opts.tile_size))
+    return opts.tile_size, overlap
 
 
 def list_subdirs(input_base_path):
@@ -294,6 +319,56 @@ class DevicePredictor:
         return wait
 
 
+class ScenePredictor:
+    """predict_batch for process_images over frames larger than the training crops: per frame, one upload, then
+    ops.scene_tiles_normalize -> forward_lowres per batch of windows into one logits buffer, ops.scene_maps over all
+    windows, and one copy of stats + the requested maps into pinned host memory.  Nothing synchronises before wait()."""
+
+    def __init__(self, model, device, num_classes, fg, pred_threshold, min_prob, max_prob, want_conf, want_band,
+                 tile_size, tile_overlap, tile_batch=1):
+        self.model, self.device = model, device
+        self.num_classes, self.fg = num_classes, fg
+        self.thr, self.min_prob, self.max_prob = pred_threshold, min_prob, max_prob
+        self.want_conf, self.want_band = want_conf, want_band
+        self.tile_size, self.tile_overlap, self.tile_batch = int(tile_size), int(tile_overlap), max(1, int(tile_batch))
+
+    def __call__(self, batch):
+        import torch
+        from . import ops
+        n, h, w, _ = batch.shape
+        plan = ops.scene_plan(h, w, self.tile_size, self.tile_overlap)
+        lay = ops.predict_maps_layout(1, h, w)
+        end = lay["band"] + h * w if self.want_band else lay["conf"] + h * w if self.want_conf else lay["pred"] + h * w
+        pin = torch.from_numpy(np.ascontiguousarray(batch)).pin_memory()
+        host = torch.empty((n, end), dtype=torch.uint8, pin_memory=True)
+        with torch.cuda.device(self.device), torch.no_grad():
+            for f in range(n):
+                scene = pin[f].to(self.device, non_blocking=True)
+                logits = None
+                for k0 in range(0, plan.ntiles, self.tile_batch):
+                    count = min(self.tile_batch, plan.ntiles - k0)
+                    yl = self.model.forward_lowres(ops.scene_tiles_normalize(scene, plan, k0, count, MEAN, STD))
+                    if count == plan.ntiles:
+                        logits = yl
+                        break
+                    if logits is None:      # sized once the first batch shows the low-resolution shape and pitch
+                        logits = torch.empty((plan.ntiles,) + tuple(yl.shape[1:]), dtype=yl.dtype, device=yl.device)
+                    logits[k0:k0 + count].copy_(yl)
+                maps = ops.scene_maps(logits, self.num_classes, self.fg, plan, self.thr, self.min_prob, self.max_prob)
+                host[f].copy_(maps.packed[:end], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+
+        def wait():
+            ev.synchronize()
+            a = host.numpy()
+            stats = np.ascontiguousarray(a[:, :40]).view(np.float64).reshape(n, 5)
+            pick = (lambda k: a[:, lay[k]:lay[k] + h * w].reshape(n, h, w))
+            return {"pred": pick("pred"), "conf": pick("conf") if self.want_conf else None,
+                    "band": pick("band") if self.want_band else None, "stats": stats}
+        return wait
+
+
 def load_model(model, ckpt_path, ck=None):
     """predict.py:80-91 with the weights-only loader: {"model_state": ...} (this project's and the reference's
     checkpoints) or a bare state dict, `module.` prefixes stripped, strict load.  No file: initial weights.
@@ -312,7 +387,9 @@ def load_model(model, ckpt_path, ck=None):
 
 
 def main(argv=None):
-    opts = get_argparser().parse_args(argv)
+    parser = get_argparser()
+    opts = parser.parse_args(argv)
+    tile_size, tile_overlap = tile_options(parser, opts)
     if opts.enable_wave_processing:
         get_argparser().error(WAVE_PROCESSING_REFUSED)
     if opts.batch_size < 1 or opts.workers < 1:
@@ -338,10 +415,17 @@ def main(argv=None):
         model = load_model(model, opts.ckpt, ck).to(device)
     model.eval()
 
-    predictor = DevicePredictor(model, device, num_classes, fg, opts.pred_threshold, opts.min_broken_prob,
-                                opts.max_broken_prob, opts.save_confidence, opts.save_binary)
+    if tile_size > 0:                            # windows share a device batch; frames go one at a time
+        predictor = ScenePredictor(model, device, num_classes, fg, opts.pred_threshold, opts.min_broken_prob,
+                                   opts.max_broken_prob, opts.save_confidence, opts.save_binary, tile_size,
+                                   tile_overlap, tile_batch=opts.batch_size)
+        frames = 1
+    else:
+        predictor = DevicePredictor(model, device, num_classes, fg, opts.pred_threshold, opts.min_broken_prob,
+                                    opts.max_broken_prob, opts.save_confidence, opts.save_binary)
+        frames = opts.batch_size
     return process_images(opts.input, opts.save_val_results_to, predictor, opts.save_confidence, opts.save_binary,
-                          pred_threshold=opts.pred_threshold, batch_size=opts.batch_size, workers=opts.workers)
+                          pred_threshold=opts.pred_threshold, batch_size=frames, workers=opts.workers)
 
 
 if __name__ == "__main__":
