@@ -2,7 +2,8 @@
 // the row -> pixel maps, the weight packing of the planes kernels, the tile choices and launch entry points of every family
 // -- conv_mfma.hip (fp32 kernels), conv_mfma_u.hip (tap-uniform fast path), conv_mfma_x6*.hip (round-1 bf16x6),
 // conv_mfma_pl2*.hip (planes kernels; their device-side pieces are in conv_pl2_stage.h), conv_stem.hip, conv_wgrad_pl.hip
-// (planes weight gradient) -- and the weight-gradient plan.  conv_api.hip is the host-only file over them: the C entry
+// (planes weight gradient; conv_wgrad_frag.h holds the fragment read and multiply it shares with the stem's weight gradient)
+// -- and the weight-gradient plan.  conv_api.hip is the host-only file over them: the C entry
 // points, the conv-math state and the route planner that decides, once per call, which family and tile a geometry gets.
 #pragma once
 #include <stdlib.h>

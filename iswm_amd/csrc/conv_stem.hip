@@ -17,7 +17,7 @@
 // builds them itself from the OHWI fp32 parameter (no pack launch), and are read once per kernel row for all the wave's pixels.
 // One wave = RB row blocks of 16 output pixels x 64 channels; 8 waves per workgroup walk the wave-tiles round-robin.
 // Epilogue: lane = pixel, 4 registers = 4 consecutive channels -> float4 stores; BatchNorm partials per wave-tile (centred).
-#include "conv_common.h"
+#include "conv_wgrad_frag.h"
 
 namespace iswm {
 
@@ -270,17 +270,11 @@ __global__ __launch_bounds__(512) void k_stem_wgrad(const ConvArgs a, float* __r
         }
     };
 
-    // fragment reader of k_wgrad_pls: 32 channels [col0, col0 + 32) x the stage's 16 pixels -> the 32x32x16 operand
+    // fragment reader of k_wgrad_pls (conv_wgrad_frag.h): 32 channels [col0, col0 + 32) x the stage's 16 pixels -> the 32x32x16 operand
     const int tg = lane >> 4, ti = lane & 15, tq = ti >> 2, tp = ti & 3;
     const int th = tg >> 1, tc = (tg & 1) * 16 + tp * 4;
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
     auto tr_frag = [&](const unsigned char* plane, int col0) __attribute__((always_inline)) -> uint4 {
-        const unsigned char* q = plane + (th * 8 + tq) * 256 + (((col0 + tc) * 2) ^ (tq * 64));
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(q));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(q + 4 * 256));
-        uint2 a2 = __builtin_bit_cast(uint2, lo), b2 = __builtin_bit_cast(uint2, hi);
-        return make_uint4(a2.x, a2.y, b2.x, b2.y);
+        return wg_tr_frag(plane + (th * 8 + tq) * 256 + (((col0 + tc) * 2) ^ (tq * 64)));
     };
     const int kh_w = wave;                                    // this wave's kernel row (wave 7 only fetches)
     const int bimg = kh_w < 2 ? 0 : (kh_w < 6 ? 1 : 2);
@@ -309,16 +303,7 @@ __global__ __launch_bounds__(512) void k_stem_wgrad(const ConvArgs a, float* __r
                 FA[1][pl] = tr_frag(st + pl * SW_PLANE, 32);
             }
 #pragma unroll
-            for (int mb = 0; mb < 2; ++mb) {
-                f32x16 c = acc[mb];
-                c = mfma_bf16(FA[mb][2], FB[0], c);     // smallest terms first
-                c = mfma_bf16(FA[mb][0], FB[2], c);
-                c = mfma_bf16(FA[mb][1], FB[1], c);
-                c = mfma_bf16(FA[mb][1], FB[0], c);
-                c = mfma_bf16(FA[mb][0], FB[1], c);
-                c = mfma_bf16(FA[mb][0], FB[0], c);
-                acc[mb] = c;
-            }
+            for (int mb = 0; mb < 2; ++mb) wg_mul<3>(acc[mb], FA[mb], FB);
         }
         if (s2 + 1 < nK) store(buf ^ 1);
         __syncthreads();

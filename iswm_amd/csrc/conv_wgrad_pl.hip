@@ -17,7 +17,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "conv_common.h"
+#include "conv_wgrad_frag.h"
 
 namespace iswm {
 
@@ -149,14 +149,8 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pl(const WgArgs a) {
     // 16 * (g & 1).. of the 32-row MFMA block for k half g >> 1; lane 4q + p of the group addresses k-row q, columns 4p..
     const int tg = lane >> 4, ti = lane & 15, tq = ti >> 2, tp = ti & 3;
     const int th = tg >> 1, tc = (tg & 1) * 16 + tp * 4;
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
     auto tr_frag = [&](const unsigned char* plane, int col0) __attribute__((always_inline)) -> uint4 {
-        const unsigned char* p = plane + (kh * 16 + th * 8 + tq) * 256 + (((col0 + tc) * 2) ^ (tq * 64));
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p + 4 * 256));
-        uint2 a2 = __builtin_bit_cast(uint2, lo), b2 = __builtin_bit_cast(uint2, hi);
-        return make_uint4(a2.x, a2.y, b2.x, b2.y);
+        return wg_tr_frag(plane + (kh * 16 + th * 8 + tq) * 256 + (((col0 + tc) * 2) ^ (tq * 64)));
     };
 
     f32x16 acc[2][2];
@@ -182,18 +176,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pl(const WgArgs a) {
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                f32x16 c = acc[mb][nb];
-                if constexpr (NP == 3) {
-                    c = mfma_bf16(af[mb][2], bf[nb][0], c);     // smallest terms first
-                    c = mfma_bf16(af[mb][0], bf[nb][2], c);
-                    c = mfma_bf16(af[mb][1], bf[nb][1], c);
-                    c = mfma_bf16(af[mb][1], bf[nb][0], c);
-                    c = mfma_bf16(af[mb][0], bf[nb][1], c);
-                }
-                c = mfma_bf16(af[mb][0], bf[nb][0], c);
-                acc[mb][nb] = c;
-            }
+            for (int nb = 0; nb < 2; ++nb) wg_mul<NP>(acc[mb][nb], af[mb], bf[nb]);
     };
 
     {
@@ -384,14 +367,8 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_plw(const WgArgs a) {
 
     const int tg = lane >> 4, ti = lane & 15, tq = ti >> 2, tp = ti & 3;
     const int th = tg >> 1, tc = (tg & 1) * 16 + tp * 4;
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
     auto tr_frag = [&](const unsigned char* plane, int ks, int col0) __attribute__((always_inline)) -> uint4 {
-        const unsigned char* p = plane + (ks * 16 + th * 8 + tq) * 256 + (((col0 + tc) * 2) ^ (tq * 64));
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p + 4 * 256));
-        uint2 a2 = __builtin_bit_cast(uint2, lo), b2 = __builtin_bit_cast(uint2, hi);
-        return make_uint4(a2.x, a2.y, b2.x, b2.y);
+        return wg_tr_frag(plane + (ks * 16 + th * 8 + tq) * 256 + (((col0 + tc) * 2) ^ (tq * 64)));
     };
 
     f32x16 acc[2][2];
@@ -417,18 +394,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_plw(const WgArgs a) {
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl) F[2 + nb][pl] = tr_frag(Bx + pl * PLANE, ks, (wn & 1) * 64 + nb * 32);
     };
-    auto mm = [&](int mb, int nb) __attribute__((always_inline)) {
-        f32x16 c = acc[mb][nb];
-        if constexpr (NP == 3) {
-            c = mfma_bf16(F[mb][2], F[2 + nb][0], c);     // smallest terms first
-            c = mfma_bf16(F[mb][0], F[2 + nb][2], c);
-            c = mfma_bf16(F[mb][1], F[2 + nb][1], c);
-            c = mfma_bf16(F[mb][1], F[2 + nb][0], c);
-            c = mfma_bf16(F[mb][0], F[2 + nb][1], c);
-        }
-        c = mfma_bf16(F[mb][0], F[2 + nb][0], c);
-        acc[mb][nb] = c;
-    };
+    auto mm = [&](int mb, int nb) __attribute__((always_inline)) { wg_mul<NP>(acc[mb][nb], F[mb], F[2 + nb]); };
     // Where the next step's DMA instructions are issued -- as a burst after the barrier, dealt over the 8 blocks, or over
     // blocks 0-3 by one wave of a SIMD and 4-7 by the other -- measured the same within noise (profiles/r02_notes.md), so
     // the burst (least code) stays.
@@ -709,14 +675,8 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pls(const WgArgs a) {
     const int wn4 = 2 * (wave & 1);                    // first 64-column group of this wave (of 4)
     const int tg = lane >> 4, ti = lane & 15, tq = ti >> 2, tp = ti & 3;
     const int th = tg >> 1, tc = (tg & 1) * 16 + tp * 4;
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
     auto tr_frag = [&](const unsigned char* plane, int col0) __attribute__((always_inline)) -> uint4 {
-        const unsigned char* p = plane + (th * 8 + tq) * 256 + (((col0 + tc) * 2) ^ (tq * 64));
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p + 4 * 256));
-        uint2 a2 = __builtin_bit_cast(uint2, lo), b2 = __builtin_bit_cast(uint2, hi);
-        return make_uint4(a2.x, a2.y, b2.x, b2.y);
+        return wg_tr_frag(plane + (th * 8 + tq) * 256 + (((col0 + tc) * 2) ^ (tq * 64)));
     };
     f32x16 acc[2][NBW];
 #pragma unroll
@@ -736,18 +696,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pls(const WgArgs a) {
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl) FB[nb][pl] = tr_frag(Bx + pl * PLANE, (wn4 & 1) * 64 + nb * 32);
     };
-    auto mm = [&](int mb, int nb) __attribute__((always_inline)) {
-        f32x16 c = acc[mb][nb];
-        if constexpr (NP == 3) {
-            c = mfma_bf16(FA[mb][2], FB[nb][0], c);     // smallest terms first
-            c = mfma_bf16(FA[mb][0], FB[nb][2], c);
-            c = mfma_bf16(FA[mb][1], FB[nb][1], c);
-            c = mfma_bf16(FA[mb][1], FB[nb][0], c);
-            c = mfma_bf16(FA[mb][0], FB[nb][1], c);
-        }
-        c = mfma_bf16(FA[mb][0], FB[nb][0], c);
-        acc[mb][nb] = c;
-    };
+    auto mm = [&](int mb, int nb) __attribute__((always_inline)) { wg_mul<NP>(acc[mb][nb], FA[mb], FB[nb]); };
 #define ISWM_SB() __builtin_amdgcn_sched_barrier(0)
     for (int s2 = 0; s2 < nK; ++s2) {
         __builtin_amdgcn_s_barrier();              // B(s2): stage s2 has landed

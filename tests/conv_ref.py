@@ -57,6 +57,15 @@ ROUTES = [
     _r("pl_d18", "pl", (1, 9, 9, 64, 128, 3, 1, 18, 18), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<4, 2, 3, true>", "k_wgrad_plw<3>"),
     _r("pl_5x5", "pl", (1, 11, 11, 64, 128, 5, 1, 2, 1), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<4, 2, 3, true>", "k_wgrad_pls<3>"),
     _r("pl_map1", "pl", (3, 1, 1, 128, 128, 1, 1, 0, 1), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<8, 1, 3, true>", "k_wgrad_pl<3>"),
+    # -- tiny maps: the pixel walk of the planes weight gradients re-divides where a step of KS pixels can cross more than one
+    #    image (KS / Wo + 1 > Ho; KS = 32, or 16 in k_wgrad_pls) -- in the 128-column kernel on a 1 x 1 that is not the `always`
+    #    form, in the loader of k_wgrad_pls, under the culling vote with taps partly in bounds, and in rect mode, where the walk
+    #    advances from a rectangle's second 16-pixel stage on: 4 images give the 1 x 5 and 5 x 1 rectangles 20 pixels (they
+    #    divide again) and the 5 x 5 one 100 (it carries) in one launch; the 1 x 1 rectangles end within their first stage
+    _r("pl_tiny_s2", "pl", (4, 5, 5, 128, 128, 1, 2, 0, 1), wgrad="k_wgrad_pl<3>"),
+    _r("pl_tiny_3x3", "pl", (4, 3, 5, 64, 128, 3, 1, 1, 1), wgrad="k_wgrad_pls<3>"),
+    _r("pl_tiny_d4", "pl", (2, 5, 5, 64, 128, 3, 1, 4, 4), wgrad="k_wgrad_plw<3>"),
+    _r("pl_tiny_rect", "pl", (4, 5, 5, 256, 128, 3, 1, 4, 4), wgrad="k_wgrad_pls<3>"),
     # -- weight gradient: tap rectangles (pad >= 4, Cin % 256 == 0), one with a multi-split plan; k_wgrad_pls with a multi-split
     #    plan (k_reduce_slabs_frag)
     _r("pl_rect", "pl", (1, 9, 9, 256, 128, 3, 1, 18, 18), "k_conv_pl2<8, 1, 3, false>", "k_conv_pl2<8, 1, 3, true>", "k_wgrad_pls<3>"),
@@ -147,6 +156,9 @@ ROUTES = [
        "k_conv_wgrad<64, 64, 1, true, 1>"),
     _r("bf16_pl", "bf16pl", (1, 9, 15, 128, 128, 3, 1, 1, 1), "k_conv_pl2<8, 1, 1, false>", "k_conv_pl2<8, 1, 1, true>",
        "k_wgrad_pls<1>"),
+    #    the one-plane instantiations of the 128-column and the vote weight-gradient kernels
+    _r("bf16_pl_1x1", "bf16pl", (5, 7, 11, 64, 128, 1, 1, 0, 1), wgrad="k_wgrad_pl<1>"),
+    _r("bf16_pl_d18", "bf16pl", (1, 9, 9, 64, 128, 3, 1, 18, 18), wgrad="k_wgrad_plw<1>"),
 ]
 ROUTE = {r.id: r for r in ROUTES}
 # MobileNetV2's 1 x 1 channel pairs (Cin, Cout) over the maps of the bench input (16 x 513 x 513: stride 2, 4, 8, 16) and its stem:
@@ -704,6 +716,10 @@ FLOOR = {
     "pl_map1.dx": 2.6e-07,
     "pl_map1.dx_acc": 2.6e-07,
     "pl_map1.dw": 6.9e-08,
+    "pl_tiny_s2.dw": 2.3e-07,
+    "pl_tiny_3x3.dw": 1.2e-07,
+    "pl_tiny_d4.dw": 1.5e-07,
+    "pl_tiny_rect.dw": 1.7e-07,
     "pl_rect.y": 4.9e-07,
     "pl_rect.dx": 4.3e-07,
     "pl_rect.dx_acc": 2.1e-07,
@@ -846,6 +862,8 @@ FLOOR = {
     "bf16_pl.dx_acc": 1.2e-07,
     "bf16_pl.dw": 1.6e-07,
     "bf16_pl.y_bias": 2.2e-07,
+    "bf16_pl_1x1.dw": 1.3e-07,
+    "bf16_pl_d18.dw": 1.3e-07,
     "aspp_small.b0.y": 3.4e-07,
     "aspp_small.b0.dw": 2.7e-07,
     "aspp_small.b1.y": 4.5e-07,

@@ -99,7 +99,8 @@ def test_route_table_reaches_every_listed_kernel():
              "k_conv_x6_patch<false, 3>", "k_conv_x6_patch<true, 3>", "k_conv_wgrad<64, 64, 2, true, 3>", "k_conv_fwd_u<64, 64>",
              "k_conv_dgrad_u<64, 64>", "k_conv_fwd<64>", "k_conv_fwd<128>", "k_conv_dgrad<64>", "k_conv_dgrad<128>",
              "k_conv_x6<64, 64, false, true, 1>", "k_conv_pl2<8, 1, 1, false>", "k_wgrad_pls<1>",
-             "k_conv_x6<128, 64, false, true, 3>", "k_conv_x6<128, 64, true, true, 3>", "k_conv_pl2w<9, 3, false>"]
+             "k_conv_x6<128, 64, false, true, 3>", "k_conv_x6<128, 64, true, true, 3>", "k_conv_pl2w<9, 3, false>",
+             "k_wgrad_pl<1>", "k_wgrad_plw<1>"]
     assert not [n for n in want if n not in names]
     assert set(("k_conv_pl2w<8, 3, false>", "k_conv_pl2<8, 1, 3, false>")) <= set(
         v for rt in R.ROUTES if rt.id not in R.NO_DENSE for v in rt.names.values())       # a dense case reaches them too
@@ -135,6 +136,33 @@ def test_route_table_reaches_every_listed_kernel():
         assert has("k_conv_wgrad<64, 64, 2, true, 3>", lambda cols, ch, kk: cols == rows), rows
     for cols_ in (24, 32, 96, 160):                                             # the accumulating data gradient of the residual blocks
         assert any(rt.geom[3] == cols_ and "dgrad" in rt.names for rt in R.ROUTES if rt.id.startswith("mb_")), cols_
+
+
+def test_tiny_maps_take_the_walks_redivide_branch():
+    """the pixel walk of the planes weight gradients advances KS pixels per step (32; 16 in k_wgrad_pls) with a carry when a step
+    crosses at most one row boundary more than KS / Wo rows and one image (KS / Wo + 1 <= Ho), and divides again otherwise:
+    every pl_tiny_* row has to be on the dividing side, over all of N x Ho x Wo or -- pl_tiny_rect -- over tap rectangles
+    of which some carry and some divide, each of them over more than one stage (the first stage only divides)"""
+    tiny = [rt for rt in R.ROUTES if rt.id.startswith("pl_tiny_")]
+    assert sorted(rt.id for rt in tiny) == ["pl_tiny_3x3", "pl_tiny_d4", "pl_tiny_rect", "pl_tiny_s2"]
+    for rt in tiny:
+        n, h, w, cin, cout, k, stride, pad, dil = rt.geom
+        ho, wo = R.out_size(h, k, stride, pad, dil), R.out_size(w, k, stride, pad, dil)
+        ks = 16 if rt.names["wgrad"].startswith("k_wgrad_pls") else 32
+        if rt.id != "pl_tiny_rect":
+            assert ks // wo + 1 > ho, rt.id
+            continue
+        assert pad >= 4 and stride == 1 and cin % 256 == 0                  # rect mode (wgrad_rect_mode)
+        assert R.wgrad_workspace(rt) == 0                                    # one split: a tile walks its whole rectangle
+        walked = set()                 # the walk advances from the second stage on: a rectangle of more than KS pixels
+        for t in range(k * k):
+            dh, dw = (t // k) * dil - pad, (t % k) * dil - pad
+            rh = max(0, min(ho, h - dh) - max(0, -dh))
+            rw = max(0, min(wo, w - dw) - max(0, -dw))
+            assert rh > 0 and rw > 0                                         # no empty tap: every rectangle is walked
+            if n * rh * rw > ks:
+                walked.add(ks // max(1, rw) + 1 <= rh)
+        assert walked == {False, True}                                       # some rectangle carries, some divides again
 
 
 def test_mobilenet_tile_thresholds():
