@@ -13,8 +13,6 @@ MI355X-specific structure:
   * in backward the five branches' input gradients accumulate in place into one
     buffer (dgrad kernels with accumulate=1) instead of five tensors plus four adds.
 """
-import ctypes
-
 import torch
 import torch.nn as nn
 
@@ -135,6 +133,17 @@ class ASPP(_hip.HipModule):
             return None
         return out
 
+    @staticmethod
+    def _branch_weights(br, x, kind, ldx, ldy):
+        """the branches' weights packed for the planes kernels (kind 0 forward, 1 data gradient) at these pitches"""
+        out = []
+        for c, _ in br:
+            d = c.geometry(x).desc(ldx, ldy)
+            p = ops.conv_plan(d, ("fwd", "dgrad")[kind], True)
+            assert p.wform == "pl2", "the fused ASPP kernels take the planes kernels' weight form"
+            out.append(ops.conv_weight(c.weight_for(kind), p, d, kind))
+        return out
+
     def _fwd_fused(self, x, save, cat, oc):
         """runs the conv branches through ops.aspp_fwd and finishes each (BatchNorm, ReLU into its slice of `cat`); returns the
         per-branch stage contexts, or None when the fused kernel does not cover this module / input"""
@@ -150,16 +159,7 @@ class ASPP(_hip.HipModule):
         training = br[0][1].training
         if any(bn.training != training for _, bn in br):
             return None
-        wpks = []
-        for c, _ in br:
-            w2 = c.packed2(0)
-            if w2 is None:
-                g = c.geometry(x)
-                d = g.desc(ops.pgeom(x)[4], oc)
-                w2 = torch.empty((ops._pl2_bytes(d, 0) // 4,), dtype=torch.float32, device=x.t.device)
-                ops.call("iswm_conv2d_pl2_pack_weights", ctypes.byref(d), 0, ops._p(c.ohwi()), ops._p(w2), ops._stream())
-            wpks.append(w2)
-        res = ops.aspp_fwd(x, ksize, dil, oc, wpks, training)
+        res = ops.aspp_fwd(x, ksize, dil, oc, self._branch_weights(br, x, 0, ops.pgeom(x)[4], oc), training)
         if res is None:
             return None
         ys, parts, tiles = res
@@ -194,20 +194,11 @@ class ASPP(_hip.HipModule):
         for i, (c, bn) in enumerate(br):
             dy_i, _ = _hip.cba_bwd_bn(c, bn, ctxs[i], dcat[..., i * oc:(i + 1) * oc], sink, dy_out=dyc[..., i * oc:(i + 1) * oc])
             c.write_wgrad(ctxs[i]["x"], dy_i, ctxs[i]["g"], sink)
-        wpks = []
-        for c, _ in br:
-            w2 = c.packed2(1)
-            if w2 is None:
-                g = c.geometry(ctxs[0]["x"])
-                d = g.desc(cin, nb * oc)
-                w2 = torch.empty((ops._pl2_bytes(d, 1) // 4,), dtype=torch.float32, device=dcat.device)
-                ops.call("iswm_conv2d_pl2_pack_weights", ctypes.byref(d), 1, ops._p(c.ohwi()), ops._p(w2), ops._stream())
-            wpks.append(w2)
+        wpks = self._branch_weights(br, ctxs[0]["x"], 1, cin, nb * oc)
         dx = ops.aspp_dgrad(dyc, [c.kernel_size[0] for c, _ in br], [c.dilation[0] for c, _ in br], cin, oc, wpks)
         if dx is None:                                   # (cannot happen when the forward plan existed; keep the path honest)
             for i, (c, _) in enumerate(br):
-                dx = ops.conv2d_dgrad(dyc[..., i * oc:(i + 1) * oc], c.ohwi(), ctxs[i]["g"], xshape, dx, dx is not None,
-                                      wpk=c.packed(1), wpk2=c.packed2(1))
+                dx = ops.conv2d_dgrad(dyc[..., i * oc:(i + 1) * oc], c.weight_for(1), ctxs[i]["g"], xshape, dx, dx is not None)
         return dx
 
     def out_channels_of(self, cin):

@@ -83,6 +83,13 @@ class GradSink:
             self.on_ready(p)
 
 
+def _bias_grad(bias, dy, sink):
+    """gradient of a conv bias (possibly None or frozen) = the column sums of dy, into the sink"""
+    if bias is not None and bias.requires_grad:
+        ops.unpad_weights(ops.colsum(dy).view(-1, 1, 1, 1), sink.target(bias).view(-1, 1, 1, 1))
+        sink.done(bias)
+
+
 class HipModule(nn.Module):
     """Base: public ``forward`` takes/returns NCHW like the reference module and
     bridges to fwd/bwd."""
@@ -173,23 +180,16 @@ class Conv2d(HipModule, nn.Conv2d):
             return v if v.is_contiguous() else v.contiguous()
         return ops.pad_weights(w, self.cout_p, self.cin_p)
 
-    def packed2(self, kind):
-        """this weight pre-packed for the planes kernels (csrc/conv_mfma_pl2.hip) by the WeightPacker, or None"""
-        e = getattr(self, "_iswm_wpk", None)
+    def weight_for(self, kind):
+        """the ops.ConvWeight of the forward (kind 0) / data gradient (1): the OHWI weight plus what the model's WeightPacker
+        pre-packed from it for the bf16x6 ("x6") and the planes ("pl2") kernels.  Those buffers count only inside the
+        forward/backward window they were made for and only while the parameter is untouched; the kernel wrappers pack the
+        weight themselves otherwise."""
+        w, e = self.ohwi(), getattr(self, "_iswm_wpk", None)
         if e is None or not e["live"] or e["epoch"] != ops.WEIGHTS_EPOCH or e["version"] != self.weight._version or \
                 e["ptr"] != self.weight.data_ptr():
-            return None
-        return e["buf"].get(kind + 2)
-
-    def packed(self, kind):
-        """this weight pre-packed for the bf16x6 forward (0) / data-gradient (1) kernel by the model's WeightPacker,
-        or None (the kernel wrappers then pack it themselves).  Valid only inside the forward/backward window it was
-        made for and only while the parameter is untouched."""
-        e = getattr(self, "_iswm_wpk", None)
-        if e is None or not e["live"] or e["epoch"] != ops.WEIGHTS_EPOCH or e["version"] != self.weight._version or \
-                e["ptr"] != self.weight.data_ptr():
-            return None
-        return e["buf"][kind]
+            return ops.ConvWeight(w)
+        return ops.ConvWeight(w, {"x6": e["buf"][kind], "pl2": e["buf"][kind + 2]})
 
     def bias_p(self):
         if self.bias is None:
@@ -222,20 +222,18 @@ class Conv2d(HipModule, nn.Conv2d):
     # -- standalone conv (+bias), e.g. the final 1x1 classifier ---------------------------
     def fwd(self, x, save, out=None):
         g = self.geometry(x)
-        y, _, _ = ops.conv2d_fwd(x, self.ohwi(), g, bias=self.bias_p(), out=out, wpk=self.packed(0), wpk2=self.packed2(0))
+        y, _, _ = ops.conv2d_fwd(x, self.weight_for(0), g, bias=self.bias_p(), out=out)
         self._saved = (x, g) if save else None
         return y
 
     def bwd(self, dy, sink, need_dx=True, dx=None, accumulate=False):
         x, g = self._saved
         self._saved = None
-        if self.bias is not None and self.bias.requires_grad:
-            ops.unpad_weights(ops.colsum(dy).view(-1, 1, 1, 1), sink.target(self.bias).view(-1, 1, 1, 1))
-            sink.done(self.bias)
+        _bias_grad(self.bias, dy, sink)
         self.write_wgrad(x, dy, g, sink)
         if not need_dx:
             return None
-        return ops.conv2d_dgrad(dy, self.ohwi(), g, tuple(x.shape), dx, accumulate, wpk=self.packed(1), wpk2=self.packed2(1))
+        return ops.conv2d_dgrad(dy, self.weight_for(1), g, tuple(x.shape), dx, accumulate)
 
     def out_channels_of(self, cin):
         return self.out_channels
@@ -300,9 +298,7 @@ class DepthwiseConv2d(HipModule, nn.Conv2d):
     def bwd(self, dy, sink, need_dx=True, dx=None, accumulate=False):
         x, g = self._saved
         self._saved = None
-        if self.bias is not None and self.bias.requires_grad:
-            ops.unpad_weights(ops.colsum(dy).view(-1, 1, 1, 1), sink.target(self.bias).view(-1, 1, 1, 1))
-            sink.done(self.bias)
+        _bias_grad(self.bias, dy, sink)
         if self.weight.requires_grad:
             buf = sink.target(self.weight)
             if buf.is_contiguous():
@@ -374,40 +370,58 @@ def cba_fwd(conv, bn, relu, x, save, residual=None, out=None, out_fmt=None):
         g = conv.geometry(x)
         if conv.is_dw3x3():                     # statistics from the convolution's own launch (csrc/dwconv3.hip)
             y, partials, tiles = conv.fwd_stats(x, save, training)
-            return _cba_finish(conv, bn, relu, x, y, g, partials, tiles, training, save, residual, out, sep, True, out_fmt)
-        y = conv.fwd(x, save)                   # other filter sizes: statistics from a column pass
-        partials, tiles = None, (0, 0)
-        if training:
-            partials, nt, tr = ops.colstat(y)
-            tiles = (nt, tr)
+        else:                                   # other filter sizes: statistics from a column pass
+            y = conv.fwd(x, save)
+            partials, tiles = _colstat_partials(y, training)
         return _cba_finish(conv, bn, relu, x, y, g, partials, tiles, training, save, residual, out, sep, True, out_fmt)
     g = conv.geometry(x)
     if conv.bias is None:
-        y, partials, tiles = ops.conv2d_fwd(x, conv.ohwi(), g, want_stats=training, wpk=conv.packed(0), wpk2=conv.packed2(0))
+        y, partials, tiles = ops.conv2d_fwd(x, conv.weight_for(0), g, want_stats=training)
     else:
         # a biased conv in front of a BatchNorm (only reachable through convert_to_separable_conv on a biased
         # conv): the fused epilogue statistics do not include the bias, so take them in a separate column pass
-        y, _, _ = ops.conv2d_fwd(x, conv.ohwi(), g, bias=conv.bias_p())
-        partials, tiles = None, (0, 0)
-        if training:
-            partials, nt, tr = ops.colstat(y)
-            tiles = (nt, tr)
+        y, _, _ = ops.conv2d_fwd(x, conv.weight_for(0), g, bias=conv.bias_p())
+        partials, tiles = _colstat_partials(y, training)
     return _cba_finish(conv, bn, relu, x, y, g, partials, tiles, training, save, residual, out, sep, False, out_fmt)
 
 
+def _colstat_partials(y, training):
+    """(partials | None, (tiles, tile_rows)) of a stage whose producer publishes no tile statistics: a column pass over y"""
+    if not training:
+        return None, (0, 0)
+    partials, nt, tr = ops.colstat(y)
+    return partials, (nt, tr)
+
+
+def _bn_coef(bn, y, partials, tiles, training):
+    """coef [4, C] = (scale, shift, mean, invstd) of a stage's BatchNorm: from the tile statistics of y when training (the
+    running buffers and the batch counter move), else from the running buffers"""
+    if not training:
+        return ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+    count = y.shape[0] * y.shape[1] * y.shape[2]
+    if count <= 1:
+        # same contract as torch (network/_deeplab.py:130-141 needs batch >= 2)
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(y.shape),))
+    coef = ops.bn_finalize(partials, tiles[0], count, tiles[1], bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                           bn.momentum, bn.eps)
+    if not getattr(bn, "_iswm_nbt_fused", False):
+        bn.num_batches_tracked.add_(1)     # models built by modeling.* bump all counters in ONE op
+    return coef
+
+
+def _bn_grad_targets(bn, sink):
+    """(dgamma, dbeta) for the BatchNorm backward to write: the sink's targets, scratch for a frozen parameter"""
+    return [sink.target(p) if p.requires_grad else torch.empty_like(p) for p in (bn.weight, bn.bias)]
+
+
+def _bn_grads_done(bn, sink):
+    for p in (bn.weight, bn.bias):
+        if p.requires_grad:
+            sink.done(p)
+
+
 def _cba_finish(conv, bn, relu, x, y, g, partials, tiles, training, save, residual, out, sep, dw, out_fmt=None):
-    if training:
-        count = y.shape[0] * y.shape[1] * y.shape[2]
-        if count <= 1:
-            # same contract as torch (network/_deeplab.py:130-141 needs batch >= 2)
-            raise ValueError("Expected more than 1 value per channel when training, got input size %s" %
-                             (tuple(y.shape),))
-        coef = ops.bn_finalize(partials, tiles[0], count, tiles[1], bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                               bn.momentum, bn.eps)
-        if not getattr(bn, "_iswm_nbt_fused", False):
-            bn.num_batches_tracked.add_(1)     # models built by modeling.* bump all counters in ONE op
-    else:
-        coef = ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+    coef = _bn_coef(bn, y, partials, tiles, training)
     if out_fmt is None:
         want_planes = ops.planes_on() and y.shape[3] % 64 == 0
     else:
@@ -451,9 +465,8 @@ def cba_bwd_bn(conv, bn, ctx, dout, sink, dy_out=None, need_dx=True):
     sep = ctx.get("sep")
     if sep is not None:
         conv = sep.body[1]
-    gw, gb = bn.weight, bn.bias
-    dgamma = sink.target(gw) if gw.requires_grad else torch.empty_like(gw)
-    dbeta = sink.target(gb) if gb.requires_grad else torch.empty_like(gb)
+    gw = bn.weight
+    dgamma, dbeta = _bn_grad_targets(bn, sink)
     # planes only when a planes kernel will read them: the data gradient, or the weight gradient of a pre-split input (the stem
     # has neither: its gradient stays fp32 instead of being split here and joined again for the weight gradient)
     dyp = (not ctx.get("dw")) and ops.planes_conv_ok(conv.cin_p, conv.cout_p, 1) and (need_dx or ops.is_planes(ctx["x"]))
@@ -466,10 +479,7 @@ def cba_bwd_bn(conv, bn, ctx, dout, sink, dy_out=None, need_dx=True):
     else:
         dy, dres = ops.bn_backward(ops.as_f32(dout), o if ctx["relu"] else None, y, ctx["coef"], gw, ctx["relu"], ctx["training"],
                                    dgamma, dbeta, want_dres=ctx["res"], dy=dy_out, dy_planes=dyp, stats=st)
-    if gw.requires_grad:
-        sink.done(gw)
-    if gb.requires_grad:
-        sink.done(gb)
+    _bn_grads_done(bn, sink)
     return dy, dres
 
 
@@ -485,16 +495,13 @@ def cba_bwd(conv, bn, ctx, dout, sink, need_dx=True, dx=None, accumulate=False, 
             return conv.bwd_fused(dy, sink, need_dx, dx, accumulate), dres
         return conv.bwd(dy, sink, need_dx, dx, accumulate), dres
     conv.write_wgrad(x, dy, g, sink)
-    if conv.bias is not None and conv.bias.requires_grad:
-        ops.unpad_weights(ops.colsum(dy).view(-1, 1, 1, 1), sink.target(conv.bias).view(-1, 1, 1, 1))
-        sink.done(conv.bias)
+    _bias_grad(conv.bias, dy, sink)
     if sep is not None:
-        dmid = ops.conv2d_dgrad(dy, conv.ohwi(), g, tuple(x.shape), wpk=conv.packed(1), wpk2=conv.packed2(1))
+        dmid = ops.conv2d_dgrad(dy, conv.weight_for(1), g, tuple(x.shape))
         return sep.body[0].bwd(dmid, sink, need_dx, dx, accumulate), dres
     if need_dx:
         req = _bn_stats_request(up) if (up is not None and tuple(up["y"].shape) == tuple(x.shape)) else None
-        dx = ops.conv2d_dgrad(dy, conv.ohwi(), g, tuple(x.shape), dx, accumulate, wpk=conv.packed(1), wpk2=conv.packed2(1),
-                              bn_stats=req)
+        dx = ops.conv2d_dgrad(dy, conv.weight_for(1), g, tuple(x.shape), dx, accumulate, bn_stats=req)
         if req is not None and req.partials is not None:
             up["bn_stats"] = req
     else:
@@ -609,17 +616,8 @@ def cba_cls_fwd(conv, bn, cls, x, save):
     """conv -> BatchNorm -> ReLU -> 1x1 classifier with the activation never stored: returns (logits [N,H,W,4], ctx)"""
     g = conv.geometry(x)
     training = bn.training
-    y, partials, tiles = ops.conv2d_fwd(x, conv.ohwi(), g, want_stats=training, wpk=conv.packed(0), wpk2=conv.packed2(0))
-    if training:
-        count = y.shape[0] * y.shape[1] * y.shape[2]
-        if count <= 1:
-            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(y.shape),))
-        coef = ops.bn_finalize(partials, tiles[0], count, tiles[1], bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                               bn.momentum, bn.eps)
-        if not getattr(bn, "_iswm_nbt_fused", False):
-            bn.num_batches_tracked.add_(1)
-    else:
-        coef = ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+    y, partials, tiles = ops.conv2d_fwd(x, conv.weight_for(0), g, want_stats=training)
+    coef = _bn_coef(bn, y, partials, tiles, training)
     wc4 = ops.pad_weights(cls.weight, 4, 256).view(4, 256)
     b4 = None if cls.bias is None else ops.pad_weights(cls.bias.view(-1, 1, 1, 1), 4, 1).view(-1)
     logits = ops.bn_apply_classify(y, coef, wc4, b4)
@@ -636,25 +634,19 @@ def cba_cls_bwd(conv, bn, ctx, dlogit, sink, need_dx=True, dx=None, accumulate=F
     conv's weight and data gradients as in cba_bwd"""
     cls, x, y, g = ctx["cls"], ctx["x"], ctx["y"], ctx["g"]
     dlogit = ops.as_f32(dlogit)
-    if cls.bias is not None and cls.bias.requires_grad:
-        ops.unpad_weights(ops.colsum(dlogit).view(-1, 1, 1, 1), sink.target(cls.bias).view(-1, 1, 1, 1))
-        sink.done(cls.bias)
-    gw, gb = bn.weight, bn.bias
-    dgamma = sink.target(gw) if gw.requires_grad else torch.empty_like(gw)
-    dbeta = sink.target(gb) if gb.requires_grad else torch.empty_like(gb)
+    _bias_grad(cls.bias, dlogit, sink)
+    gw = bn.weight
+    dgamma, dbeta = _bn_grad_targets(bn, sink)
     dyp = ops.planes_conv_ok(conv.cin_p, conv.cout_p, 1)
     dy, dwc4 = ops.bn_backward_classify(dlogit, ctx["wc4"], y, ctx["coef"], gw, ctx["training"], dgamma, dbeta, dyp)
-    if gw.requires_grad:
-        sink.done(gw)
-    if gb.requires_grad:
-        sink.done(gb)
+    _bn_grads_done(bn, sink)
     if cls.weight.requires_grad:
         ops.unpad_weights(dwc4.view(4, 1, 1, 256), sink.target(cls.weight))
         sink.done(cls.weight)
     conv.write_wgrad(x, dy, g, sink)
     if not need_dx:
         return None
-    return ops.conv2d_dgrad(dy, conv.ohwi(), g, tuple(x.shape), dx, accumulate, wpk=conv.packed(1), wpk2=conv.packed2(1))
+    return ops.conv2d_dgrad(dy, conv.weight_for(1), g, tuple(x.shape), dx, accumulate)
 
 
 class SeparableBase(HipModule):
@@ -679,13 +671,8 @@ class HipSequential(HipModule, nn.Sequential):
                 st.append(("cba", m, mods[i + 1], relu))
                 i += 3 if relu else 2
             elif isinstance(m, Conv2d):
-                if i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d):
-                    relu = i + 2 < len(mods) and isinstance(mods[i + 2], nn.ReLU)
-                    st.append(("cba", m, mods[i + 1], relu))
-                    i += 3 if relu else 2
-                else:
-                    st.append(("conv", m))
-                    i += 1
+                st.append(("conv", m))
+                i += 1
             elif isinstance(m, HipModule):
                 st.append(("mod", m))
                 i += 1

@@ -9,6 +9,7 @@ Activations are NHWC: a 4-D fp32 tensor ``[N, H, W, C]`` whose last dim is
 contiguous and whose pixel pitch ``ld = t.stride(2)`` may exceed C (a channel
 slice of a wider buffer -- that is how torch.cat disappears from the graph).
 """
+import collections
 import ctypes
 import functools
 
@@ -190,48 +191,34 @@ class KernelProfile:
         self.only = only    # when set: time launches of this kernel only (keeps the timed region light)
         self.scope = None   # free-form label stamped on the records added while it is set (bench: "head_fwd")
 
-    def begin(self):
-        return True
-
-    def end(self, name, start, flops, tag=None):
-        # the bracketing events are recorded by _timed(); kept for API symmetry
-        raise NotImplementedError
-
     def wants(self, name):
         return self.only is None or name == self.only or name + "+reduce" == self.only
 
     def add(self, name, a, b, flops, tag):
         self.records.append((name, a, b, flops, tag, self.scope))
 
+    def _totals(self, key, records=None):
+        """{key(record): dict(launches, ms, flops)} over the records -- call after torch.cuda.synchronize()"""
+        out = {}
+        for r in self.records if records is None else records:
+            d = out.setdefault(key(r), dict(launches=0, ms=0.0, flops=0.0))
+            d["launches"] += 1
+            d["ms"] += r[1].elapsed_time(r[2])
+            d["flops"] += r[3]
+        return out
+
     def scope_total(self, scope):
         """dict(launches, ms, flops) over the records stamped with this scope"""
-        d = dict(launches=0, ms=0.0, flops=0.0)
-        for name, a, b, fl, _, sc in self.records:
-            if sc == scope:
-                d["launches"] += 1
-                d["ms"] += a.elapsed_time(b)
-                d["flops"] += fl
-        return d
+        tot = self._totals(lambda r: scope, [r for r in self.records if r[5] == scope])
+        return tot.get(scope, dict(launches=0, ms=0.0, flops=0.0))
 
     def summary(self):
-        """{name: dict(launches, ms, flops)} -- call after torch.cuda.synchronize()"""
-        out = {}
-        for name, a, b, fl, _, _sc in self.records:
-            d = out.setdefault(name, dict(launches=0, ms=0.0, flops=0.0))
-            d["launches"] += 1
-            d["ms"] += a.elapsed_time(b)
-            d["flops"] += fl
-        return out
+        """{name: dict(launches, ms, flops)}"""
+        return self._totals(lambda r: r[0])
 
     def by_geometry(self):
         """{(name, geometry tag): dict(launches, ms, flops)}"""
-        out = {}
-        for name, a, b, fl, tag, _sc in self.records:
-            d = out.setdefault((name, tag), dict(launches=0, ms=0.0, flops=0.0))
-            d["launches"] += 1
-            d["ms"] += a.elapsed_time(b)
-            d["flops"] += fl
-        return out
+        return self._totals(lambda r: (r[0], r[4]))
 
 
 KPROF = None
@@ -278,35 +265,33 @@ class ConvGeom:
             self._flops = 2.0 * self.n * vh * vw * self.alg_cin * self.alg_cout
         return self._flops
 
-    def desc(self, ldx, ldy):
-        return ConvDesc(self.n, self.h, self.w, self.cin, self.ho, self.wo, self.cout, self.kh, self.kw,
+    def desc(self, ldx, ldy, cout=None):
+        return ConvDesc(self.n, self.h, self.w, self.cin, self.ho, self.wo, cout or self.cout, self.kh, self.kw,
                         self.stride, self.pad, self.dil, ldx, ldy)
-
-
-_NAME_CACHE = {}
 
 
 def _kernel_name(d, kind):
     """device kernel symbol the library launches for this geometry (labels profile records)"""
-    lib = _lib.load()
-    key = (kind, lib.iswm_get_conv_math(), d.N, d.H, d.W, d.Cin, d.Cout, d.KH, d.stride, d.pad, d.dil)
-    name = _NAME_CACHE.get(key)
-    if name is None:
-        buf = ctypes.create_string_buffer(64)
-        lib.iswm_conv2d_kernel_name(ctypes.byref(d), kind, buf, 64)
-        name = _NAME_CACHE[key] = buf.value.decode()
-    return name
+    buf = ctypes.create_string_buffer(64)
+    _lib.load().iswm_conv2d_kernel_name(ctypes.byref(d), kind, buf, 64)
+    return buf.value.decode()
+
+
+def _geoms_tag(geoms):
+    if len(geoms) == 1:
+        return geoms[0].tag()
+    g0 = geoms[0]
+    return "n%d %dx%d c%d->%dx%d aspp d%s" % (g0.n, g0.h, g0.w, g0.alg_cin, len(geoms), g0.alg_cout,
+                                             "/".join(str(g.dil) for g in geoms if g.kh > 1))
 
 
 class _timed:
-    """bracket one conv launch with HIP events on the launch stream when a KernelProfile is active"""
+    """bracket one conv launch with HIP events on the launch stream when a KernelProfile is active; `geoms`: the conv
+    geometries the launch computes (one, or the ASPP branches: flops add up)"""
 
-    def __init__(self, d, kind, g, suffix=""):
-        self.on = False
-        if KPROF is not None:
-            name = _kernel_name(d, kind) + suffix
-            if KPROF.wants(name):
-                self.on, self.name, self.g = True, name, g
+    def __init__(self, name, geoms):
+        self.on = KPROF is not None and KPROF.wants(name)
+        self.name, self.geoms = name, geoms
 
     def __enter__(self):
         if self.on:
@@ -317,7 +302,7 @@ class _timed:
         if self.on:
             b = torch.cuda.Event(enable_timing=True)
             b.record()
-            KPROF.add(self.name, self.a, b, self.g.flops(), self.g.tag())
+            KPROF.add(self.name, self.a, b, sum(g.flops() for g in self.geoms), _geoms_tag(self.geoms))
         return False
 
 
@@ -335,59 +320,8 @@ def weights_changed():
     WEIGHTS_EPOCH += 1
 
 
-def conv2d_fwd(x, w_ohwi, g, bias=None, out=None, want_stats=False, wpk=None, wpk2=None):
-    """y = conv(x, w) [+ bias]; returns (y, partials|None, (tiles, tile_rows)).  wpk: this weight already packed
-    for the forward kernel (network._hip.WeightPacker), else it is packed here.  The partials describe the convolution BEFORE
-    the bias (the same bits with and without one): a caller that normalises a biased output takes colstat(y) instead."""
-    _check_w(w_ohwi, g)
-    if out is None:
-        out = new_act(g.n, g.ho, g.wo, g.cout, x.device)
-    on, oh, ow, oc, ldy = geom(out)
-    assert (on, oh, ow, oc) == (g.n, g.ho, g.wo, g.cout)
-    if isinstance(x, Planes):
-        _, _, _, _, ldp, ps = pgeom(x)
-        d = g.desc(ldp, ldy)
-        nb2 = _pl2_bytes(d, 0)
-        if nb2:
-            partials, tiles = None, (0, 0)
-            if want_stats:
-                tr = _lib.load().iswm_conv2d_pl2_tile_rows(ctypes.byref(d), 0)
-                tiles = ((g.n * g.ho * g.wo + tr - 1) // tr, tr)
-                partials = torch.empty((2, tiles[0], g.cout), dtype=torch.float32, device=out.device)
-            if wpk2 is None:
-                wpk2 = torch.empty((nb2 // 4,), dtype=torch.float32, device=out.device)
-                call("iswm_conv2d_pl2_pack_weights", ctypes.byref(d), 0, _p(w_ohwi), _p(wpk2), _stream())
-            with _timed(d, 5, g):
-                call("iswm_conv2d_fwd_pl2", ctypes.byref(d), _p(x.t), ps, _p(wpk2), _p(bias), _p(out), _p(partials), _stream())
-            return out, partials, tiles
-        x = x.f32()
-    ldx = geom(x)[4]
-    d = g.desc(ldx, ldy)
-    partials, tiles = None, (0, 0)
-    if want_stats:
-        lib = _lib.load()
-        tiles = (lib.iswm_conv2d_stat_tiles(ctypes.byref(d)), lib.iswm_conv2d_stat_tile_rows(ctypes.byref(d)))
-        partials = torch.empty((2, tiles[0], g.cout), dtype=torch.float32, device=x.device)
-    nb = _packed_bytes(d, 0)
-    if nb:
-        if want_stats:
-            nt, tr = ctypes.c_int(0), ctypes.c_int(0)
-            call("iswm_conv2d_fwd_packed_stat_layout", ctypes.byref(d), ctypes.byref(nt), ctypes.byref(tr))
-            tiles = (nt.value, tr.value)
-            flat = torch.empty((2 * nt.value * g.cout + nt.value,), dtype=torch.float32, device=x.device)
-            partials = flat[:2 * nt.value * g.cout].view(2, nt.value, g.cout)   # per-tile row counts follow
-        if wpk is None:
-            wpk = torch.empty((nb // 4,), dtype=torch.float32, device=x.device)
-            call("iswm_conv2d_pack_weights", ctypes.byref(d), 0, _p(w_ohwi), _p(wpk), _stream())
-        with _timed(d, 3, g):
-            call("iswm_conv2d_fwd_packed", ctypes.byref(d), _p(x), _p(wpk), _p(bias), _p(out), _p(partials), _stream())
-        return out, partials, tiles
-    with _timed(d, 0, g):
-        call("iswm_conv2d_fwd", ctypes.byref(d), _p(x), _p(w_ohwi), _p(bias), _p(out), _p(partials), _stream())
-    return out, partials, tiles
-
-
 _USE_PACKED = True      # False: the packed-weight kernels stay unused (tests compare both paths)
+_BN_FUSE = True         # False: BatchNorm backward always reduces itself (tests compare both paths)
 
 
 def _packed_bytes(d, kind):
@@ -404,6 +338,131 @@ def planes_conv_ok(cin, cout, kind):
     return planes_on() and (cout if kind else cin) % 64 == 0
 
 
+# ---- one plan per conv call: THE entry-point ladder (planes kernel -> packed bf16x6 kernel -> transposed-weight data
+# gradient -> plain) and everything the wrappers size from it.  tests/conv_ref.planned() restates it independently.
+ConvPlan = collections.namedtuple("ConvPlan", "entry kind name wform wbytes planes tiles tile_rows rows_stored stat_tiles workspace")
+ConvPlan.__doc__ = """How one conv call runs: `entry` point, its iswm_conv2d_kernel_name `kind` and the kernel `name`; the weight form
+it reads (wform "ohwi" / "wt" transposed / "x6" packed / "pl2" packed for the planes kernels, None for a weight gradient) and
+its size `wbytes`; `planes`: the operand is taken pre-split (False on a plan made for a Planes operand: join it and plan again).
+Forward: the BatchNorm-partial layout (tiles, tile_rows) and rows_stored -- the halo-patch layout, whose per-tile row counts
+follow the two planes.  Planes data gradient: stat_tiles of the BnStats epilogue.  Weight gradient: workspace bytes."""
+_PLANS = {}
+_PACK_ENTRY = {"x6": "iswm_conv2d_pack_weights", "pl2": "iswm_conv2d_pl2_pack_weights"}
+
+
+def conv_plan(d, op, planes):
+    """the ConvPlan of op ("fwd" / "dgrad" / "wgrad") on descriptor d whose operand (x; dy for the data gradient) is Planes or
+    fp32 -- pure host queries of the C ABI, cached under everything they depend on: all descriptor fields (pitches route too),
+    the conv math and the two switches"""
+    lib = _lib.load()
+    key = (bytes(d), op, planes, lib.iswm_get_conv_math(), planes_on(), _USE_PACKED)
+    p = _PLANS.get(key)
+    if p is not None:
+        return p
+    ref, dirn = ctypes.byref(d), int(op == "dgrad")
+    entry = wform = None
+    kind = wbytes = tiles = tile_rows = stat_tiles = workspace = 0
+    rows_stored = False
+    if op == "wgrad":
+        if not planes:
+            entry, kind, workspace = "iswm_conv2d_wgrad", 2, lib.iswm_conv2d_wgrad_workspace(ref)
+        elif planes_on() and lib.iswm_conv2d_wgrad_planes_ok(ref):
+            entry, kind, workspace = "iswm_conv2d_wgrad_planes", 7, lib.iswm_conv2d_wgrad_planes_workspace(ref)
+    elif planes:
+        wbytes = _pl2_bytes(d, dirn)
+        if wbytes:
+            entry, kind, wform = ("iswm_conv2d_dgrad_pl2", 6, "pl2") if dirn else ("iswm_conv2d_fwd_pl2", 5, "pl2")
+            if dirn:
+                stat_tiles = lib.iswm_conv2d_dgrad_pl2_stat_tiles(ref)
+            else:
+                tile_rows = lib.iswm_conv2d_pl2_tile_rows(ref, 0)
+                tiles = (d.N * d.Ho * d.Wo + tile_rows - 1) // tile_rows
+    else:
+        wbytes = _packed_bytes(d, dirn)
+        if wbytes:
+            entry, kind, wform = ("iswm_conv2d_dgrad_packed", 4, "x6") if dirn else ("iswm_conv2d_fwd_packed", 3, "x6")
+            if not dirn:
+                nt, tr = ctypes.c_int(0), ctypes.c_int(0)
+                call("iswm_conv2d_fwd_packed_stat_layout", ref, ctypes.byref(nt), ctypes.byref(tr))
+                tiles, tile_rows, rows_stored = nt.value, tr.value, True
+        else:
+            wbytes = 4 * d.Cout * d.KH * d.KW * d.Cin
+            if dirn:
+                # bf16x6 math: the matrix cores want the K axis (tap, cout) contiguous -> transposed weights
+                wt = lib.iswm_conv2d_dgrad_wants_wt(ref)
+                entry, kind, wform = ("iswm_conv2d_dgrad_wt", 1, "wt") if wt else ("iswm_conv2d_dgrad", 1, "ohwi")
+            else:
+                entry, kind, wform = "iswm_conv2d_fwd", 0, "ohwi"
+                tiles, tile_rows = lib.iswm_conv2d_stat_tiles(ref), lib.iswm_conv2d_stat_tile_rows(ref)
+    p = _PLANS[key] = ConvPlan(entry, kind, _kernel_name(d, kind) if entry else None, wform, wbytes, bool(planes and entry),
+                               tiles, tile_rows, rows_stored, stat_tiles, workspace)
+    return p
+
+
+class ConvWeight(object):
+    """One conv weight for one direction: the OHWI tensor plus the live buffers a WeightPacker pre-packed from it
+    ({"x6": ..., "pl2": ...}, network._hip.Conv2d.weight_for).  The op wrappers take this or a bare OHWI tensor."""
+    __slots__ = ("ohwi", "packed")
+
+    def __init__(self, ohwi, packed=None):
+        self.ohwi, self.packed = ohwi, packed or {}
+
+
+def _ohwi(w):
+    return w.ohwi if isinstance(w, ConvWeight) else w
+
+
+def conv_weight(w, p, d, dirn):
+    """the weight of plan p (dirn 0 forward, 1 data gradient) in the form its entry point reads: the OHWI tensor itself, the
+    handle's pre-packed buffer, else a buffer allocated and packed / transposed here"""
+    ohwi = _ohwi(w)
+    if p.wform == "ohwi":
+        return ohwi
+    buf = w.packed.get(p.wform) if isinstance(w, ConvWeight) else None
+    if buf is None:
+        buf = torch.empty((p.wbytes // 4,), dtype=torch.float32, device=ohwi.device)
+        if p.wform == "wt":
+            call("iswm_transpose_weights", ctypes.byref(d), _p(ohwi), _p(buf), _stream())
+        else:
+            call(_PACK_ENTRY[p.wform], ctypes.byref(d), dirn, _p(ohwi), _p(buf), _stream())
+    return buf
+
+
+def _plan_operand(t, op, desc):
+    """(operand tensor, its plane stride | None, descriptor, plan) of a forward / data-gradient call; desc(ld) -> the descriptor
+    for an operand pitch.  A Planes operand stays pre-split when a planes kernel takes the geometry, else it is joined first."""
+    if isinstance(t, Planes):
+        _, _, _, _, ld, ps = pgeom(t)
+        d = desc(ld)
+        p = conv_plan(d, op, True)
+        if p.planes:
+            return t.t, ps, d, p
+        t = t.f32()
+    d = desc(geom(t)[4])
+    return t, None, d, conv_plan(d, op, False)
+
+
+def conv2d_fwd(x, w, g, bias=None, out=None, want_stats=False):
+    """y = conv(x, w) [+ bias]; returns (y, partials|None, (tiles, tile_rows)).  w: OHWI tensor or ConvWeight.  The partials
+    describe the convolution BEFORE the bias (the same bits with and without one): a caller that normalises a biased output
+    takes colstat(y) instead."""
+    _check_w(_ohwi(w), g)
+    if out is None:
+        out = new_act(g.n, g.ho, g.wo, g.cout, x.device)
+    on, oh, ow, oc, ldy = geom(out)
+    assert (on, oh, ow, oc) == (g.n, g.ho, g.wo, g.cout)
+    x, ps, d, p = _plan_operand(x, "fwd", lambda ld: g.desc(ld, ldy))
+    partials, tiles = None, (0, 0)
+    if want_stats:
+        tiles, n2 = (p.tiles, p.tile_rows), 2 * p.tiles * g.cout
+        flat = torch.empty((n2 + (p.tiles if p.rows_stored else 0),), dtype=torch.float32, device=out.device)
+        partials = flat[:n2].view(2, p.tiles, g.cout)
+    wk = conv_weight(w, p, d, 0)
+    with _timed(p.name, [g]):
+        call(p.entry, ctypes.byref(d), _p(x), *([ps] if p.planes else []), _p(wk), _p(bias), _p(out), _p(partials), _stream())
+    return out, partials, tiles
+
+
 class BnStats(object):
     """Request / result of the BatchNorm-backward statistics a planes data gradient can take in its epilogue: `y`, `coef`
     (scale, shift, mean, invstd) and `relu` describe the stage that PRODUCED the conv's input (whose BatchNorm backward will
@@ -418,107 +477,66 @@ class BnStats(object):
         self.mask, self.masked = mask, False
 
 
-_BN_FUSE = True      # False: BatchNorm backward always reduces itself (tests compare both paths)
-
-
-def conv2d_dgrad(dy, w_ohwi, g, x_like_shape, dx=None, accumulate=False, wpk=None, wpk2=None, bn_stats=None):
-    """dx (=|+=) conv^T(dy, w).  x_like_shape = (N,H,W,Cin) of the conv input.  wpk: weight already packed for the
-    data-gradient kernel (wpk2: for the planes kernel).  bn_stats: a BnStats to fill (planes kernel only)."""
-    _check_w(w_ohwi, g)
+def conv2d_dgrad(dy, w, g, x_like_shape, dx=None, accumulate=False, bn_stats=None):
+    """dx (=|+=) conv^T(dy, w).  x_like_shape = (N,H,W,Cin) of the conv input.  w: OHWI tensor or ConvWeight.
+    bn_stats: a BnStats to fill (planes kernel only)."""
+    _check_w(_ohwi(w), g)
     if dx is None:
         assert not accumulate
         dx = new_act(*x_like_shape, dy.device)
     ldx = geom(dx)[4]
-    if isinstance(dy, Planes):
-        _, _, _, _, ldp, ps = pgeom(dy)
-        d = g.desc(ldx, ldp)
-        nb2 = _pl2_bytes(d, 1)
-        if nb2:
-            if wpk2 is None:
-                wpk2 = torch.empty((nb2 // 4,), dtype=torch.float32, device=dx.device)
-                call("iswm_conv2d_pl2_pack_weights", ctypes.byref(d), 1, _p(w_ohwi), _p(wpk2), _stream())
-            if bn_stats is not None and _BN_FUSE and g.cin % 4 == 0:
-                b = bn_stats
-                tiles = _lib.load().iswm_conv2d_dgrad_pl2_stat_tiles(ctypes.byref(d))
-                part = torch.empty((2, tiles, g.cin), dtype=torch.float64, device=dx.device)
-                masky = _relu_code(b.relu) == 1 and b.mask is None
-                pm, ldm, code = None, 0, 2 if masky else 0
-                if b.mask is not None:
-                    pm, _, _, ldm, _ = xrows(b.mask)            # plane 0 = hi
-                    code = 3
-                with _timed(d, 6, g):
-                    call("iswm_conv2d_dgrad_pl2_bn", ctypes.byref(d), _p(dy.t), ps, _p(wpk2), _p(dx), int(bool(accumulate)),
-                         _p(b.y), rows(b.y)[2], _p(b.coef[2]), _p(b.coef[3]), _p(b.coef[0]) if masky else None,
-                         _p(b.coef[1]) if masky else None, code, _p(pm), ldm, _p(part), tiles, _stream())
-                b.partials, b.tiles, b.masked = part, tiles, b.mask is not None
-                return dx
-            with _timed(d, 6, g):
-                call("iswm_conv2d_dgrad_pl2", ctypes.byref(d), _p(dy.t), ps, _p(wpk2), _p(dx), int(bool(accumulate)), _stream())
-            return dx
-        dy = dy.f32()
-    ldy = geom(dy)[4]
-    d = g.desc(ldx, ldy)
-    nb = _packed_bytes(d, 1)
-    if nb:
-        if wpk is None:
-            wpk = torch.empty((nb // 4,), dtype=torch.float32, device=dy.device)
-            call("iswm_conv2d_pack_weights", ctypes.byref(d), 1, _p(w_ohwi), _p(wpk), _stream())
-        with _timed(d, 4, g):
-            call("iswm_conv2d_dgrad_packed", ctypes.byref(d), _p(dy), _p(wpk), _p(dx), int(bool(accumulate)), _stream())
-        return dx
-    if _lib.load().iswm_conv2d_dgrad_wants_wt(ctypes.byref(d)):
-        # bf16x6 math: the matrix cores want the K axis (tap, cout) contiguous -> transposed weights
-        wt = torch.empty((g.cin, g.kh, g.kw, g.cout), dtype=torch.float32, device=dy.device)
-        call("iswm_transpose_weights", ctypes.byref(d), _p(w_ohwi), _p(wt), _stream())
-        with _timed(d, 1, g):
-            call("iswm_conv2d_dgrad_wt", ctypes.byref(d), _p(dy), _p(wt), _p(dx), int(bool(accumulate)), _stream())
-        return dx
-    with _timed(d, 1, g):
-        call("iswm_conv2d_dgrad", ctypes.byref(d), _p(dy), _p(w_ohwi), _p(dx), int(bool(accumulate)), _stream())
+    dy, ps, d, p = _plan_operand(dy, "dgrad", lambda ld: g.desc(ldx, ld))
+    wk = conv_weight(w, p, d, 1)
+    entry, b = p.entry, bn_stats if (p.planes and _BN_FUSE and g.cin % 4 == 0) else None
+    args = [ctypes.byref(d), _p(dy)] + ([ps] if p.planes else []) + [_p(wk), _p(dx), int(bool(accumulate))]
+    if b is not None:                     # the BnStats epilogue, on top of the plan
+        part = torch.empty((2, p.stat_tiles, g.cin), dtype=torch.float64, device=dx.device)
+        masky = _relu_code(b.relu) == 1 and b.mask is None
+        pm, ldm, code = None, 0, 2 if masky else 0
+        if b.mask is not None:
+            pm, _, _, ldm, _ = xrows(b.mask)            # plane 0 = hi
+            code = 3
+        entry += "_bn"
+        args += [_p(b.y), rows(b.y)[2], _p(b.coef[2]), _p(b.coef[3]), _p(b.coef[0]) if masky else None,
+                 _p(b.coef[1]) if masky else None, code, _p(pm), ldm, _p(part), p.stat_tiles]
+    with _timed(p.name, [g]):
+        call(entry, *args, _stream())
+    if b is not None:
+        b.partials, b.tiles, b.masked = part, p.stat_tiles, b.mask is not None
     return dx
 
 
-def _wgrad_planes_ok(x, dy, g, c8):
-    """iswm_conv2d_wgrad_planes_ok on the descriptor the planes weight gradient would get (every precondition of the
-    kernel: channel / pitch alignment, the 2^30-element indexing bound); False -> the fp32-input weight gradient runs"""
-    ldx = pgeom(x)[4]
-    ldy = pgeom(dy)[4] if (isinstance(dy, Planes) and c8 == g.cout) else c8
-    d = ConvDesc(g.n, g.h, g.w, g.cin, g.ho, g.wo, c8, g.kh, g.kw, g.stride, g.pad, g.dil, ldx, ldy)
-    return bool(_lib.load().iswm_conv2d_wgrad_planes_ok(ctypes.byref(d)))
-
-
 def conv2d_wgrad(x, dy, g, dw_ohwi=None):
-    """dw[Cout,KH,KW,Cin] = sum_pixels dy (x) gathered x.  With a pre-split x the planes kernel runs (dy is split
-    here when the producer did not: the few-channel classifier gradient)."""
+    """dw[Cout,KH,KW,Cin] = sum_pixels dy (x) gathered x.  With a pre-split x the planes kernel runs, over Cout padded to 8
+    (dy is split here when the producer did not: the few-channel classifier gradient)."""
     if dw_ohwi is None:
         dw_ohwi = torch.empty((g.cout, g.kh, g.kw, g.cin), dtype=torch.float32, device=x.device)
     _check_w(dw_ohwi, g)
     c8 = (g.cout + 7) // 8 * 8
-    if isinstance(x, Planes) and planes_on() and _wgrad_planes_ok(x, dy, g, c8):
+    p, tgt = None, dw_ohwi
+    if isinstance(x, Planes):
+        # the descriptor the planes kernel would get: its plan holds every precondition (iswm_conv2d_wgrad_planes_ok)
+        d = g.desc(pgeom(x)[4], pgeom(dy)[4] if (isinstance(dy, Planes) and c8 == g.cout) else c8, cout=c8)
+        p = conv_plan(d, "wgrad", True)
+    if p is not None and p.planes:
         if not isinstance(dy, Planes) or c8 != g.cout:
             dyf = as_f32(dy)
             dy = new_planes(g.n, g.ho, g.wo, c8, x.device)
             if c8 != g.cout:
                 zero_channels(dy, g.cout)
+                tgt = torch.empty((c8, g.kh, g.kw, g.cin), dtype=torch.float32, device=x.device)
             split_planes(dyf, out=dy[..., :g.cout] if c8 != g.cout else dy)
-        _, _, _, _, ldx, psx = pgeom(x)
-        _, _, _, _, ldy, psy = pgeom(dy)
-        d = ConvDesc(g.n, g.h, g.w, g.cin, g.ho, g.wo, c8, g.kh, g.kw, g.stride, g.pad, g.dil, ldx, ldy)
-        need = _lib.load().iswm_conv2d_wgrad_planes_workspace(ctypes.byref(d))
-        ws = torch.empty((need // 4,), dtype=torch.float32, device=x.device) if need else None
-        tgt = dw_ohwi if c8 == g.cout else torch.empty((c8, g.kh, g.kw, g.cin), dtype=torch.float32, device=x.device)
-        with _timed(d, 7, g, "+reduce"):
-            call("iswm_conv2d_wgrad_planes", ctypes.byref(d), _p(x.t), psx, _p(dy.t), psy, _p(tgt), _p(ws), need, _stream())
-        if tgt is not dw_ohwi:
-            unpad_weights(tgt, dw_ohwi.permute(0, 3, 1, 2))
-        return dw_ohwi
-    x, dy = as_f32(x), as_f32(dy)
-    ldx, ldy = geom(x)[4], geom(dy)[4]
-    d = g.desc(ldx, ldy)
-    need = _lib.load().iswm_conv2d_wgrad_workspace(ctypes.byref(d))
-    ws = torch.empty((need // 4,), dtype=torch.float32, device=x.device) if need else None
-    with _timed(d, 2, g, "+reduce"):
-        call("iswm_conv2d_wgrad", ctypes.byref(d), _p(x), _p(dy), _p(dw_ohwi), _p(ws), need, _stream())
+        args = (_p(x.t), pgeom(x)[5], _p(dy.t), pgeom(dy)[5], _p(tgt))
+    else:
+        x, dy = as_f32(x), as_f32(dy)
+        d = g.desc(geom(x)[4], geom(dy)[4])
+        p = conv_plan(d, "wgrad", False)
+        args = (_p(x), _p(dy), _p(tgt))
+    ws = torch.empty((p.workspace // 4,), dtype=torch.float32, device=x.device) if p.workspace else None
+    with _timed(p.name + "+reduce", [g]):
+        call(p.entry, ctypes.byref(d), *args, _p(ws), p.workspace, _stream())
+    if tgt is not dw_ohwi:
+        unpad_weights(tgt, dw_ohwi.permute(0, 3, 1, 2))
     return dw_ohwi
 
 
@@ -575,7 +593,7 @@ def aspp_fwd(x, ksize, dil, cout, wpks, want_stats):
     parts = [torch.empty((2, tiles, cout), dtype=torch.float32, device=x.device) for _ in range(nb)] if want_stats else None
     d = aspp_desc(n, h, w, cin, cout, ldx, cout)
     gs = [ConvGeom(x, cout, k, k, 1, dl * (k - 1) // 2, dl) for k, dl in zip(ksize, dil)]
-    with _timed_multi("k_conv_pl2t<false>", gs):
+    with _timed("k_conv_pl2t<false>", gs):
         call("iswm_aspp_fwd", ctypes.byref(d), nb, _int_array(ksize), _int_array(dil), _p(plan), _p(x.t), ps, _ptr_array(wpks),
              _ptr_array(ys), _ptr_array(parts) if parts else None, _stream())
     return ys, parts, tiles
@@ -611,33 +629,10 @@ def aspp_dgrad(dyc, ksize, dil, cin, cout, wpks, dx=None, accumulate=False, x=No
         ws = torch.empty((max(need, 16) // 4,), dtype=torch.float32, device=dyc.device)
         d = aspp_desc(n, h, w, cin, cout, pgeom(x)[4], cout)
         assert geom(dx)[4] == pgeom(x)[4], "iswm_aspp_bwd takes ONE pitch for x and dx"
-    with _timed_multi("k_conv_pl2t<true>", gs):
+    with _timed("k_conv_pl2t<true>", gs):
         call("iswm_aspp_bwd", ctypes.byref(d), nb, _int_array(ksize), _int_array(dil), _p(plan), _p(dyc.t), ps, ld, _ptr_array(wpks),
              _p(dx), int(bool(accumulate)), _p(px), xps, pdw, _p(ws), need, _stream())
     return dx
-
-
-class _timed_multi:
-    """_timed for a launch that computes several conv geometries at once (flops add up)"""
-
-    def __init__(self, name, geoms):
-        self.on = KPROF is not None and KPROF.wants(name)
-        self.name, self.geoms = name, geoms
-
-    def __enter__(self):
-        if self.on:
-            self.a = torch.cuda.Event(enable_timing=True)
-            self.a.record()
-
-    def __exit__(self, *exc):
-        if self.on:
-            b = torch.cuda.Event(enable_timing=True)
-            b.record()
-            g0 = self.geoms[0]
-            tag = "n%d %dx%d c%d->%dx%d aspp d%s" % (g0.n, g0.h, g0.w, g0.alg_cin, len(self.geoms), g0.alg_cout,
-                                                    "/".join(str(g.dil) for g in self.geoms if g.kh > 1))
-            KPROF.add(self.name, self.a, b, sum(g.flops() for g in self.geoms), tag)
-        return False
 
 
 # ---- depthwise conv (groups == channels) -------------------------------------------------------------

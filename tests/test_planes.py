@@ -450,3 +450,74 @@ def test_baseline_config2_per_gpu_workload():
     assert worst[0] <= 3e-3, worst
     tail = max(e for e in errs if e[2].startswith("classifier.classifier."))
     assert tail[0] <= 3e-4, tail
+
+
+# ---- the weight handle (Conv2d.weight_for): pre-packed buffers count only inside their window and while the parameter is untouched ----
+def _retire(pk, convs):
+    pk.end()
+
+
+def _epoch(pk, convs):
+    from iswm_amd import ops
+    ops.weights_changed()
+
+
+def _inplace(pk, convs):
+    with torch.no_grad():
+        for c in convs:
+            c.weight.add_(0.25)
+
+
+def _new_storage(pk, convs):
+    for c in convs:
+        c.weight.data = c.weight.data * 1.5
+
+
+def _two_convs():
+    from iswm_amd.network import _hip
+    torch.manual_seed(5)
+    return _hip.HipSequential(_hip.Conv2d(64, 64, 3, padding=1), _hip.Conv2d(64, 64, 1)).to(dev())
+
+
+def _packs(monkeypatch, fn):
+    """(result of fn(), number of single-weight pack launches it made)"""
+    from iswm_amd import ops
+    seen, real = [], ops.call
+
+    def spy(name, *a):
+        seen.append(name)
+        return real(name, *a)
+    monkeypatch.setattr(ops, "call", spy)
+    out = fn()
+    monkeypatch.setattr(ops, "call", real)
+    return out, sum(n in ("iswm_conv2d_pack_weights", "iswm_conv2d_pl2_pack_weights") for n in seen)
+
+
+@pytest.mark.parametrize("state", [None, _retire, _epoch, _inplace, _new_storage], ids=lambda s: s.__name__ if s else "live")
+def test_weight_handle_reports_packed_buffers_only_while_valid(state, monkeypatch):
+    """A two-conv HipSequential inside the WeightPacker's begin/end window, input 2 x 9 x 11 x 64 (pre-split: the first conv
+    takes the planes kernel, whose weight the packer made).  Right after begin() the handle holds a pre-packed buffer and the
+    forward packs nothing for that conv; after end(), ops.weights_changed(), an in-place weight.add_() or a replaced parameter
+    storage it holds none, the wrappers pack again, and the output equals, bit for bit, that of a model with the same
+    weights that never had a packer."""
+    from iswm_amd import ops
+    from iswm_amd.network import _hip
+    m = _two_convs()
+    convs = [m[0], m[1]]
+    x = ops.split_planes(rnd(2, 9, 11, 64, seed=3).to(dev()))
+    pk = _hip.WeightPacker(m)
+    pk.begin()
+    try:
+        assert all(any(b is not None for b in c.weight_for(k).packed.values()) for c in convs for k in (0, 1))
+        if state is not None:
+            state(pk, convs)
+            assert all(not any(b is not None for b in c.weight_for(k).packed.values()) for c in convs for k in (0, 1))
+        y, packs = _packs(monkeypatch, lambda: m.fwd(x, False))
+    finally:
+        pk.end()
+    fresh = _two_convs()
+    fresh.load_state_dict(m.state_dict())
+    y_fresh, packs_fresh = _packs(monkeypatch, lambda: fresh.fwd(x, False))
+    assert packs_fresh == 2 and packs == (1 if state is None else 2)      # live: only the fp32-input second conv packs its own
+    if state is not None:
+        assert torch.equal(y, y_fresh)

@@ -1,4 +1,5 @@
-"""Host-side cost of one training step: wall time to enqueue a step from an idle GPU, thread CPU time, GPU time."""
+"""Host-side cost of one training step: wall time to enqueue a step from an idle GPU, thread CPU time, GPU time; and the
+wall time to enqueue forward + backward alone from an idle GPU, median (min - max) of 20 (profiles/host_plan_ab.txt)."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -27,3 +28,13 @@ t0 = time.perf_counter()
 for _ in range(5): step()
 t1 = time.perf_counter(); torch.cuda.synchronize(); t2 = time.perf_counter()
 print("5 steps back-to-back: enqueue %.1f ms/step, total %.1f ms/step" % ((t1 - t0) * 200, (t2 - t0) * 200))
+# forward + backward alone, queue drained before each, timed before the final synchronize
+ts = []
+for _ in range(20):
+    opt.zero_grad(); torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    crit(m(x), lab).backward()
+    ts.append((time.perf_counter() - t0) * 1e3)
+    torch.cuda.synchronize()
+ts.sort()
+print("forward+backward enqueue from idle: median %.2f ms (min %.2f - max %.2f) of %d" % ((ts[9] + ts[10]) / 2, ts[0], ts[-1], len(ts)))

@@ -57,20 +57,21 @@ for c in CASES:
     d0 = g.desc(ldp, cout)
     wpk = torch.empty((_pl2_bytes(d0, 0) // 4,), device=dev)
     call("iswm_conv2d_pl2_pack_weights", ctypes.byref(d0), 0, _p(wt), _p(wpk), _stream())
-    tf = med(lambda: ops.conv2d_fwd(x, wt, g, out=y, want_stats=True, wpk2=wpk))
+    tf = med(lambda: ops.conv2d_fwd(x, ops.ConvWeight(wt, {"pl2": wpk}), g, out=y, want_stats=True))
     d1 = g.desc(cin, pgeom(dy)[4])
     nb = _pl2_bytes(d1, 1)
     td = ta = tb = float("nan")
     if nb:
         wpk1 = torch.empty((nb // 4,), device=dev)
         call("iswm_conv2d_pl2_pack_weights", ctypes.byref(d1), 1, _p(wt), _p(wpk1), _stream())
-        td = med(lambda: ops.conv2d_dgrad(dy, wt, g, (n, h, w, cin), dx=dx, wpk2=wpk1))
-        ta = med(lambda: ops.conv2d_dgrad(dy, wt, g, (n, h, w, cin), dx=dx, accumulate=True, wpk2=wpk1))
+        wh = ops.ConvWeight(wt, {"pl2": wpk1})
+        td = med(lambda: ops.conv2d_dgrad(dy, wh, g, (n, h, w, cin), dx=dx))
+        ta = med(lambda: ops.conv2d_dgrad(dy, wh, g, (n, h, w, cin), dx=dx, accumulate=True))
         # the residual-stage form (relu code 3): accumulate + mask by the producer's saved output + its two BatchNorm sums
         yprod = torch.randn(n, h, w, cin, device=dev)
         coef = torch.stack([torch.ones(cin, device=dev), torch.zeros(cin, device=dev), torch.zeros(cin, device=dev), torch.ones(cin, device=dev)])
         try:
-            tb = med(lambda: ops.conv2d_dgrad(dy, wt, g, (n, h, w, cin), dx=dx, accumulate=True, wpk2=wpk1,
+            tb = med(lambda: ops.conv2d_dgrad(dy, wh, g, (n, h, w, cin), dx=dx, accumulate=True,
                                               bn_stats=ops.BnStats(yprod, coef, True, mask=x)))
         except Exception as e:
             print("   bn3 form:", str(e)[:100])
