@@ -42,8 +42,8 @@ def geom(t, dtype=torch.float32):
         ld = t.stride(1)
     elif n > 1:
         ld = t.stride(0)
-    else:
-        ld = c
+    else:                                  # one pixel: a channel slice keeps its buffer's pitch in its strides
+        ld = max(c, t.stride(2))
     ok = (c == 1 or t.stride(3) == 1) and (w == 1 or t.stride(2) == ld) and \
         (h == 1 or t.stride(1) == w * ld) and (n == 1 or t.stride(0) == h * w * ld)
     if not ok or ld < c:
@@ -1297,15 +1297,17 @@ def qconv_fwd(x, w, mul, add, k, stride, pad, dil, relu, lo, inv_s_out, out=None
               cstore=None):
     """int8 implicit-GEMM convolution: x int8 NHWC [N,H,W,Cin] (Cin % 64 == 0), w int8 [Cout_p, KH*KW*Cin] (OHWI,
     Cout_p % 16 == 0), mul / add fp64 [Cout_p] -> `out` (int8, or fp32 when out_f32) of which the first `cstore`
-    channels are written (default Cout_p).  Epilogue: see iswm_qconv_fwd."""
+    channels are written (default Cout_p; the default `out` has cstore channels on a pad4(cstore) pitch).  Epilogue: see
+    iswm_qconv_fwd."""
     cout = w.shape[0]
     cstore = cout if cstore is None else cstore
     if w.dtype != torch.int8 or not w.is_contiguous() or mul.dtype != torch.float64 or add.dtype != torch.float64:
         raise ValueError("qconv: int8 contiguous weights and fp64 mul / add expected")
     n, h, wd, cin, _ = i8geom(x)
     ho, wo = conv_out_size(h, k, stride, pad, dil), conv_out_size(wd, k, stride, pad, dil)
-    if out is None:
-        out = torch.empty((n, ho, wo, cstore), dtype=torch.float32 if out_f32 else torch.int8, device=x.device)
+    if out is None:                                       # the C ABI wants ldy % 4 == 0: a pad4 pitch under a cstore view
+        out = torch.empty((n, ho, wo, (cstore + 3) // 4 * 4), dtype=torch.float32 if out_f32 else torch.int8,
+                          device=x.device)[..., :cstore]
     on, oh, ow, oc, ldy = geom(out, torch.float32 if out_f32 else torch.int8)
     if (on, oh, ow) != (n, ho, wo) or oc < cstore:
         raise ValueError("qconv: out %s cannot hold [%d, %d, %d, %d]" % (tuple(out.shape), n, ho, wo, cstore))

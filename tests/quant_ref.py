@@ -36,6 +36,12 @@ def quantize(x, inv_s, lo):
 
 
 # ---- kernels ----
+def absmax(x, c=None, amax0=0.0):
+    """max(amax0, max |x[..., :c]|) as the fp32 the device holds"""
+    x = np.asarray(x, np.float32)
+    return np.float32(max(np.float32(amax0), np.abs(x[..., :c]).max()))
+
+
 def conv_int(x, w, stride, pad, dil):
     """x int8 [N, H, W, Cin], w int8 [Cout, Cin, KH, KW] -> exact int64 [N, Ho, Wo, Cout] (zero padding)"""
     n, h, wd, cin = x.shape
@@ -45,7 +51,7 @@ def conv_int(x, w, stride, pad, dil):
     wo = (wd + 2 * pad - dil * (kw - 1) - 1) // stride + 1
     xp = np.zeros((n, h + 2 * pad, wd + 2 * pad, cin2), np.float64)
     xp[:, pad:pad + h, pad:pad + wd] = x[..., :cin2]
-    acc = np.zeros((n, ho, wo, cout), np.float64)        # |partial sums| < 2^27: exact in fp64
+    acc = np.zeros((n, ho, wo, cout), np.float64)        # |partial sums| < 2^31 (the kernel's int32): exact in fp64
     wt = np.asarray(w, np.float64)
     for i in range(kh):
         for j in range(kw):

@@ -272,3 +272,72 @@ def test_scene_cli_end_to_end(tmp_path, capsys):
         assert nbad <= 1e-3 * npix
         assert 0.05 < nfg / npix < 0.95, "probabilities do not spread"
     print("scene CLI: window batch 1 and 4 maps %s" % ("bit-identical" if same_maps else "differ"))
+
+
+def test_scene_predictor_on_an_int8_model(tmp_path, capsys):
+    """ScenePredictor over a QuantizedSegmentationModel: the packed result is the same bytes for window batches of 1
+    (six one-window calls), 4 (an assembled logits buffer with a short last batch) and 6 (the single-batch shortcut),
+    and the bytes of scene_maps over six one-window forward_lowres calls, each of which equals the numpy restatement
+    of the INT8 network bit for bit; the command line on the INT8 checkpoint writes the same three maps.  scene_maps
+    itself is held to float64 by test_scene_maps_against_restatement: this pins the route into it."""
+    from iswm_amd import ops, predict, quant
+    from iswm_amd.predict import ScenePredictor, decode_image
+    from oracle.synth import synth_images
+    from tests import quant_cases as Q
+    from tests import quant_ref as QR
+    H, W, T, O = (Q.SCENE[k] for k in ("H", "W", "tile", "overlap"))
+    m, sd = _r50()
+    inp = _frames(str(tmp_path))
+    os.remove(os.path.join(inp, "s1", "a.png"))
+    big = decode_image(os.path.join(inp, "s1", "c.png"))
+    assert big.shape == (H, W, 3) and big.dtype == np.uint8
+    plan = ops.scene_plan(H, W, T, O)
+    rp = S.Plan(H, W, T, O)
+    assert plan.ntiles == Q.SCENE["windows"] and plan.astuple() == rp.astuple()
+    scene = torch.from_numpy(big.copy()).to(dev())
+    with torch.no_grad():
+        x0 = ops.scene_tiles_normalize(scene, plan, 0, plan.ntiles, R.MEAN, R.STD)
+    m.load_state_dict(_spread_head(m, sd, x0), strict=True)            # spread before calibration
+    qm = quant.quantize_model(m, quant.calibrate(m, [synth_images(2, T, T, seed=s).to(dev()) for s in (1, 2)]))
+    st = qm.state_int8()
+
+    # the reference route: one window per call, each pinned to the restatement
+    tiles = []
+    for k in range(plan.ntiles):
+        with torch.no_grad():
+            xk = ops.scene_tiles_normalize(scene, plan, k, 1, R.MEAN, R.STD)
+            assert torch.equal(xk, x0[k:k + 1])
+            yk = qm.forward_lowres(xk)
+            want = QR.forward_body(st, qm.stem(xk).cpu().numpy())
+        assert np.array_equal(yk.cpu().numpy()[..., :2], want), k
+        tiles.append(yk)
+    stacked = torch.cat(tiles)
+    ref = ops.scene_maps(stacked, 2, 1, plan, 0.5, 0.2, 0.7)
+    lay = ops.predict_maps_layout(1, H, W)
+    ref_maps = {k: ref.packed[lay[k]:lay[k] + H * W].view(H, W).cpu().numpy() for k in ("pred", "conf", "band")}
+    ref_stats = ref.stats.cpu().numpy()
+
+    # the restated probabilities spread: the maps are no constant
+    p64 = S.blend(R.softmax_fg(SC.upsample64(stacked.cpu().numpy(), 2, T, T), 1), rp, np.float64)
+    share = float((p64 > 0.5).mean())
+    assert 0.05 <= share <= 0.95, share
+
+    for b in Q.SCENE["tile_batches"]:
+        got = ScenePredictor(qm, dev(), 2, 1, 0.5, 0.2, 0.7, True, True, T, O, tile_batch=b)(big.copy()[None])()
+        assert got["stats"].tobytes() == ref_stats.tobytes(), b
+        for k in ("pred", "conf", "band"):
+            assert got[k].shape == (1, H, W) and np.array_equal(got[k][0], ref_maps[k]), (b, k)
+    assert ref_stats[0, 4] == (ref_maps["pred"] == 255).sum()
+
+    ckpt = os.path.join(str(tmp_path), "m_int8.pth")
+    qm.save_int8(ckpt)
+    out = os.path.join(str(tmp_path), "out")
+    n = predict.main(["--input", inp, "--ckpt", ckpt, "--save_val_results_to", out, "--save_confidence", "--save_binary",
+                      "--tile_size", str(T), "--tile_overlap", str(O), "--batch_size", "4"])
+    text = capsys.readouterr().out
+    assert n == 1 and "INT8 model loaded from" in text and "Error while processing" not in text
+    for kind, k in zip(KINDS, ("pred", "conf", "band")):
+        im = Image.open(os.path.join(out, "s1", "c_%s.png" % kind))
+        assert im.mode == "L" and np.array_equal(np.asarray(im), ref_maps[k]), kind
+    print("INT8 scene: foreground share of the restated probabilities %.4f; batches %s and the command line identical" %
+          (share, list(Q.SCENE["tile_batches"])))
