@@ -524,6 +524,34 @@ int iswm_scene_maps(const float* yl, const iswm_scene_plan* plan, int Hi, int Wi
                     int band_lo, int band_hi, unsigned char* pred, unsigned char* conf, unsigned char* band,
                     float* prob, double* stats, void* workspace, size_t workspace_bytes, iswm_stream_t stream);
 
+/* ---- flip and multi-scale test-time augmentation (predict.hip) ------------------------------
+ * The foreground probability of a frame is averaged over views of it: the frame resampled to Hv x Wv (bilinear,
+ * align_corners=False) and, for a flipped view, mirrored left to right.  At most ISWM_PREDICT_MAX_VIEWS views.
+ * predict_view_normalize: uint8 [N][H][W][3] RGB -> one view as fp32 NCHW [N][3][Hv][Wv].  Per output (y, x):
+ * xs = flip ? Wv - 1 - x : x; the four uint8 taps and weights of source coordinates (y, xs) with scales
+ * (float)H / (float)Hv and (float)W / (float)Wv (the index arithmetic of iswm_bilinear_fwd), their bilinear value in
+ * fp32, then iswm_predict_normalize's (v / 255.0f - mean) / std.  Hv = H, Wv = W, flip = 0 gives
+ * iswm_predict_normalize's bits; flip = 1 those of the mirrored frame.  mean3 / std3 are HOST arrays of 3 floats.
+ * predict_views_maps: the low-resolution NHWC logits of every view, views[v].yl [N][Hi][Wi][ldx] (N, ldx, C, fg common
+ * to all views), -> the maps of iswm_predict_maps at [N][Ho][Wo].  Per output pixel, views in list order:
+ * p_v = iswm_predict_maps's probability of view v at row oh and column (flip ? Wo - 1 - ow : ow), sampled straight from
+ * the view's logits with scales (float)Hi / (float)Ho and (float)Wi / (float)Wo; p = (sum_v p_v) / nviews in fp32.  A
+ * gather: no canvas, no atomics, every output byte written once, bit-reproducible.  A list of one unflipped view is run
+ * as iswm_predict_maps (the same bytes for every C).  Outputs, stats [N][5] and alignment as iswm_predict_maps;
+ * workspace: iswm_predict_views_maps_workspace (= iswm_predict_maps_workspace). */
+#define ISWM_PREDICT_MAX_VIEWS 16
+typedef struct iswm_predict_view {
+    const float* yl;    /* the view's low-resolution logits [N][Hi][Wi][ldx], 16-byte aligned */
+    int Hi, Wi, flip;
+} iswm_predict_view;
+int iswm_predict_view_normalize(const unsigned char* img, int N, int H, int W, int Hv, int Wv, int flip,
+                                const float* mean3, const float* std3, float* out_nchw, iswm_stream_t stream);
+size_t iswm_predict_views_maps_workspace(int N, int H, int W);
+int iswm_predict_views_maps(const iswm_predict_view* views, int nviews, int N, int ldx, int C, int fg, int Ho, int Wo,
+                            float thr, int band_lo, int band_hi, unsigned char* pred, unsigned char* conf,
+                            unsigned char* band, float* prob, double* stats, void* workspace, size_t workspace_bytes,
+                            iswm_stream_t stream);
+
 /* ---- INT8 post-training quantized inference (qconv.hip, quant.hip) ----------------------
  * Activations are int8 NHWC with a pixel pitch in bytes; one symmetric scale s per tensor (value = q * s).
  * qconv: implicit-GEMM convolution on v_mfma_i32_16x16x64_i8, forward only.  x int8 [N][H][W][ldx] (first Cin

@@ -43,6 +43,11 @@ class ScenePlan(Structure):
         return tuple(getattr(self, n) for n, _ in self._fields_)
 
 
+class PredictView(Structure):
+    """iswm_predict_view: one view's low-resolution logits [N][Hi][Wi][ldx] and whether the view was mirrored"""
+    _fields_ = [("yl", c_void_p), ("Hi", c_int), ("Wi", c_int), ("flip", c_int)]
+
+
 P = c_void_p
 _SIGS = {
     # name: (restype, [argtypes])
@@ -175,6 +180,11 @@ _SIGS = {
     "iswm_scene_maps_workspace": (c_size_t, [c_int, c_int]),
     "iswm_scene_maps": (c_int, [P, POINTER(ScenePlan), c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P, P, P, P,
                                 P, P, c_size_t, P]),
+    "iswm_predict_view_normalize": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float),
+                                            P, P]),
+    "iswm_predict_views_maps_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "iswm_predict_views_maps": (c_int, [POINTER(PredictView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                        c_int, c_int, P, P, P, P, P, P, c_size_t, P]),
     "iswm_qconv_weight_bytes": (c_size_t, [POINTER(QConvDesc)]),
     "iswm_qconv_fwd": (c_int, [POINTER(QConvDesc), P, P, P, P, P, c_double, c_double, P, P]),
     "iswm_absmax_workspace": (c_size_t, [c_int64, c_int]),

@@ -11,6 +11,10 @@
 //   * k_scene_tiles_normalize: the windows of a resident uint8 scene -> normalised fp32 NCHW, the same arithmetic;
 //   * k_scene_maps: the logits of all windows -> per scene pixel the ramp-weighted blend of the covering windows' p
 //     (a gather in a fixed order) -> the same maps and statistics.
+// and, for test-time augmentation, the probability averaged over resampled and mirrored views:
+//   * k_predict_view_normalize: resident uint8 frames -> one view (bilinear resample, mirror) as normalised fp32 NCHW;
+//   * k_predict_views_maps: the logits of all views -> per frame pixel the mean of the views' p (a gather in list
+//     order) -> the same maps and statistics.
 // Exactness: the threshold compare is fp32 (torch compares a float32 tensor with a Python float
 // in float32); conf truncates (numpy astype(uint8)); the band compares conf with integer bounds the host derived
 // from the reference's fp64 expression conf / 255.0 >= min_prob, <= max_prob; no float atomics anywhere.
@@ -428,6 +432,172 @@ __global__ __launch_bounds__(PM_BLOCK) void k_scene_maps(const float* __restrict
     }
 }
 
+// ---- flip and multi-scale test-time augmentation -----------------------------------------
+// The probability of a frame is the mean over views of it: the frame resampled to Hv x Wv and, for a flipped view,
+// mirrored left to right.  k_predict_view_normalize makes one view's network input from the resident uint8 frames;
+// k_predict_views_maps gathers every view's low-resolution logits into the frame's maps.
+
+// uint8 NHWC frames -> one view as fp32 NCHW [N][3][Hv][Wv]: F.interpolate(bilinear, align_corners=False) of the
+// frame, then .flip(-1), then k_predict_normalize's arithmetic.  One thread per output pixel, consecutive threads
+// along an output row.  With Hv = H the scale is 1.0f, the source coordinate the integer itself, l1 = 0 and l0 = 1:
+// 1 * (1 * a + 0 * b) + 0 * (...) = a with or without contraction, so the identity view is k_predict_normalize's bits.
+__global__ __launch_bounds__(256) void k_predict_view_normalize(const unsigned char* __restrict__ img, int N, int H,
+                                                                int W, int Hv, int Wv, int flip, float sh, float sw,
+                                                                float m0, float m1, float m2, float s0, float s1,
+                                                                float s2, float* __restrict__ out) {
+    const int64_t HWv = (int64_t)Hv * Wv, M = (int64_t)N * HWv;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M; i += (int64_t)gridDim.x * 256) {
+        const int64_t n = i / HWv, p = i - n * HWv;
+        const int y = (int)(p / Wv), x = (int)(p - (int64_t)y * Wv);
+        const Lerp lh = src_index(sh, y, H);
+        const Lerp lw = src_index(sw, flip ? Wv - 1 - x : x, W);
+        const unsigned char* f = img + n * ((int64_t)H * W * 3);
+        const unsigned char* pa = f + ((int64_t)lh.i0 * W + lw.i0) * 3;
+        const unsigned char* pb = f + ((int64_t)lh.i0 * W + lw.i1) * 3;
+        const unsigned char* pd = f + ((int64_t)lh.i1 * W + lw.i0) * 3;
+        const unsigned char* pe = f + ((int64_t)lh.i1 * W + lw.i1) * 3;
+        const float v0 = lh.l0 * (lw.l0 * (float)pa[0] + lw.l1 * (float)pb[0]) +
+                         lh.l1 * (lw.l0 * (float)pd[0] + lw.l1 * (float)pe[0]);
+        const float v1 = lh.l0 * (lw.l0 * (float)pa[1] + lw.l1 * (float)pb[1]) +
+                         lh.l1 * (lw.l0 * (float)pd[1] + lw.l1 * (float)pe[1]);
+        const float v2 = lh.l0 * (lw.l0 * (float)pa[2] + lw.l1 * (float)pb[2]) +
+                         lh.l1 * (lw.l0 * (float)pd[2] + lw.l1 * (float)pe[2]);
+        float* o = out + n * 3 * HWv + p;
+        o[0] = __fdiv_rn(__fdiv_rn(v0, 255.0f) - m0, s0);
+        o[HWv] = __fdiv_rn(__fdiv_rn(v1, 255.0f) - m1, s1);
+        o[2 * HWv] = __fdiv_rn(__fdiv_rn(v2, 255.0f) - m2, s2);
+    }
+}
+
+// the views of one launch, passed by value: iswm_predict_view plus the two scales the host derived from it
+struct PredictViewArg {
+    const float* yl;
+    int Hi, Wi, flip;
+    float sh, sw;                    // (float)Hi / (float)Ho, (float)Wi / (float)Wo
+};
+struct PredictViewList {
+    PredictViewArg v[ISWM_PREDICT_MAX_VIEWS];
+};
+
+// p of frame pixel (oh, ow) of image n: every view sampled as k_predict_maps samples its image, one bilinear step from
+// the view's logits to the frame, a flipped view at the mirrored column; summed in list order and divided once.  No
+// clamp: every p_v <= 1, so the exact partial sum of k of them is <= k, k is representable, and round-to-nearest is
+// monotone: the fp32 partial sum stays <= k and acc / V <= 1.
+template <int G>
+__device__ __forceinline__ float views_prob(const PredictViewList& vl, int V, int n, int ldx, int C, int fg, int Wo,
+                                            int oh, int ow) {
+    float acc = 0.f;
+    for (int v = 0; v < V; ++v) {
+        const PredictViewArg& a = vl.v[v];
+        const Lerp lh = src_index(a.sh, oh, a.Hi);
+        const Lerp lw = src_index(a.sw, a.flip ? Wo - 1 - ow : ow, a.Wi);
+        const float* base = a.yl + (size_t)n * a.Hi * a.Wi * ldx;
+        const float* pa = base + ((size_t)lh.i0 * a.Wi + lw.i0) * ldx;
+        const float* pb = base + ((size_t)lh.i0 * a.Wi + lw.i1) * ldx;
+        const float* pd = base + ((size_t)lh.i1 * a.Wi + lw.i0) * ldx;
+        const float* pe = base + ((size_t)lh.i1 * a.Wi + lw.i1) * ldx;
+        acc += fg_prob<G>(pa, pb, pd, pe, lh, lw, C, fg);
+    }
+    return __fdiv_rn(acc, (float)V);
+}
+
+// grid (blocks_per_image, N): k_predict_maps's chunks, maps, statistics and order of reduction, with views_prob for p.
+// A gather: nothing is accumulated in memory and every output byte is written once.
+template <int G>
+__global__ __launch_bounds__(PM_BLOCK) void k_predict_views_maps(PredictViewList vl, int V, int ldx, int C, int fg,
+                                                                 int Ho, int Wo, float thr, int lo, int hi,
+                                                                 unsigned char* __restrict__ pred,
+                                                                 unsigned char* __restrict__ conf,
+                                                                 unsigned char* __restrict__ band,
+                                                                 float* __restrict__ prob,
+                                                                 PredictPartial* __restrict__ partials) {
+    const int n = blockIdx.y;
+    const int64_t HW = (int64_t)Ho * Wo;
+    const int64_t p_begin = (int64_t)n * HW, p_end = p_begin + HW;
+    const int64_t k_begin = p_begin / PM_PIX, k_end = (p_end + PM_PIX - 1) / PM_PIX;
+
+    double sum = 0.0;
+    float mn = INFINITY, mx = -INFINITY;
+    long long n_low = 0, n_pred = 0;
+    for (int64_t k = k_begin + (int64_t)blockIdx.x * PM_BLOCK + threadIdx.x; k < k_end;
+         k += (int64_t)gridDim.x * PM_BLOCK) {
+        const int64_t q0 = k * PM_PIX;
+        const int j0 = q0 < p_begin ? (int)(p_begin - q0) : 0;
+        const int j1 = q0 + PM_PIX > p_end ? (int)(p_end - q0) : PM_PIX;
+        int rem = (int)(q0 + j0 - p_begin);
+        int oh = rem / Wo, ow = rem - oh * Wo;
+        unsigned int wp[4] = {0u, 0u, 0u, 0u}, wc[4] = {0u, 0u, 0u, 0u}, wb[4] = {0u, 0u, 0u, 0u};
+        float pv[PM_PIX];
+#pragma unroll
+        for (int j = 0; j < PM_PIX; ++j) {
+            pv[j] = 0.f;
+            if (j < j0 || j >= j1) continue;
+            const float p = views_prob<G>(vl, V, n, ldx, C, fg, Wo, oh, ow);
+            pv[j] = p;
+            const unsigned int vp = p > thr ? 255u : 0u;
+            const unsigned int vc = (unsigned int)(p * 255.0f);
+            const unsigned int vb = ((int)vc >= lo && (int)vc <= hi) ? 255u : 0u;
+            wp[j >> 2] |= vp << (8 * (j & 3));
+            wc[j >> 2] |= vc << (8 * (j & 3));
+            wb[j >> 2] |= vb << (8 * (j & 3));
+            sum += (double)p;
+            mn = fminf(mn, p);
+            mx = fmaxf(mx, p);
+            n_low += p < thr ? 1 : 0;
+            n_pred += vp ? 1 : 0;
+            if (++ow == Wo) {
+                ow = 0;
+                ++oh;
+            }
+        }
+        if (j0 == 0 && j1 == PM_PIX) {
+            *reinterpret_cast<uint4*>(pred + q0) = make_uint4(wp[0], wp[1], wp[2], wp[3]);
+            *reinterpret_cast<uint4*>(conf + q0) = make_uint4(wc[0], wc[1], wc[2], wc[3]);
+            *reinterpret_cast<uint4*>(band + q0) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
+            if (prob) {
+#pragma unroll
+                for (int j = 0; j < PM_PIX; j += 4)
+                    *reinterpret_cast<float4*>(prob + q0 + j) = make_float4(pv[j], pv[j + 1], pv[j + 2], pv[j + 3]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < PM_PIX; ++j) {
+                if (j < j0 || j >= j1) continue;
+                const int sh8 = 8 * (j & 3);
+                pred[q0 + j] = (unsigned char)(wp[j >> 2] >> sh8);
+                conf[q0 + j] = (unsigned char)(wc[j >> 2] >> sh8);
+                band[q0 + j] = (unsigned char)(wb[j >> 2] >> sh8);
+                if (prob) prob[q0 + j] = pv[j];
+            }
+        }
+    }
+
+    // k_predict_maps's workgroup reduction, in its order (kept apart: that kernel's code is pinned, section 13)
+    __shared__ PredictPartial red[PM_BLOCK / 64];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_down(sum, off, 64);
+        mn = fminf(mn, __shfl_down(mn, off, 64));
+        mx = fmaxf(mx, __shfl_down(mx, off, 64));
+        n_low += __shfl_down(n_low, off, 64);
+        n_pred += __shfl_down(n_pred, off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = PredictPartial{sum, mn, mx, n_low, n_pred};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        PredictPartial r = red[0];
+        for (int w = 1; w < PM_BLOCK / 64; ++w) {
+            r.sum += red[w].sum;
+            r.mn = fminf(r.mn, red[w].mn);
+            r.mx = fmaxf(r.mx, red[w].mx);
+            r.n_low += red[w].n_low;
+            r.n_pred += red[w].n_pred;
+        }
+        partials[(size_t)n * gridDim.x + blockIdx.x] = r;
+    }
+}
+
 // one axis of the plan: t = min(T, L); one window when it spans the axis, else windows every s = t - O with the last
 // pulled back.  false: the overlap exceeds half a window.
 static bool scene_plan_axis(int L, int T, int O, int* t, int* s, int* n) {
@@ -592,5 +762,75 @@ extern "C" int iswm_scene_maps(const float* yl, const iswm_scene_plan* plan, int
     int rc = check_launch("scene_maps");
     if (rc) return rc;
     hipLaunchKernelGGL(k_predict_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, part, blocks, stats);
+    return check_launch("predict_stats");
+}
+
+extern "C" int iswm_predict_view_normalize(const unsigned char* img, int N, int H, int W, int Hv, int Wv, int flip,
+                                           const float* mean3, const float* std3, float* out_nchw,
+                                           iswm_stream_t stream) {
+    ISWM_REQUIRE(img && mean3 && std3 && out_nchw, "predict_view_normalize: null pointer");
+    ISWM_REQUIRE(N > 0 && H > 0 && W > 0, "predict_view_normalize: bad size");
+    ISWM_REQUIRE(Hv > 0 && Wv > 0, "predict_view_normalize: bad view size %d x %d", Hv, Wv);
+    ISWM_REQUIRE(flip == 0 || flip == 1, "predict_view_normalize: flip %d is neither 0 nor 1", flip);
+    const float sh = (float)H / (float)Hv, sw = (float)W / (float)Wv;
+    hipLaunchKernelGGL(k_predict_view_normalize, dim3(stream_grid((int64_t)N * Hv * Wv, 256)), dim3(256), 0,
+                       (hipStream_t)stream, img, N, H, W, Hv, Wv, flip, sh, sw, mean3[0], mean3[1], mean3[2], std3[0],
+                       std3[1], std3[2], out_nchw);
+    return check_launch("predict_view_normalize");
+}
+
+extern "C" size_t iswm_predict_views_maps_workspace(int N, int H, int W) {
+    return iswm_predict_maps_workspace(N, H, W);
+}
+
+extern "C" int iswm_predict_views_maps(const iswm_predict_view* views, int nviews, int N, int ldx, int C, int fg,
+                                       int Ho, int Wo, float thr, int band_lo, int band_hi, unsigned char* pred,
+                                       unsigned char* conf, unsigned char* band, float* prob, double* stats,
+                                       void* workspace, size_t workspace_bytes, iswm_stream_t stream) {
+    ISWM_REQUIRE(views && pred && conf && band && stats && workspace, "predict_views_maps: null pointer");
+    ISWM_REQUIRE(nviews >= 1 && nviews <= ISWM_PREDICT_MAX_VIEWS, "predict_views_maps: %d views outside [1, %d]",
+                 nviews, ISWM_PREDICT_MAX_VIEWS);
+    ISWM_REQUIRE(N > 0 && N <= 65535 && Ho > 0 && Wo > 0, "predict_views_maps: bad size");
+    ISWM_REQUIRE(C > 0 && ldx % 4 == 0 && ldx >= ((C + 3) / 4) * 4,
+                 "predict_views_maps: need ldx %% 4 == 0, ldx >= pad4(C)");
+    ISWM_REQUIRE(fg >= 0 && fg < C, "predict_views_maps: foreground class %d outside [0, %d)", fg, C);
+    ISWM_REQUIRE(aligned16(pred) && aligned16(conf) && aligned16(band) && (!prob || aligned16(prob)),
+                 "predict_views_maps: pointers must be 16-byte aligned");
+    PredictViewList vl = {};
+    for (int v = 0; v < nviews; ++v) {
+        ISWM_REQUIRE(views[v].yl, "predict_views_maps: view %d has no logits (null pointer)", v);
+        ISWM_REQUIRE(aligned16(views[v].yl), "predict_views_maps: the logits of view %d must be 16-byte aligned", v);
+        ISWM_REQUIRE(views[v].Hi > 0 && views[v].Wi > 0, "predict_views_maps: view %d has bad size %d x %d", v,
+                     views[v].Hi, views[v].Wi);
+        ISWM_REQUIRE(views[v].flip == 0 || views[v].flip == 1, "predict_views_maps: view %d has flip %d, neither 0 nor 1",
+                     v, views[v].flip);
+        vl.v[v] = PredictViewArg{views[v].yl, views[v].Hi, views[v].Wi, views[v].flip,
+                                 (float)views[v].Hi / (float)Ho, (float)views[v].Wi / (float)Wo};
+    }
+    // one unflipped view is predict_maps itself: run that kernel, so the bytes are its own for every class count (the
+    // compiler contracts bilerp4 per inlining site; iswm_scene_maps does the same for a one-window plan)
+    if (nviews == 1 && !views[0].flip)
+        return iswm_predict_maps(views[0].yl, N, views[0].Hi, views[0].Wi, ldx, C, fg, Ho, Wo, thr, band_lo, band_hi,
+                                 pred, conf, band, prob, stats, workspace, workspace_bytes, stream);
+    const int blocks = predict_blocks_per_image(N, Ho, Wo);
+    ISWM_REQUIRE(workspace_bytes >= (size_t)N * blocks * sizeof(PredictPartial),
+                 "predict_views_maps: workspace too small (see iswm_predict_views_maps_workspace)");
+    const dim3 grid(blocks, N);
+    PredictPartial* part = (PredictPartial*)workspace;
+    const int groups = (C + 3) / 4;
+#define ISWM_VM(G)                                                                                                  \
+    hipLaunchKernelGGL(k_predict_views_maps<G>, grid, dim3(PM_BLOCK), 0, (hipStream_t)stream, vl, nviews, ldx, C, \
+                       fg, Ho, Wo, thr, band_lo, band_hi, pred, conf, band, prob, part)
+    switch (groups > PM_MAX_GROUPS ? 0 : groups) {
+        case 1: ISWM_VM(1); break;
+        case 2: ISWM_VM(2); break;
+        case 3: ISWM_VM(3); break;
+        case 4: ISWM_VM(4); break;
+        default: ISWM_VM(0); break;
+    }
+#undef ISWM_VM
+    int rc = check_launch("predict_views_maps");
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_predict_stats, dim3(N), dim3(64), 0, (hipStream_t)stream, part, blocks, stats);
     return check_launch("predict_stats");
 }

@@ -1270,6 +1270,103 @@ def scene_maps(yl_tiles, num_classes, fg, plan, thr, min_prob, max_prob, want_pr
     return PredictMaps((pred, conf, band, prob, stats, packed))
 
 
+PREDICT_MAX_VIEWS = 16             # ISWM_PREDICT_MAX_VIEWS
+TTA_MAX_SCALES = 8
+TTA_SCALE_RANGE = (0.25, 4.0)
+
+
+def tta_views(H, W, scales, flip):
+    """the ordered views (Hv, Wv, flip) of an H x W frame under test-time augmentation (a pure host function):
+    per scale s in the order given, Hv = max(1, int(H * s + 0.5)) and the same for Wv, the unflipped view and, with
+    `flip`, the horizontally flipped one after it.  1 to 8 distinct scales in [0.25, 4.0], at most 16 views; two
+    scales that round to the same size are still two views.  Anything else raises ValueError naming the value."""
+    if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, int) or not isinstance(W, int) or H < 1 or W < 1:
+        raise ValueError("tta_views: bad frame size %r x %r" % (H, W))
+    if not isinstance(flip, (bool, int)) or flip not in (0, 1):
+        raise ValueError("tta_views: flip %r is neither False nor True" % (flip,))
+    try:
+        scales = list(scales)
+    except TypeError:
+        raise ValueError("tta_views: scales %r is no list of numbers" % (scales,)) from None
+    if not 1 <= len(scales) <= TTA_MAX_SCALES:
+        raise ValueError("tta_views: %d scales %r, need 1 to %d" % (len(scales), scales, TTA_MAX_SCALES))
+    seen = []
+    for s in scales:
+        if isinstance(s, bool) or not isinstance(s, (int, float)):
+            raise ValueError("tta_views: scale %r is no number" % (s,))
+        s = float(s)
+        if not TTA_SCALE_RANGE[0] <= s <= TTA_SCALE_RANGE[1]:             # a NaN fails both compares
+            raise ValueError("tta_views: scale %r outside [%g, %g]" % ((s,) + TTA_SCALE_RANGE))
+        if s in seen:
+            raise ValueError("tta_views: scale %r is given twice" % (s,))
+        seen.append(s)
+    views = []
+    for s in seen:
+        hv, wv = max(1, int(H * s + 0.5)), max(1, int(W * s + 0.5))
+        views.append((hv, wv, False))
+        if flip:
+            views.append((hv, wv, True))
+    if len(views) > PREDICT_MAX_VIEWS:
+        raise ValueError("tta_views: %d views exceed the limit of %d" % (len(views), PREDICT_MAX_VIEWS))
+    return views
+
+
+def predict_view_normalize(img, Hv, Wv, flip, mean, std):
+    """uint8 [N, H, W, 3] RGB on the device -> one test-time-augmentation view as normalised fp32 NCHW [N, 3, Hv, Wv]:
+    the frame resampled (bilinear, align_corners=False), mirrored left to right when `flip`, then predict_normalize's
+    arithmetic.  (H, W, False) is bit-identical to predict_normalize, (H, W, True) to that of the mirrored frame."""
+    if img.dim() == 3:
+        img = img.unsqueeze(0)
+    if img.dim() != 4 or img.shape[3] != 3 or img.dtype != torch.uint8 or not img.is_cuda:
+        raise ValueError("expected a uint8 CUDA [N, H, W, 3] image batch, got %s %s" % (tuple(img.shape), img.dtype))
+    Hv, Wv = int(Hv), int(Wv)
+    if Hv < 1 or Wv < 1:
+        raise ValueError("bad view size %d x %d" % (Hv, Wv))
+    img = img.contiguous()
+    n, h, w, _ = img.shape
+    out = torch.empty((n, 3, Hv, Wv), dtype=torch.float32, device=img.device)
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    call("iswm_predict_view_normalize", _p(img), n, h, w, Hv, Wv, int(bool(flip)), m, s, _p(out), _stream())
+    return out
+
+
+def predict_views_maps(yls, flips, num_classes, fg, H, W, thr, min_prob, max_prob, want_prob=False):
+    """the low-resolution NHWC logits of every view of one frame batch (a list of the model's forward_lowres outputs
+    [N, hl_v, wl_v, ld], one per view, and the views' flip flags) -> PredictMaps at [N, H, W]: per pixel the mean over
+    the views of predict_maps's probability, each view sampled straight from its logits (a flipped one at the
+    mirrored column), then predict_maps's outputs.  A gather: no canvas, no atomics.  One unflipped view gives
+    predict_maps's bytes.  Enqueues only; never synchronises."""
+    yls, flips = list(yls), [bool(f) for f in flips]
+    if not 1 <= len(yls) <= PREDICT_MAX_VIEWS or len(flips) != len(yls):
+        raise ValueError("%d views (%d flip flags), need 1 to %d" % (len(yls), len(flips), PREDICT_MAX_VIEWS))
+    yls = [as_f32(y) for y in yls]
+    n, _, _, c, ld = geom(yls[0])
+    views = (_lib.PredictView * len(yls))()
+    for v, (y, f) in enumerate(zip(yls, flips)):
+        nv, hl, wl, cv, ldv = geom(y)
+        if (nv, cv, ldv) != (n, c, ld) or y.device != yls[0].device:
+            raise ValueError("view %d: logits %s (pitch %d) do not match view 0's %s (pitch %d)" %
+                             (v, tuple(y.shape), ldv, tuple(yls[0].shape), ld))
+        views[v] = _lib.PredictView(y.data_ptr(), hl, wl, int(f))
+    if ld % 4 or ld < (num_classes + 3) // 4 * 4 or num_classes > c:
+        raise ValueError("logits %s (pitch %d) do not hold %d classes" % (tuple(yls[0].shape), ld, num_classes))
+    if not 0 <= fg < num_classes:
+        raise ValueError("foreground class %d outside [0, %d)" % (fg, num_classes))
+    dev = yls[0].device
+    lay = predict_maps_layout(n, H, W)
+    packed = torch.empty(lay["end"], dtype=torch.uint8, device=dev)
+    stats = packed[:40 * n].view(torch.float64).view(n, 5)
+    pred, conf, band = (packed[lay[k]:lay[k] + n * H * W].view(n, H, W) for k in ("pred", "conf", "band"))
+    prob = torch.empty((n, H, W), dtype=torch.float32, device=dev) if want_prob else None
+    lo, hi = band_bounds(min_prob, max_prob)
+    nbytes = _lib.load().iswm_predict_views_maps_workspace(n, H, W)
+    ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=dev)
+    call("iswm_predict_views_maps", views, len(yls), n, ld, int(num_classes), int(fg), int(H), int(W), float(thr),
+         lo, hi, _p(pred), _p(conf), _p(band), _p(prob), _p(stats), _p(ws), nbytes, _stream())
+    return PredictMaps((pred, conf, band, prob, stats, packed))
+
+
 def sgd_step(p, g, buf, lr_dev, momentum, weight_decay, nesterov):
     call("iswm_sgd_step", _p(p), _p(g), _p(buf), p.numel(), _p(lr_dev), float(momentum), float(weight_decay),
          int(bool(nesterov)), _stream())

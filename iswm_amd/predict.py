@@ -2,6 +2,7 @@
 
     python -m iswm_amd.predict --input <dir> --ckpt <checkpoint> --save_val_results_to <out> \\
         [--save_confidence] [--save_binary] [--batch_size B] [--workers W] [--tile_size T [--tile_overlap O]]
+        [--tta_scales S1,S2,... ] [--tta_flip]
 
 Every subfolder of ``--input`` is walked (process_images, predict.py:292-368) and each frame gets
 ``<out>/<subfolder>/<name>_predict.png`` (0/255 foreground mask), plus ``_confidence.png`` (uint8(p * 255), p = the
@@ -24,6 +25,11 @@ Same flags and defaults as the reference's get_argparser (predict.py:19-67).  Di
     pulled back inside the frame, and the overlaps are blended with weights that ramp over O pixels (ScenePredictor;
     DESIGN.md section 13).  ``--batch_size`` then counts windows per device batch and frames are handed over one at
     a time.  A frame no larger than T is one window and gives the whole-frame path's bytes;
+  * new ``--tta_scales S1,S2,...`` (default ``1.0``) and ``--tta_flip``: test-time augmentation.  The foreground
+    probability is the mean over views of the frame, one per scale (the frame resampled bilinearly to
+    int(H * s + 0.5) x int(W * s + 0.5)) and, with ``--tta_flip``, its mirror image after each; the maps are cut from
+    that mean (TTAPredictor).  1 to 8 distinct scales in [0.25, 4.0].  With the defaults the
+    whole-frame path runs unchanged.  Not combined with ``--tile_size``: TTA over windows is not built;
   * ``--binary_threshold`` is accepted and unused, as in the reference (predict.py:223);
   * ``--enable_wave_processing`` is refused: its synthetic "broken area" generator is random and draws with
     OpenCV, which is not a dependency here.  Its flags still parse;
@@ -108,7 +114,34 @@ def get_argparser():
                              "--batch_size then counts windows per device batch")
     parser.add_argument("--tile_overlap", type=int, default=-1,
                         help="overlap of neighbouring windows in pixels (default: tile_size // 8)")
+    parser.add_argument("--tta_scales", type=str, default="1.0",
+                        help="test-time augmentation: comma list of 1 to 8 distinct scales in [0.25, 4.0] whose "
+                             "foreground probabilities are averaged (default: 1.0)")
+    parser.add_argument("--tta_flip", action='store_true',
+                        help="test-time augmentation: add the horizontally mirrored view of every scale")
     return parser
+
+
+def tta_options(parser, opts):
+    """(scales, flip), or None for the defaults (one unflipped view at scale 1: the whole-frame path); bad lists and
+    TTA together with --tile_size are argparse errors"""
+    from . import ops
+    scales = []
+    for item in opts.tta_scales.split(","):
+        try:
+            scales.append(float(item))
+        except ValueError:
+            parser.error("--tta_scales %r: %r is no number" % (opts.tta_scales, item.strip()))
+    try:
+        ops.tta_views(1, 1, scales, opts.tta_flip)
+    except ValueError as e:
+        parser.error("--tta_scales %r: %s" % (opts.tta_scales, e))
+    if scales == [1.0] and not opts.tta_flip:
+        return None
+    if opts.tile_size != 0:
+        parser.error("--tta_scales / --tta_flip cannot be combined with --tile_size: test-time augmentation over "
+                     "windows is not built")
+    return scales, bool(opts.tta_flip)
 
 
 def tile_options(parser, opts):
@@ -369,6 +402,50 @@ class ScenePredictor:
         return wait
 
 
+class TTAPredictor:
+    """predict_batch for process_images with test-time augmentation: one upload, then per view of ops.tta_views
+    ops.predict_view_normalize -> forward_lowres on the whole frame batch with every view's logits kept, one
+    ops.predict_views_maps over all of them, and one copy of stats + the requested maps into pinned host memory.
+    Nothing synchronises before wait()."""
+
+    def __init__(self, model, device, num_classes, fg, pred_threshold, min_prob, max_prob, want_conf, want_band,
+                 scales, flip):
+        self.model, self.device = model, device
+        self.num_classes, self.fg = num_classes, fg
+        self.thr, self.min_prob, self.max_prob = pred_threshold, min_prob, max_prob
+        self.want_conf, self.want_band = want_conf, want_band
+        self.scales, self.flip = tuple(float(s) for s in scales), bool(flip)
+
+    def __call__(self, batch):
+        import torch
+        from . import ops
+        n, h, w, _ = batch.shape
+        views = ops.tta_views(h, w, self.scales, self.flip)
+        pin = torch.from_numpy(np.ascontiguousarray(batch)).pin_memory()
+        with torch.cuda.device(self.device), torch.no_grad():
+            img = pin.to(self.device, non_blocking=True)
+            yls = [self.model.forward_lowres(ops.predict_view_normalize(img, hv, wv, f, MEAN, STD))
+                   for hv, wv, f in views]
+            maps = ops.predict_views_maps(yls, [f for _, _, f in views], self.num_classes, self.fg, h, w, self.thr,
+                                          self.min_prob, self.max_prob)
+            lay = ops.predict_maps_layout(n, h, w)
+            end = lay["band"] + n * h * w if self.want_band else lay["conf"] + n * h * w if self.want_conf else \
+                lay["pred"] + n * h * w
+            host = torch.empty(end, dtype=torch.uint8, pin_memory=True)
+            host.copy_(maps.packed[:end], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+
+        def wait():
+            ev.synchronize()
+            a = host.numpy()
+            stats = a[:40 * n].view(np.float64).reshape(n, 5)
+            pick = (lambda k: a[lay[k]:lay[k] + n * h * w].reshape(n, h, w))
+            return {"pred": pick("pred"), "conf": pick("conf") if self.want_conf else None,
+                    "band": pick("band") if self.want_band else None, "stats": stats}
+        return wait
+
+
 def load_model(model, ckpt_path, ck=None):
     """predict.py:80-91 with the weights-only loader: {"model_state": ...} (this project's and the reference's
     checkpoints) or a bare state dict, `module.` prefixes stripped, strict load.  No file: initial weights.
@@ -390,6 +467,7 @@ def main(argv=None):
     parser = get_argparser()
     opts = parser.parse_args(argv)
     tile_size, tile_overlap = tile_options(parser, opts)
+    tta = tta_options(parser, opts)
     if opts.enable_wave_processing:
         get_argparser().error(WAVE_PROCESSING_REFUSED)
     if opts.batch_size < 1 or opts.workers < 1:
@@ -420,6 +498,10 @@ def main(argv=None):
                                    opts.max_broken_prob, opts.save_confidence, opts.save_binary, tile_size,
                                    tile_overlap, tile_batch=opts.batch_size)
         frames = 1
+    elif tta is not None:
+        predictor = TTAPredictor(model, device, num_classes, fg, opts.pred_threshold, opts.min_broken_prob,
+                                 opts.max_broken_prob, opts.save_confidence, opts.save_binary, tta[0], tta[1])
+        frames = opts.batch_size
     else:
         predictor = DevicePredictor(model, device, num_classes, fg, opts.pred_threshold, opts.min_broken_prob,
                                     opts.max_broken_prob, opts.save_confidence, opts.save_binary)
