@@ -446,7 +446,7 @@ typedef struct iswm_aug_sample {
     int rs_h, rs_w;         /* size after the random rescale */
     int pad;                /* border added on every side by pad_if_needed (0: none) */
     int crop_i, crop_j;     /* crop origin (row, column) in the padded image */
-    int flip;               /* horizontal flip after the crop */
+    int flip;               /* bit 0: horizontal flip after the crop; bit 1 (iswm_augment_batch_ex only): vertical flip */
     int tab_off;
     int ksize_h, ksize_v;
     int reserved;
@@ -454,6 +454,55 @@ typedef struct iswm_aug_sample {
 int iswm_augment_batch(const unsigned char* images, const unsigned char* labels, const void* samples,
                        const int* tables, int B, int crop_h, int crop_w, const float* mean3, const float* std3,
                        float* out_nchw, unsigned char* out_labels, iswm_stream_t stream);
+
+/* ---- rotation, vertical flip and colour jitter (augment.hip) ---------------------------------
+ * The reference's ExtRandomRotation (nearest, no expand, image centre), ExtRandomVerticalFlip and ExtColorJitter
+ * (utils/ext_transforms.py:147,236,429) around the chain above, bit for bit Pillow's arithmetic.  Every sample has a
+ * second record next to its iswm_aug_sample:
+ *   rotation: Pillow's Geometry.c affine_fixed.  The host passes the 16.16 fixed-point coefficients; output pixel
+ *     (x, y) of the rotated tile reads source ((a[2] + y*a[1] + x*a[0]) >> 16, (a[5] + y*a[4] + x*a[3]) >> 16) when
+ *     both lie inside the tile, else image 0 / label 0.  Pillow's exact transposes (180; 90 / 270 of a square tile)
+ *     are the same form with whole-pixel coefficients.  rot_mode 0: the sample is not rotated and not copied.
+ *   ops: up to four colour operations applied in order to the uint8 RGB triple of each output pixel:
+ *     ISWM_AUG_OP_BRIGHTNESS / _CONTRAST / _SATURATION: Image.blend(degenerate, image, factor[op]) with the degenerate
+ *     0 / the rounded mean grey of the whole cropped image as it is when the op runs / the pixel's own grey;
+ *     ISWM_AUG_OP_HUE: RGB -> HSV, H += hue_shift (mod 256), HSV -> RGB (Convert.c).
+ * aug_rotate: one pass; writes the rotated image (uint8 HWC) and label (uint8 HW) of every sample with rot_mode != 0
+ *   at rot_img_off / rot_lbl_off (multiples of 16) of the two scratch arenas; same size as the source tile.  max_hw >=
+ *   every src_h * src_w (sizes the grid).  A record whose copy would end past an arena is left unwritten.
+ * augment_batch_ex: iswm_augment_batch's chain with, per sample, the source read from the scratch arenas when
+ *   rot_mode != 0, bit 1 of iswm_aug_sample.flip = vertical flip after the horizontal one, then the op list, then
+ *   ToTensor / Normalize.  any_contrast != 0 (some list holds a contrast op) runs a pre-pass that sums the grey of every
+ *   such sample in int64: per-workgroup partials in the workspace, summed per sample by one workgroup in index order.
+ *   any_contrast == 0 is the caller's promise that no record holds a contrast op (the records are device memory and the
+ *   entry point does not read them back, as with max_rs and max_hw); a contrast op under a broken promise blends
+ *   against 0, i.e. acts as a brightness op.  Passing 1 is always right.  crop_h * crop_w <= 2^30.
+ *   rot_images / rot_labels may be null when no sample has rot_mode != 0.
+ * iswm_augment_batch_ex_workspace(B, crop_h, crop_w) = bytes of the workspace (needed whatever any_contrast is). */
+#define ISWM_AUG_OP_BRIGHTNESS 0
+#define ISWM_AUG_OP_CONTRAST 1
+#define ISWM_AUG_OP_SATURATION 2
+#define ISWM_AUG_OP_HUE 3
+typedef struct iswm_aug_extra {
+    int rot_mode;           /* 0: none, 1: fixed-point affine map */
+    int a[6];               /* 16.16 fixed point */
+    int n_ops;              /* 0..4 */
+    long long rot_img_off;  /* byte offsets of the rotated copy in the scratch arenas */
+    long long rot_lbl_off;
+    int ops[4];             /* ISWM_AUG_OP_*, in the order they are applied */
+    float factor[4];        /* indexed by op code; factor[ISWM_AUG_OP_HUE] is unused */
+    int hue_shift;          /* 0..255 */
+    int reserved[3];
+} iswm_aug_extra;
+int iswm_aug_rotate(const unsigned char* images, const unsigned char* labels, const void* samples, const void* extras,
+                    int B, long long max_hw, unsigned char* rot_images, size_t rot_images_bytes,
+                    unsigned char* rot_labels, size_t rot_labels_bytes, iswm_stream_t stream);
+size_t iswm_augment_batch_ex_workspace(int B, int crop_h, int crop_w);
+int iswm_augment_batch_ex(const unsigned char* images, const unsigned char* labels, const unsigned char* rot_images,
+                          const unsigned char* rot_labels, const void* samples, const void* extras, const int* tables,
+                          int B, int crop_h, int crop_w, const float* mean3, const float* std3, int any_contrast,
+                          float* out_nchw, unsigned char* out_labels, void* workspace, size_t workspace_bytes,
+                          iswm_stream_t stream);
 
 /* ---- GPU-resident tile store (dataset.hip) ------------------------------------------
  * A data set is decoded once into two uint8 device arenas (images HWC RGB, masks HW); every tile starts at a

@@ -153,6 +153,10 @@ _SIGS = {
     "iswm_loss_bwd_scale": (c_int, [P, c_int64, P, P, c_int, c_int64, P]),
     "iswm_argmax_nchw": (c_int, [P, c_int, c_int, c_int64, P, P]),
     "iswm_augment_batch": (c_int, [P, P, P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P, P]),
+    "iswm_aug_rotate": (c_int, [P, P, P, P, c_int, c_int64, P, c_size_t, P, c_size_t, P]),
+    "iswm_augment_batch_ex_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "iswm_augment_batch_ex": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_int, P,
+                                      P, P, c_size_t, P]),
     "iswm_label_prepare_workspace": (c_size_t, [c_int64]),
     "iswm_label_prepare": (c_int, [P, c_int64, P, P, c_size_t, P]),
     "iswm_label_count_workspace": (c_size_t, [c_int64]),

@@ -84,6 +84,14 @@ def get_argparser():
     parser.add_argument("--device_augment", action='store_true', default=False,
                         help="run the reference's train_transform (random scale / crop / flip / normalise, "
                              "train.py:355-362) as one HIP kernel per batch on uint8 tiles")
+    parser.add_argument("--aug_rotate", type=float, default=0.0, metavar="DEG",
+                        help="device augmentation: ExtRandomRotation(DEG) (nearest, about the tile centre) before the random "
+                             "scale; 0 = off.  Needs --device_augment or --dataset binary")
+    parser.add_argument("--aug_vflip", action='store_true', default=False,
+                        help="device augmentation: ExtRandomVerticalFlip() after the horizontal flip")
+    parser.add_argument("--aug_color_jitter", type=str, default=None, metavar="B,C,S,H",
+                        help="device augmentation: ExtColorJitter(brightness, contrast, saturation, hue) after the flips; "
+                             "four non-negative numbers, H <= 0.5")
     parser.add_argument("--pretrained_backbone", action='store_true', default=False)
     parser.add_argument("--val_metrics", type=str, default='confusion', choices=['confusion', 'sequence'],
                         help="confusion: every validation frame counted into the confusion matrix, best checkpoint on "
@@ -342,21 +350,56 @@ def main(argv=None):
     np.random.seed(opts.random_seed)
     random.seed(opts.random_seed)
 
+    check_augment_flags(opts)
     train_dst, val_dst = get_dataset(opts)
     if opts.dataset == 'binary':
         return _main_resident(opts, train_dst, val_dst, device, rank, world)
     return _main_loader(opts, train_dst, val_dst, device, rank, world)
 
 
+def _augment_flags(opts):
+    """(--aug_rotate, --aug_vflip, --aug_color_jitter); off for an options object built without them"""
+    return getattr(opts, "aug_rotate", 0.0), getattr(opts, "aug_vflip", False), getattr(opts, "aug_color_jitter", None)
+
+
+def check_augment_flags(opts):
+    """--aug_rotate / --aug_vflip / --aug_color_jitter live in the device pipeline only"""
+    rotate, vflip, jitter = _augment_flags(opts)
+    if (rotate or vflip or jitter) and not opts.device_augment and opts.dataset != 'binary':
+        raise ValueError("--aug_rotate, --aug_vflip and --aug_color_jitter act in the device input pipeline: add "
+                         "--device_augment (or train with --dataset binary); the DataLoader path has no such transforms")
+
+
+def _color_jitter_arg(text):
+    try:
+        v = [float(x) for x in text.split(",")]
+    except ValueError:
+        v = []
+    if len(v) != 4 or any(not x >= 0 for x in v) or v[3] > 0.5:
+        raise ValueError("--aug_color_jitter wants B,C,S,H: four non-negative numbers, H <= 0.5 (got %r)" % (text,))
+    return v
+
+
 def _train_transform(opts, et):
-    """the reference's train_transform (train.py:355-362)"""
-    return et.ExtCompose([
+    """the reference's train_transform (train.py:355-362), plus what --aug_rotate, --aug_vflip and --aug_color_jitter add"""
+    rotate, vflip, jitter = _augment_flags(opts)
+    if rotate < 0:
+        raise ValueError("--aug_rotate wants a non-negative angle in degrees (got %r)" % (rotate,))
+    chain = [et.ExtRandomRotation(rotate)] if rotate else []
+    chain += [
         et.ExtRandomScale((0.5, 2.0)),
         et.ExtRandomCrop(size=(opts.crop_size, opts.crop_size), pad_if_needed=True),
         et.ExtRandomHorizontalFlip(),
+    ]
+    if vflip:
+        chain.append(et.ExtRandomVerticalFlip())
+    if jitter:
+        chain.append(et.ExtColorJitter(*_color_jitter_arg(jitter)))
+    chain += [
         et.ExtToTensor(),
         et.ExtNormalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225]),
-    ])
+    ]
+    return et.ExtCompose(chain)
 
 
 def _main_resident(opts, train_dst, val_dst, device, rank, world):

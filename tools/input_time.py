@@ -7,9 +7,10 @@ Tiles are generated into a temporary directory (PNG, blob masks), so the files a
 1. per batch of 16, crop 513 from 513^2 tiles and crop 200 from 200^2 tiles: host time per call (perf_counter around
    the call, device idle at its start) and device-event window of ExtCompose.batch (the parent path: torch.cat of the
    tiles, numpy tables, two blocking uploads) and of ExtCompose.batch_resident, alternated in one process, warm-up
-   excluded, median and range; plus iswm_gather_normalize of 16 tiles;
+   excluded, median and range; plus iswm_gather_normalize of 16 tiles; plus batch_resident with rotation only, colour
+   jitter without and with contrast, and rotation + vertical flip + jitter (DESIGN.md section 15);
 2. training images/s of deeplabv3plus_resnet101 os16, 16 x 513^2: (a) one fixed resident batch (what bench.py times),
-   (b) batch_resident from the store, (c) the parent's --device_augment loop on the same tiles (DataLoader of uint8
+   (b) batch_resident from the store, (b') the same with rotation + vertical flip + jitter, (c) the parent's --device_augment loop on the same tiles (DataLoader of uint8
    tiles, 2 workers started before the timed window, .to(device), ExtCompose.batch), alternated, three rounds each;
 3. one-off cost: decode + upload of 2000 tiles of 200^2 with 4 threads, arena size.
 
@@ -53,9 +54,22 @@ def make_tiles(root, split, n, size, seed):
         Image.fromarray(mask).save(os.path.join(root, split, "masks", "f%05d_mask.png" % k))
 
 
-def compose(crop):
-    return et.ExtCompose([et.ExtRandomScale((0.5, 2.0)), et.ExtRandomCrop(size=(crop, crop), pad_if_needed=True),
-                          et.ExtRandomHorizontalFlip(), et.ExtToTensor(), et.ExtNormalize(MEAN, STD)])
+def compose(crop, rotate=None, vflip=False, jitter=None):
+    chain = [et.ExtRandomRotation(rotate)] if rotate is not None else []
+    chain += [et.ExtRandomScale((0.5, 2.0)), et.ExtRandomCrop(size=(crop, crop), pad_if_needed=True),
+              et.ExtRandomHorizontalFlip()]
+    if vflip:
+        chain.append(et.ExtRandomVerticalFlip())
+    if jitter is not None:
+        chain.append(et.ExtColorJitter(*jitter))
+    return et.ExtCompose(chain + [et.ExtToTensor(), et.ExtNormalize(MEAN, STD)])
+
+
+# the arms of DESIGN.md section 15: batch_resident with the transforms the plain pipeline lacks
+EXT_ARMS = (("rotation only", dict(rotate=30)),
+            ("jitter without contrast", dict(jitter=(0.4, 0, 0.4, 0.1))),
+            ("jitter with contrast", dict(jitter=(0.4, 0.4, 0.4, 0.1))),
+            ("all on", dict(rotate=30, vflip=True, jitter=(0.4, 0.4, 0.4, 0.1))))
 
 
 def one_call(fn):
@@ -119,14 +133,20 @@ def main():
             parent = lambda: comp.batch(*store.tiles(idx))
             resident = lambda: comp.batch_resident(store, idx)
             gather = lambda: store.gather(0, 16, MEAN, STD)
+            arms = [("parent", parent), ("resident", resident), ("gather", gather)]
+            labels = [("parent", "ExtCompose.batch (parent path)"), ("resident", "batch_resident"),
+                      ("gather", "gather_normalize (validation)")]
+            for arm, kw in EXT_ARMS:
+                arms.append((arm, lambda c=compose(size, **kw): c.batch_resident(store, idx)))
+                labels.append((arm, "batch_resident, " + arm))
             for _ in range(4):
-                parent(), resident(), gather()
-            res = {"parent": [], "resident": [], "gather": []}
+                for _name, fn in arms:
+                    fn()
+            res = {name: [] for name, _ in arms}
             for _ in range(reps):
-                for name, fn in (("parent", parent), ("resident", resident), ("gather", gather)):
+                for name, fn in arms:
                     res[name].append(one_call(fn))
-            for name, label in (("parent", "ExtCompose.batch (parent path)"), ("resident", "batch_resident"),
-                                ("gather", "gather_normalize (validation)")):
+            for name, label in labels:
                 say("   %d^2 crop %d  %-30s host %s | device %s" % (size, size, label, spread([r[0] for r in res[name]]),
                                                                  spread([r[1] for r in res[name]])))
         if args.kernels_only:
@@ -180,14 +200,21 @@ def main():
                         yield comp.batch(list(images.to(dev, non_blocking=True)), list(labels.to(dev, non_blocking=True)))
             return train_steps(gen())
 
+        comp_all = compose(513, **dict(EXT_ARMS)["all on"])
+
+        def loop_resident_all():
+            return train_steps(comp_all.batch_resident(store, idx) for idx in order)
+
         say("2. training images/s, deeplabv3plus_resnet101 os16, 16 x 513^2, %d steps after %d warm-up, alternated:" % (steps, warm))
         loop_fixed()
-        rates = {"fixed": [], "resident": [], "parent": []}
+        rates = {"fixed": [], "resident": [], "resident_all": [], "parent": []}
         for _ in range(3):
             rates["fixed"].append(loop_fixed())
             rates["resident"].append(loop_resident())
+            rates["resident_all"].append(loop_resident_all())
             rates["parent"].append(loop_parent())
         for name, label in (("fixed", "one fixed resident batch (no input path)"), ("resident", "resident store + batch_resident"),
+                            ("resident_all", "resident store + batch_resident, rotation + vflip + jitter"),
                             ("parent", "parent --device_augment loop (DataLoader, 2 workers + batch)")):
             say("   %-62s %s" % (label, "  ".join("%6.1f" % r for r in rates[name])))
         del model, opt
