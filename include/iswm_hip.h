@@ -601,7 +601,35 @@ int iswm_predict_views_maps(const iswm_predict_view* views, int nviews, int N, i
                             unsigned char* band, float* prob, double* stats, void* workspace, size_t workspace_bytes,
                             iswm_stream_t stream);
 
-/* ---- INT8 post-training quantized inference (qconv.hip, quant.hip) ----------------------
+/* ---- validation image panels (val_panels.hip) ----------------------------------------------
+ * What save_validation_results (train.py:461-523) draws for a frame, in one launch.  Inputs: x, the normalised fp32
+ * NCHW batch [N][3][H][W]; yl, the classifier's low-resolution NHWC logits [N][Hi][Wi][ldx] (first C channels,
+ * 1 <= C <= 256; ldx % 4 == 0, ldx >= pad4(C)); labels [N][H][W] as class indices 0 .. 255 with 255 = ignore
+ * (label_dtype 0 = uint8, 1 = int64, the low byte is taken); palette, 256 x 3 uint8 RGB on the DEVICE;
+ * denorm_mean3 / denorm_std3, HOST arrays of 3 floats holding M = float32(-mean / std) and S = float32(1 / std).
+ * Outputs, all uint8 on the device, any of them NULL = skipped (an input only skipped outputs need may be NULL too):
+ *   original   [N][H][W][3]  t = ((x - M) / S) * 255.0f in IEEE fp32 (round to nearest, nothing fused), truncated
+ *                            toward zero: Denormalize -> * 255 -> astype(uint8) (utils/utils.py:14-24, train.py:491-492).
+ *                            t < 0 or NaN gives 0 and t > 255 gives 255 -- numpy's wrap-around is not reproduced; no
+ *                            uint8 image reaches either.
+ *   pred       [N][H][W]     the first maximal class of the bilinearly up-sampled logits: iswm_argmax_nchw's strict
+ *                            compare over k_bilinear_to_nchw_fwd's samples, bit for bit the mask the metrics score.
+ *   conf       [N][H][W]     (uint8)(p * 255.0f), p = max_c softmax(l)_c = 1 / sum_c expf(l_c - m), m = max_c l_c,
+ *                            summed in class order, fp32 division (train.py:494-495, 515); prob (fp32, optional) = p.
+ *   target_rgb, pred_rgb [N][H][W][3]  palette[label], palette[pred] (decode_target, train.py:611-618).
+ *   overlay    [N][H][W][3]  (3 * original + 7 * pred_rgb + 5) / 10 per channel in integers: the 0.7-alpha composite.
+ *   error      [N][H][W][3]  label 255: grey (128,128,128); pred == label: black for label 0, white otherwise;
+ *                            label 0, pred != 0: red; label != 0, pred 0: blue; two different foreground classes:
+ *                            magenta.
+ * x, yl and every output pointer 16-byte aligned.  No workspace, no allocation, no synchronisation; two calls give
+ * the same bytes. */
+int iswm_val_panels(const float* x, const float* yl, const void* labels, int label_dtype, int N, int Hi, int Wi,
+                    int ldx, int C, int H, int W, const float* denorm_mean3, const float* denorm_std3,
+                    const unsigned char* palette, unsigned char* original, unsigned char* pred, unsigned char* conf,
+                    float* prob, unsigned char* target_rgb, unsigned char* pred_rgb, unsigned char* overlay,
+                    unsigned char* error, iswm_stream_t stream);
+
+/* ---- INT8 post-training quantized inference (qconv.hip, quant.hip)----------------------
  * Activations are int8 NHWC with a pixel pitch in bytes; one symmetric scale s per tensor (value = q * s).
  * qconv: implicit-GEMM convolution on v_mfma_i32_16x16x64_i8, forward only.  x int8 [N][H][W][ldx] (first Cin
  * channels, Cin % 64 == 0, ldx % 16 == 0, 16-byte aligned), w int8 OHWI [Cout][KH][KW][Cin] (Cout % 16 == 0; rows past

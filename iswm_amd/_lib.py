@@ -189,6 +189,8 @@ _SIGS = {
     "iswm_predict_views_maps_workspace": (c_size_t, [c_int, c_int, c_int]),
     "iswm_predict_views_maps": (c_int, [POINTER(PredictView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                                         c_int, c_int, P, P, P, P, P, P, c_size_t, P]),
+    "iswm_val_panels": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float),
+                                POINTER(c_float), P, P, P, P, P, P, P, P, P, P]),
     "iswm_qconv_weight_bytes": (c_size_t, [POINTER(QConvDesc)]),
     "iswm_qconv_fwd": (c_int, [POINTER(QConvDesc), P, P, P, P, P, c_double, c_double, P, P]),
     "iswm_absmax_workspace": (c_size_t, [c_int64, c_int]),

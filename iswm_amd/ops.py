@@ -13,6 +13,7 @@ import collections
 import ctypes
 import functools
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1215,6 +1216,109 @@ def predict_maps(yl, num_classes, fg, H, W, thr, min_prob, max_prob, want_prob=F
     call("iswm_predict_maps", _p(yl), n, hl, wl, ld, int(num_classes), int(fg), int(H), int(W), float(thr),
          lo, hi, _p(pred), _p(conf), _p(band), _p(prob), _p(stats), _p(ws), nbytes, _stream())
     return PredictMaps((pred, conf, band, prob, stats, packed))
+
+
+VAL_PANELS = ("original", "target_rgb", "pred_rgb", "overlay", "error", "pred", "conf")     # the packed order
+
+
+def val_palette(num_classes):
+    """uint8 [256, 3] RGB colour of every class index.  num_classes == 2: the reference's decode_target
+    (train.py:611-618) -- index 1 white, every other index (255 included) black.  Any other class count: the PASCAL VOC
+    bit-interleave colour map over all 256 indices (the reference paints everything black there)."""
+    pal = np.zeros((256, 3), dtype=np.uint8)
+    if num_classes == 2:
+        pal[1] = 255
+        return pal
+    for i in range(256):
+        c, rgb = i, [0, 0, 0]
+        for j in range(8):
+            for k in range(3):
+                rgb[k] |= ((c >> k) & 1) << (7 - j)
+            c >>= 3
+        pal[i] = rgb
+    return pal
+
+
+def denorm_constants(mean, std):
+    """(M, S) of the reference's Denormalize (utils/utils.py:14-24): -mean / std and 1 / std per channel, the
+    quotients taken in fp64 and rounded once to fp32 (torchvision's normalize casts them to the tensor's dtype)"""
+    mean, std = np.array(mean, dtype=np.float64), np.array(std, dtype=np.float64)
+    return (-mean / std).astype(np.float32), (1 / std).astype(np.float32)
+
+
+def val_panels_layout(n, h, w, want=VAL_PANELS):
+    """byte offsets of the wanted panels in val_panels' packed uint8 buffer, in VAL_PANELS order, each 16-byte aligned
+    (RGB panels [n, h, w, 3], pred / conf [n, h, w]), and its size under "end": the whole buffer comes back to the
+    host in one transfer"""
+    lay, off = {}, 0
+    for k in VAL_PANELS:
+        if k in want:
+            lay[k] = off
+            off += _align16(n * h * w * (1 if k in ("pred", "conf") else 3))
+    lay["end"] = off
+    return lay
+
+
+class ValPanels(tuple):
+    """(original, target_rgb, pred_rgb, overlay, error, pred, conf, prob, packed): uint8 RGB panels [N, H, W, 3], the
+    class-index map pred and the confidence map conf uint8 [N, H, W], prob = max softmax probability fp32 [N, H, W];
+    a panel that was not asked for is None; every uint8 tensor is a view of `packed` (val_panels_layout)"""
+    __slots__ = ()
+    original = property(lambda self: self[0])
+    target_rgb = property(lambda self: self[1])
+    pred_rgb = property(lambda self: self[2])
+    overlay = property(lambda self: self[3])
+    error = property(lambda self: self[4])
+    pred = property(lambda self: self[5])
+    conf = property(lambda self: self[6])
+    prob = property(lambda self: self[7])
+    packed = property(lambda self: self[8])
+
+
+@functools.lru_cache(maxsize=8)
+def _palette_on(num_classes, device):
+    return torch.from_numpy(val_palette(num_classes)).to(device)
+
+
+def val_panels(x, yl, labels, num_classes, mean, std, want=VAL_PANELS, want_prob=False):
+    """the image panels of the reference's save_validation_results (train.py:461-523) for a batch, one launch:
+    x normalised fp32 NCHW [N, 3, H, W], yl the model's forward_lowres logits, labels uint8 / int64 [N, H, W] class
+    indices (255 = ignore) -> ValPanels with the panels named in `want` (VAL_PANELS; see iswm_hip.h for each).
+    Enqueues only; never synchronises."""
+    want = tuple(want)
+    if [k for k in want if k not in VAL_PANELS] or not (want or want_prob):
+        raise ValueError("val_panels: want %r must name at least one of %r" % (want, VAL_PANELS))
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32):
+        raise ValueError("expected a fp32 CUDA [N, 3, H, W] batch, got %s" %
+                         ((tuple(x.shape), x.dtype, x.device) if torch.is_tensor(x) else type(x),))
+    x = x.contiguous()
+    n, _, H, W = x.shape
+    dev = x.device
+    if not (torch.is_tensor(labels) and labels.is_cuda) or tuple(labels.shape) != (n, H, W):
+        raise ValueError("expected CUDA labels [%d, %d, %d], got %s" %
+                         (n, H, W, (tuple(labels.shape), labels.device) if torch.is_tensor(labels) else type(labels)))
+    labels = labels.contiguous()
+    code = _int_code(labels)
+    yl = as_f32(yl)
+    ny, hl, wl, c, ld = geom(yl)
+    if ld % 4 or ld < (num_classes + 3) // 4 * 4 or num_classes > c or not 1 <= num_classes <= 256:
+        raise ValueError("logits %s (pitch %d) do not hold %d classes" % (tuple(yl.shape), ld, num_classes))
+    if ny != n:
+        raise ValueError("logits of %d images for a batch of %d" % (ny, n))
+    lay = val_panels_layout(n, H, W, want)
+    packed = torch.empty(max(lay["end"], 16), dtype=torch.uint8, device=dev)
+    views = {k: packed[lay[k]:lay[k] + n * H * W * (1 if k in ("pred", "conf") else 3)].view(
+        (n, H, W) if k in ("pred", "conf") else (n, H, W, 3)) for k in want}
+    prob = torch.empty((n, H, W), dtype=torch.float32, device=dev) if want_prob else None
+    dm, ds = denorm_constants(mean, std)
+    m3 = (ctypes.c_float * 3)(*[float(v) for v in dm])
+    s3 = (ctypes.c_float * 3)(*[float(v) for v in ds])
+    pal = _palette_on(int(num_classes), dev)
+    out = [views.get(k) for k in VAL_PANELS]
+    call("iswm_val_panels", _p(x), _p(yl), _p(labels), code, n, hl, wl, ld, int(num_classes), int(H),
+         int(W), m3, s3, _p(pal), _p(out[0]), _p(out[5]), _p(out[6]), _p(prob), _p(out[1]), _p(out[2]), _p(out[3]),
+         _p(out[4]), _stream())
+    return ValPanels(tuple(out) + (prob, packed))
 
 
 def scene_plan(H, W, tile, overlap):

@@ -18,7 +18,11 @@ forced by the reference not being runnable as shipped:
   * multi-GPU is one process per GPU (``torchrun --nproc-per-node N -m iswm_amd.train ...``) with RCCL
     gradient all-reduce instead of nn.DataParallel (train.py:970);
   * MLflow logging is used when the package is importable, skipped otherwise; the loss is read back
-    every ``--print_interval`` steps instead of every step (train.py:1051 syncs each iteration).
+    every ``--print_interval`` steps instead of every step (train.py:1051 syncs each iteration);
+  * ``--save_val_results`` defaults to False (the reference: True, train.py:297).  With it, every new best
+    checkpoint -- and a ``--test_only`` run, into ``test_only_iter_<itr>_score_<weighted>`` -- writes the validation
+    images of val_results.save_validation_results under ``--val_results_dir``; ``--save_confidence_map`` adds the
+    confidence map.  Without the flag nothing is written there.
 """
 import argparse
 import math
@@ -36,6 +40,7 @@ from . import network, ops
 from .optim import FusedAdam, FusedAdamW, FusedSGD
 from .parallel import DistributedDataParallelHIP
 from .utils.loss import CrossEntropyLoss, calculate_class_weights, calculate_class_weights_resident
+from .val_results import save_validation_results
 
 
 def get_argparser():
@@ -501,7 +506,13 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
         if ckpt is not None and opts.continue_training and isinstance(ckpt.get("best_score"), dict):
             best_score = ckpt["best_score"]
     if opts.test_only:
-        print((validate_sequence if sequence_val else validate)(model, val_loader, device, opts))
+        score = (validate_sequence if sequence_val else validate)(model, val_loader, device, opts)
+        print(score)
+        if opts.save_val_results and rank == 0:
+            weighted = logged_weighted_score(score) if sequence_val else \
+                0.5 * score["Foreground IoU"] + 0.5 * score["Foreground F1"]
+            save_validation_results(model, val_loader, device, opts, int(ckpt.get("cur_itrs", 0)) if ckpt else 0,
+                                    weighted, prefix="test_only")
         return
     model.train()
     interval_loss = torch.zeros((), device=device)
@@ -537,16 +548,21 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
                     print("Validation @%d: %s" % (cur_itrs, score))
                     if is_best_score(score, best_score):
                         best_score = update_best_score(score)
-                        print("saved", save_best_model(model, optimizer, scheduler, opts, score,
-                                                       logged_weighted_score(score), cur_itrs, best_score))
+                        weighted = logged_weighted_score(score)
+                        path = save_best_model(model, optimizer, scheduler, opts, score, weighted, cur_itrs, best_score)
+                        print("saved", path)
+                        if path and opts.save_val_results:          # train.py:733-737
+                            save_validation_results(model, val_loader, device, opts, cur_itrs, weighted)
                 else:
                     score = validate(model, val_loader, device, opts)
                     weighted = 0.5 * score["Foreground IoU"] + 0.5 * score["Foreground F1"]
                     print("Validation @%d: %s" % (cur_itrs, score))
                     if weighted > best_score:
                         best_score = weighted
-                        print("saved", save_best_model(model, optimizer, scheduler, opts, score, weighted, cur_itrs,
-                                                       best_score))
+                        path = save_best_model(model, optimizer, scheduler, opts, score, weighted, cur_itrs, best_score)
+                        print("saved", path)
+                        if path and opts.save_val_results:
+                            save_validation_results(model, val_loader, device, opts, cur_itrs, weighted)
             if cur_itrs % opts.val_interval == 0 and world > 1:
                 dist.barrier()
             scheduler.step()
