@@ -384,6 +384,32 @@ int iswm_loss_finalize(const float* partials, int blocks, int mode, int64_t npix
 /* grad *= upstream * (mode 0: 1/sums[1]; mode 1: 1/npix; mode 2: 1) */
 int iswm_loss_bwd_scale(float* grad, int64_t n, const float* sums, const float* upstream, int mode,
                         int64_t npix, iswm_stream_t stream);
+/* ---- region-overlap losses (soft Dice / Tversky / focal-Tversky) + weighted CE ---
+ * Over the valid pixels (label != ignore_index and 0 <= label < C), p = softmax:
+ *   I_c = sum p_c [y == c], P_c = sum p_c, G_c = sum [y == c],
+ *   T_c = (I_c + s) / (I_c + alpha (P_c - I_c) + beta (G_c - I_c) + s),
+ *   L = ce_weight * sum(w nll) / sum(w) + overlap_weight * mean_{c in S} max(1 - T_c, 0)^gamma,
+ *   S = the classes >= 1 (classes 0) or all of them (classes 1).  1 <= C <= 8.
+ * fwd: one pass over logits and labels (no per-pixel store) into partials
+ *   [(2 + 3C) * iswm_loss_blocks(B * HW)] and their fixed-order double sums
+ *   sums[2 + 3C] = {sum w nll, sum w, I[C], P[C], G[C]} (device memory); sums[0..1]
+ *   are iswm_loss_fwd's mode-0 sums bit for bit.  Under data parallelism the host
+ *   all-reduces sums before coeffs.
+ * coeffs: sums -> loss[1] and coef[1 + 2C] = {ce_weight / sum w, overlap_weight *
+ *   dL_ov/dI_c [C], overlap_weight * dL_ov/dP_c [C]}, in double on the device; the
+ *   derivative of max(1 - T, 0)^gamma is taken as 0 where 1 - T <= 0.  ce_weight 0
+ *   leaves the CE term out (finite on a batch with no valid pixel).
+ * bwd: reads logits and labels again and writes upstream[0] * dL/dlogits once
+ *   (exactly 0 at invalid pixels); upstream is a device scalar. */
+int iswm_overlap_loss_fwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
+                          const float* class_weight, int ignore_index, float* partials, double* sums,
+                          iswm_stream_t stream);
+int iswm_overlap_loss_coeffs(const double* sums, int C, double ce_weight, double overlap_weight, double alpha,
+                             double beta, double gamma, double smooth, int classes, float* loss, float* coef,
+                             iswm_stream_t stream);
+int iswm_overlap_loss_bwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
+                          const float* class_weight, int ignore_index, const float* coef, const float* upstream,
+                          float* grad, iswm_stream_t stream);
 /* logits.max(1)[1], train.py:644,659 -- ties resolve to the lowest class index */
 int iswm_argmax_nchw(const float* logits, int B, int C, int64_t HW, int64_t* out, iswm_stream_t stream);
 

@@ -151,6 +151,9 @@ _SIGS = {
     "iswm_loss_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, c_float, c_float, c_int, P, P, P]),
     "iswm_loss_finalize": (c_int, [P, c_int, c_int, c_int64, P, P, P]),
     "iswm_loss_bwd_scale": (c_int, [P, c_int64, P, P, c_int, c_int64, P]),
+    "iswm_overlap_loss_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, P, P, P]),
+    "iswm_overlap_loss_coeffs": (c_int, [P, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_int, P, P, P]),
+    "iswm_overlap_loss_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, P, P, P, P]),
     "iswm_argmax_nchw": (c_int, [P, c_int, c_int, c_int64, P, P]),
     "iswm_augment_batch": (c_int, [P, P, P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P, P]),
     "iswm_aug_rotate": (c_int, [P, P, P, P, c_int, c_int64, P, c_size_t, P, c_size_t, P]),

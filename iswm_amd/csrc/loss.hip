@@ -235,6 +235,211 @@ __global__ __launch_bounds__(256) void k_argmax_nchw(const float* __restrict__ l
     }
 }
 
+// ---- region-overlap losses (soft Dice / Tversky / focal-Tversky) next to the weighted CE: two passes -------------------------
+//   V = valid pixels (loss_pixel's rule), p = softmax(z), g = one-hot(y)
+//   I_c = sum_V p_ic g_ic,  P_c = sum_V p_ic,  G_c = sum_V g_ic (an exact count)
+//   D_c = I_c + alpha (P_c - I_c) + beta (G_c - I_c) + s,  T_c = (I_c + s) / D_c,  l_c = max(1 - T_c, 0)^gamma
+//   L   = lambda_ce sum(w nll) / sum(w) + lambda_ov mean_{c in S} l_c
+// CE's gradient needs one global scalar, so k_loss_fwd writes it in the pass that forms the sums.  A Tversky gradient needs
+// per-class coefficients that exist only after the global reduction:
+//   k_overlap_sums      reads logits + labels, writes per-block partials of {sum w nll, sum w, I_c, P_c, G_c}  (no per-pixel store)
+//   k_overlap_finalize  one wave per value: partials -> sums[2 + 3C] in double, fixed order
+//   k_overlap_coeffs    sums -> loss (fp32) and coef = {lambda_ce / sum w, lambda_ov u_c, lambda_ov v_c}, in double, on the device
+//   k_overlap_bwd       reads logits + labels again, recomputes the softmax, writes the finished gradient once
+// Under data parallelism the host all-reduces sums between finalize and coeffs: T_c is then the global batch's.
+// Per pixel at C = 2, uint8 labels: 9 B read + (9 B read + 8 B written) = 26 B; the CE path moves 17 + 16 = 33 B.
+constexpr int OVL_CMAX = 8;
+
+template <typename LabelT, int CT>
+__global__ __launch_bounds__(256) void k_overlap_sums(const float* __restrict__ logits, const LabelT* __restrict__ labels,
+                                                      int Crt, int64_t HW, int64_t npix, const float* __restrict__ cw,
+                                                      int ignore_index, float* __restrict__ partials, int nblocks) {
+    constexpr int UNR = 4, CMAX = CT > 0 ? CT : OVL_CMAX;
+    const int C = CT > 0 ? CT : Crt;
+    __shared__ float red[2 + 3 * CMAX][4];
+    float s1 = 0.f, s2 = 0.f, si[CMAX], sp[CMAX], sg[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) si[c] = sp[c] = sg[c] = 0.f;
+    // the pixel walk of k_loss_fwd: the two CE partials come out bit for bit as iswm_loss_fwd writes them
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i0 < npix; i0 += UNR * stride) {
+        float z[UNR][CMAX];
+        long long y[UNR];
+        bool in[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int64_t i = i0 + u * stride;
+            in[u] = i < npix;
+            const int64_t ii = in[u] ? i : 0;
+            const int64_t b = ii / HW, p = ii - b * HW;
+            y[u] = in[u] ? (long long)labels[ii] : (long long)ignore_index;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) z[u][c] = (in[u] && c < C) ? logits[b * C * HW + c * HW + p] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            if (!in[u]) continue;
+            float coef, m, lg;
+            bool valid;
+            loss_pixel(z[u], C, y[u], cw, ignore_index, 1.f, 0.f, 0, s1, s2, coef, m, lg, valid);
+            if (!valid) continue;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+                if (c < C) {
+                    const float pc = expf(log_softmax(z[u][c], m, lg));
+                    const bool hit = c == (int)y[u];
+                    sp[c] += pc;
+                    si[c] += hit ? pc : 0.f;
+                    sg[c] += hit ? 1.f : 0.f;
+                }
+        }
+    }
+    // lanes -> LDS -> one partial per block and value, fixed order, no atomics
+    for (int o = 32; o > 0; o >>= 1) {
+        s1 += __shfl_down(s1, o);
+        s2 += __shfl_down(s2, o);
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) {
+            si[c] += __shfl_down(si[c], o);
+            sp[c] += __shfl_down(sp[c], o);
+            sg[c] += __shfl_down(sg[c], o);
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[0][wave] = s1;
+        red[1][wave] = s2;
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) {
+            red[2 + c][wave] = si[c];
+            red[2 + CMAX + c][wave] = sp[c];
+            red[2 + 2 * CMAX + c][wave] = sg[c];
+        }
+    }
+    __syncthreads();
+    const int v = threadIdx.x;                  // value index in the [2 + 3C] layout {s1, s2, I[C], P[C], G[C]}
+    if (v < 2 + 3 * C) {
+        const int k = v < 2 ? v : 2 + ((v - 2) / C) * CMAX + (v - 2) % C;
+        partials[(int64_t)v * nblocks + blockIdx.x] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+    }
+}
+
+// block v, one wave: the lane loop and shuffle tree of k_loss_finalize over the partials of value v -- the same additions in the
+// same order (the CE sums come out bit for bit), but the loads are issued 16 at a time: one load per addition is a chain of
+// memory latencies (4112 partials: 65 of them per lane, 17 us in the kernel trace)
+__global__ __launch_bounds__(64) void k_overlap_finalize(const float* __restrict__ partials, int blocks, double* __restrict__ sums) {
+    constexpr int DEPTH = 16;
+    const int lane = threadIdx.x;
+    const float* p = partials + (int64_t)blockIdx.x * blocks;
+    double a = 0.0;
+    int i = lane;
+    for (; i + (DEPTH - 1) * 64 < blocks; i += DEPTH * 64) {
+        float v[DEPTH];
+#pragma unroll
+        for (int k = 0; k < DEPTH; ++k) v[k] = p[i + k * 64];
+#pragma unroll
+        for (int k = 0; k < DEPTH; ++k) a += (double)v[k];
+    }
+    for (; i < blocks; i += 64) a += (double)p[i];
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o);
+    if (lane == 0) sums[blockIdx.x] = a;
+}
+
+// one wave, double: the loss value and the coefficients of the backward pass.  coef = {lambda_ce / sum w, lambda_ov u_c [C],
+// lambda_ov v_c [C]} with u_c = dL_ov/dI_c, v_c = dL_ov/dP_c; l'_c is taken as 0 where 1 - T_c <= 0 (the definition: autograd's
+// 0 * inf there is nan for gamma < 1).  lambda_ce == 0 leaves the CE term out altogether, so an all-ignored batch (sum w == 0) is
+// finite when only the overlap term is asked for.
+__global__ __launch_bounds__(64) void k_overlap_coeffs(const double* __restrict__ sums, int C, double lce, double lov, double alpha,
+                                                       double beta, double gamma, double s, int all, float* __restrict__ loss,
+                                                       float* __restrict__ coef) {
+    const int c = threadIdx.x;                  // lane c: class c (one pow per class, the classes side by side)
+    const int first = all ? 0 : 1;
+    const double inv = 1.0 / (double)(C - first);
+    double l = 0.0;
+    if (c < C) {
+        const double I = sums[2 + c], P = sums[2 + C + c], G = sums[2 + 2 * C + c];
+        const double num = I + s, D = I + alpha * (P - I) + beta * (G - I) + s;
+        const double om = 1.0 - num / D;
+        double dl = 0.0;
+        if (om > 0.0) {
+            l = gamma == 1.0 ? om : pow(om, gamma);
+            dl = -gamma * (l / om);             // -gamma om^(gamma - 1)
+        }
+        const double k = c >= first ? lov * inv * dl / (D * D) : 0.0;
+        l = c >= first ? l : 0.0;
+        coef[1 + c] = (float)(k * (D - num * (1.0 - alpha - beta)));
+        coef[1 + C + c] = (float)(k * (-alpha * num));
+    }
+    double acc = 0.0;
+    for (int k = 0; k < C; ++k) acc += __shfl(l, k);        // fixed order
+    if (c == 0) {
+        coef[0] = lce != 0.0 ? (float)(lce / sums[1]) : 0.f;
+        loss[0] = (float)((lce != 0.0 ? lce * (sums[0] / sums[1]) : 0.0) + lov * acc * inv);
+    }
+}
+
+// for valid i:  dL/dz_ik = upstream [ coef[0] w_y (p_ik - g_ik) + p_ik (q_ik - sum_c p_ic q_ic) ],  q_ic = u_c g_ic + v_c;  else 0
+template <typename LabelT, int CT>
+__global__ __launch_bounds__(256) void k_overlap_bwd(const float* __restrict__ logits, const LabelT* __restrict__ labels, int Crt,
+                                                     int64_t HW, int64_t npix, const float* __restrict__ cw, int ignore_index,
+                                                     const float* __restrict__ coef, const float* __restrict__ upstream,
+                                                     float* __restrict__ grad) {
+    constexpr int UNR = 4, CMAX = CT > 0 ? CT : OVL_CMAX;
+    const int C = CT > 0 ? CT : Crt;
+    const float up = upstream ? upstream[0] : 1.f;
+    const float a = coef[0];
+    float uc[CMAX], vc[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+        uc[c] = c < C ? coef[1 + c] : 0.f;
+        vc[c] = c < C ? coef[1 + C + c] : 0.f;
+    }
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i0 < npix; i0 += UNR * stride) {
+        float z[UNR][CMAX];
+        long long y[UNR];
+        int64_t off[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int64_t i = i0 + u * stride;
+            const bool in = i < npix;
+            const int64_t ii = in ? i : 0;
+            const int64_t b = ii / HW, p = ii - b * HW;
+            off[u] = in ? b * C * HW + p : -1;
+            y[u] = in ? (long long)labels[ii] : (long long)ignore_index;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) z[u][c] = (in && c < C) ? logits[b * C * HW + c * HW + p] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            if (off[u] < 0) continue;
+            const long long yy = y[u];
+            const bool valid = (yy != (long long)ignore_index) && yy >= 0 && yy < C;
+            float m = z[u][0];
+#pragma unroll
+            for (int c = 1; c < CMAX; ++c) m = c < C ? fmaxf(m, z[u][c]) : m;
+            float se = 0.f;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) se += c < C ? expf(z[u][c] - m) : 0.f;
+            const float lg = logf(se);
+            const float aw = valid ? a * (cw ? cw[yy] : 1.f) : 0.f;
+            float pc[CMAX], q[CMAX], dot = 0.f;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) {
+                pc[c] = c < C ? expf(log_softmax(z[u][c], m, lg)) : 0.f;
+                q[c] = (c == (int)yy ? uc[c] : 0.f) + vc[c];
+                dot += pc[c] * q[c];
+            }
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+                if (c < C) {
+                    const float g = c == (int)yy ? 1.f : 0.f;
+                    grad[off[u] + c * HW] = valid ? up * (aw * (pc[c] - g) + pc[c] * (q[c] - dot)) : 0.f;
+                }
+        }
+    }
+}
+
 }  // namespace iswm
 
 using namespace iswm;
@@ -291,4 +496,71 @@ extern "C" int iswm_argmax_nchw(const float* logits, int B, int C, int64_t HW, i
     hipLaunchKernelGGL(k_argmax_nchw, dim3(stream_grid(npix, 256)), dim3(256), 0, (hipStream_t)stream, logits, C,
                        HW, npix, out);
     return check_launch("argmax");
+}
+
+extern "C" int iswm_overlap_loss_fwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
+                                     const float* class_weight, int ignore_index, float* partials, double* sums,
+                                     iswm_stream_t stream) {
+    ISWM_REQUIRE(logits && labels && partials && sums, "overlap_loss_fwd: null pointer");
+    ISWM_REQUIRE(B > 0 && HW > 0, "overlap_loss_fwd: bad shape");
+    ISWM_REQUIRE(C >= 1 && C <= OVL_CMAX, "overlap_loss_fwd: %d classes (the overlap losses take 1 to %d)", C, OVL_CMAX);
+    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "overlap_loss_fwd: labels must be uint8 or int64");
+    const int64_t npix = (int64_t)B * HW;
+    const int blocks = iswm_loss_blocks(npix);
+    hipStream_t s = (hipStream_t)stream;
+#define OLAUNCH(T, CT)                                                                                                \
+    hipLaunchKernelGGL((k_overlap_sums<T, CT>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C, HW, npix, \
+                       class_weight, ignore_index, partials, blocks)
+    if (label_bytes == 1) {
+        if (C == 2) OLAUNCH(uint8_t, 2);
+        else OLAUNCH(uint8_t, 0);
+    } else {
+        if (C == 2) OLAUNCH(int64_t, 2);
+        else OLAUNCH(int64_t, 0);
+    }
+#undef OLAUNCH
+    hipLaunchKernelGGL(k_overlap_finalize, dim3(2 + 3 * C), dim3(64), 0, s, partials, blocks, sums);
+    return check_launch("overlap_loss_fwd");
+}
+
+extern "C" int iswm_overlap_loss_coeffs(const double* sums, int C, double ce_weight, double overlap_weight, double alpha,
+                                        double beta, double gamma, double smooth, int classes, float* loss, float* coef,
+                                        iswm_stream_t stream) {
+    ISWM_REQUIRE(sums && loss && coef, "overlap_loss_coeffs: null pointer");
+    ISWM_REQUIRE(C >= 1 && C <= OVL_CMAX, "overlap_loss_coeffs: %d classes (the overlap losses take 1 to %d)", C, OVL_CMAX);
+    ISWM_REQUIRE(smooth > 0.0 && smooth < INFINITY, "overlap_loss_coeffs: smooth must be positive");
+    ISWM_REQUIRE(alpha >= 0.0 && beta >= 0.0 && alpha < INFINITY && beta < INFINITY,
+                 "overlap_loss_coeffs: alpha and beta must not be negative");
+    ISWM_REQUIRE(gamma > 0.0 && gamma < INFINITY, "overlap_loss_coeffs: gamma must be positive");
+    ISWM_REQUIRE(ce_weight >= 0.0 && overlap_weight >= 0.0 && ce_weight < INFINITY && overlap_weight < INFINITY,
+                 "overlap_loss_coeffs: the term weights must not be negative");
+    ISWM_REQUIRE(classes == 0 || classes == 1, "overlap_loss_coeffs: classes is 0 (foreground) or 1 (all)");
+    ISWM_REQUIRE(classes == 1 || C >= 2, "overlap_loss_coeffs: no foreground class among %d (empty class set)", C);
+    hipLaunchKernelGGL(k_overlap_coeffs, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, C, ce_weight, overlap_weight,
+                       alpha, beta, gamma, smooth, classes, loss, coef);
+    return check_launch("overlap_loss_coeffs");
+}
+
+extern "C" int iswm_overlap_loss_bwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
+                                     const float* class_weight, int ignore_index, const float* coef, const float* upstream,
+                                     float* grad, iswm_stream_t stream) {
+    ISWM_REQUIRE(logits && labels && coef && upstream && grad, "overlap_loss_bwd: null pointer");
+    ISWM_REQUIRE(B > 0 && HW > 0, "overlap_loss_bwd: bad shape");
+    ISWM_REQUIRE(C >= 1 && C <= OVL_CMAX, "overlap_loss_bwd: %d classes (the overlap losses take 1 to %d)", C, OVL_CMAX);
+    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "overlap_loss_bwd: labels must be uint8 or int64");
+    const int64_t npix = (int64_t)B * HW;
+    const int blocks = iswm_loss_blocks(npix);
+    hipStream_t s = (hipStream_t)stream;
+#define OLAUNCH(T, CT)                                                                                               \
+    hipLaunchKernelGGL((k_overlap_bwd<T, CT>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C, HW, npix, \
+                       class_weight, ignore_index, coef, upstream, grad)
+    if (label_bytes == 1) {
+        if (C == 2) OLAUNCH(uint8_t, 2);
+        else OLAUNCH(uint8_t, 0);
+    } else {
+        if (C == 2) OLAUNCH(int64_t, 2);
+        else OLAUNCH(int64_t, 0);
+    }
+#undef OLAUNCH
+    return check_launch("overlap_loss_bwd");
 }

@@ -1001,6 +1001,56 @@ def loss_bwd_scale(grad, sums, upstream, mode, npix):
     return grad
 
 
+OVERLAP_CLASSES = {"foreground": 0, "all": 1}
+
+
+def _overlap_args(logits, labels, weight):
+    if not (logits.dim() == 4 and logits.dtype == torch.float32 and logits.is_cuda):
+        raise ValueError("the overlap loss expects fp32 CUDA logits [B,C,H,W] (there is no CPU fallback)")
+    logits = logits.contiguous()
+    b, c, h, w = logits.shape
+    if c > 8:
+        raise ValueError("the overlap losses take at most 8 classes (got %d)" % c)
+    assert labels.shape == (b, h, w) and labels.dtype in (torch.uint8, torch.int64)
+    assert weight is None or (weight.dtype == torch.float32 and weight.numel() == c and weight.is_cuda)
+    return logits, labels.contiguous(), b, c, h * w
+
+
+def overlap_loss_fwd(logits, labels, weight, ignore_index):
+    """One pass over the logits, nothing stored per pixel -> sums (float64 [2 + 3C], on the device) =
+    {sum w*nll, sum w, I_c [C], P_c [C], G_c [C]} over the valid pixels (include/iswm_hip.h)."""
+    logits, labels, b, c, hw = _overlap_args(logits, labels, weight)
+    blocks = _lib.load().iswm_loss_blocks(b * hw)
+    nv = 2 + 3 * c
+    partials = torch.empty((nv, blocks), dtype=torch.float32, device=logits.device)
+    sums = torch.empty((nv,), dtype=torch.float64, device=logits.device)
+    call("iswm_overlap_loss_fwd", _p(logits), _p(labels), labels.element_size(), b, c, hw, _p(weight), int(ignore_index),
+         _p(partials), _p(sums), _stream())
+    return sums
+
+
+def overlap_loss_coeffs(sums, C, ce_weight, overlap_weight, alpha, beta, gamma, smooth, classes):
+    """sums (this process's, or all-reduced over the ranks) -> (loss fp32 [1], coef fp32 [1 + 2C]) on the device."""
+    if classes not in OVERLAP_CLASSES:
+        raise ValueError("classes is 'foreground' or 'all' (got %r)" % (classes,))
+    assert sums.dtype == torch.float64 and sums.is_cuda and sums.is_contiguous() and sums.numel() == 2 + 3 * C
+    out = torch.empty((2 + 2 * C,), dtype=torch.float32, device=sums.device)     # loss, coef[1 + 2C]
+    call("iswm_overlap_loss_coeffs", _p(sums), int(C), float(ce_weight), float(overlap_weight), float(alpha), float(beta),
+         float(gamma), float(smooth), OVERLAP_CLASSES[classes], _p(out), _p(out[1:]), _stream())
+    return out[:1], out[1:]
+
+
+def overlap_loss_bwd(logits, labels, weight, ignore_index, coef, upstream):
+    """The second pass: upstream[0] * dL/dlogits, written once (upstream: fp32 device scalar [1])."""
+    logits, labels, b, c, hw = _overlap_args(logits, labels, weight)
+    assert coef.dtype == torch.float32 and coef.numel() == 1 + 2 * c and coef.is_cuda
+    assert upstream.dtype == torch.float32 and upstream.numel() == 1 and upstream.is_cuda
+    grad = torch.empty_like(logits)
+    call("iswm_overlap_loss_bwd", _p(logits), _p(labels), labels.element_size(), b, c, hw, _p(weight), int(ignore_index),
+         _p(coef), _p(upstream), _p(grad), _stream())
+    return grad
+
+
 def argmax_nchw(logits):
     logits = logits.contiguous()
     b, c, h, w = logits.shape

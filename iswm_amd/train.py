@@ -39,12 +39,28 @@ from torch.utils import data
 from . import network, ops
 from .optim import FusedAdam, FusedAdamW, FusedSGD
 from .parallel import DistributedDataParallelHIP
-from .utils.loss import CrossEntropyLoss, calculate_class_weights, calculate_class_weights_resident
+from .utils.loss import CrossEntropyLoss, DiceLoss, TverskyLoss, calculate_class_weights, calculate_class_weights_resident
 from .val_results import save_validation_results
 
 
+class _ArgParser(argparse.ArgumentParser):
+    """refuses, at parse time, the combinations of the criterion options that no criterion can be built from"""
+
+    def parse_known_args(self, args=None, namespace=None):
+        opts, rest = super().parse_known_args(args, namespace)
+        if opts.overlap_loss == 'none' and opts.ce_weight == 0:
+            self.error("--ce_weight 0 with --overlap_loss none leaves no loss term")
+        if opts.ce_weight < 0 or opts.overlap_weight < 0:
+            self.error("--ce_weight and --overlap_weight must not be negative")
+        if not opts.overlap_smooth > 0:
+            self.error("--overlap_smooth must be positive")
+        if opts.tversky_alpha < 0 or opts.tversky_beta < 0 or not opts.tversky_gamma > 0:
+            self.error("--tversky_alpha and --tversky_beta must not be negative, --tversky_gamma must be positive")
+        return opts, rest
+
+
 def get_argparser():
-    parser = argparse.ArgumentParser()
+    parser = _ArgParser()
     parser.add_argument("--data_root", type=str, default='./datasets/data', help="path to Dataset")
     parser.add_argument("--dataset", type=str, default='synthetic', choices=['synthetic', 'binary'])
     parser.add_argument("--num_classes", type=int, default=None)
@@ -103,6 +119,17 @@ def get_argparser():
                              "0.5*FG-IoU + 0.5*FG-F1; sequence: the reference's validate_and_save (train.py:620-745) -- "
                              "sliding windows of --sequence_length frames ordered by file name, the temporal / front / "
                              "region evaluators, best checkpoint by is_best_score")
+    parser.add_argument("--overlap_loss", type=str, default='none', choices=['none', 'dice', 'tversky', 'focal_tversky'],
+                        help="add a region-overlap term to the criterion: soft Dice, Tversky(alpha, beta) or focal-Tversky "
+                             "(Tversky raised to --tversky_gamma); --loss_type still selects the CE term's class weights")
+    parser.add_argument("--overlap_weight", type=float, default=1.0, help="factor of the overlap term")
+    parser.add_argument("--ce_weight", type=float, default=1.0, help="factor of the CE term; 0 = overlap term only")
+    parser.add_argument("--tversky_alpha", type=float, default=0.3, help="false-positive weight (tversky, focal_tversky)")
+    parser.add_argument("--tversky_beta", type=float, default=0.7, help="false-negative weight (tversky, focal_tversky)")
+    parser.add_argument("--tversky_gamma", type=float, default=0.75, help="exponent of focal_tversky")
+    parser.add_argument("--overlap_smooth", type=float, default=1.0, help="smoothing constant of the overlap term (> 0)")
+    parser.add_argument("--overlap_classes", type=str, default='foreground', choices=['foreground', 'all'],
+                        help="classes the overlap term averages over: every class but 0, or all")
     return parser
 
 
@@ -209,7 +236,16 @@ def setup_scheduler(optimizer, opts):
 
 
 def setup_criterion(opts, class_weights, group=None):
-    """train.py:454-459"""
+    """train.py:454-459; with --overlap_loss the same CE (times --ce_weight) plus a Dice / Tversky / focal-Tversky term"""
+    weight = None if opts.loss_type == 'ce_loss' else class_weights
+    kind = getattr(opts, 'overlap_loss', 'none')
+    if kind != 'none':
+        common = dict(smooth=opts.overlap_smooth, classes=opts.overlap_classes, ce_weight=opts.ce_weight,
+                      overlap_weight=opts.overlap_weight, weight=weight, ignore_index=255, group=group)
+        if kind == 'dice':
+            return DiceLoss(**common)
+        return TverskyLoss(alpha=opts.tversky_alpha, beta=opts.tversky_beta,
+                           gamma=opts.tversky_gamma if kind == 'focal_tversky' else 1.0, **common)
     if opts.loss_type == 'ce_loss':
         return CrossEntropyLoss(ignore_index=255, reduction='mean', group=group)
     return CrossEntropyLoss(weight=class_weights, ignore_index=255, reduction='mean', group=group)

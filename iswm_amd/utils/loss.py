@@ -92,6 +92,68 @@ class FocalLoss(nn.Module):
                              self.group)
 
 
+class _OverlapLossFn(torch.autograd.Function):
+    """ce_weight * weighted CE + overlap_weight * Tversky term on the two-pass kernels (csrc/loss.hip): the forward pass
+    stores nothing per pixel, the backward pass reads the logits again and writes the finished gradient once.  With `group`
+    the sums are all-reduced before the coefficients are formed, so every T_c is the global batch's and the SUM gradient
+    all-reduce of parallel.py yields the gradient of the global loss."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, ignore_index, params, group):
+        sums = ops.overlap_loss_fwd(logits, labels, weight, ignore_index)
+        if group is not None:
+            import torch.distributed as dist
+            dist.all_reduce(sums, group=group)
+        loss, coef = ops.overlap_loss_coeffs(sums, logits.shape[1], *params)
+        ctx.save_for_backward(logits, labels, weight, coef)
+        ctx.ignore_index = ignore_index
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, upstream):
+        logits, labels, weight, coef = ctx.saved_tensors
+        up = upstream.reshape(1).contiguous().to(torch.float32)
+        grad = ops.overlap_loss_bwd(logits, labels, weight, ctx.ignore_index, coef, up)
+        return grad, None, None, None, None, None
+
+
+class TverskyLoss(nn.Module):
+    """ce_weight * CrossEntropyLoss(weight, ignore_index) + overlap_weight * mean over the chosen classes of
+    (1 - T_c)^gamma, T_c = (I_c + smooth) / (I_c + alpha FP_c + beta FN_c + smooth) on softmax probabilities over the
+    pixels the CE counts.  beta > alpha favours recall; gamma != 1 is the focal-Tversky loss.  classes: 'foreground'
+    (every class but 0) or 'all'.  At most 8 classes."""
+
+    def __init__(self, alpha=0.3, beta=0.7, gamma=1.0, smooth=1.0, classes='foreground', ce_weight=0.0, overlap_weight=1.0,
+                 weight=None, ignore_index=255, group=None):
+        super().__init__()
+        if not smooth > 0:
+            raise ValueError("smooth must be positive (it keeps the empty and all-ignored cases finite)")
+        if alpha < 0 or beta < 0 or not gamma > 0:
+            raise ValueError("alpha and beta must not be negative and gamma must be positive")
+        if ce_weight < 0 or overlap_weight < 0:
+            raise ValueError("ce_weight and overlap_weight must not be negative")
+        if classes not in ops.OVERLAP_CLASSES:
+            raise ValueError("classes is 'foreground' or 'all' (got %r)" % (classes,))
+        self.register_buffer('weight', None if weight is None else weight.detach().float().clone())
+        self.params = (float(ce_weight), float(overlap_weight), float(alpha), float(beta), float(gamma), float(smooth), classes)
+        self.ignore_index = ignore_index
+        self.group = group
+
+    def forward(self, inputs, targets):
+        targets = _check(inputs, targets)
+        w = None if self.weight is None else self.weight.to(inputs.device)
+        return _OverlapLossFn.apply(inputs, targets, w, self.ignore_index, self.params, self.group)
+
+
+class DiceLoss(TverskyLoss):
+    """soft Dice: TverskyLoss with alpha = beta = 0.5"""
+
+    def __init__(self, **kw):
+        if 'alpha' in kw or 'beta' in kw:
+            raise TypeError("DiceLoss fixes alpha = beta = 0.5; use TverskyLoss for other values")
+        super().__init__(alpha=0.5, beta=0.5, **kw)
+
+
 def create_loss(loss_type="focal", temporal_loss="none", temporal_weight=0.5, **kwargs):
     """reference utils/loss.py:37-39"""
     return FocalLoss(**kwargs)
