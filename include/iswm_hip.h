@@ -709,6 +709,33 @@ int iswm_adam_step(float* p, const float* g, float* m, float* v, int64_t n, cons
                    float beta1, float beta2, float eps, float weight_decay, int decoupled,
                    iswm_stream_t stream);
 
+/* ---- gradient-norm clipping and EMA weights inside the step ------------------------
+ * grad_sqnorm: sum of g[i]^2 over one range, left as one double per workgroup in `slots`
+ * (iswm_grad_sqnorm_slots() doubles).  accumulate == 0 starts a total (every slot is written),
+ * != 0 adds this range to the total the earlier calls on the same stream left there.  No atomics;
+ * the launch geometry depends on n alone, so the same input gives the same bits.  g 16-byte
+ * aligned, any n > 0 (float4 loads and a scalar tail); double accumulation throughout. */
+int iswm_grad_sqnorm_slots(void);
+int iswm_grad_sqnorm(const float* g, int64_t n, double* slots, int accumulate, iswm_stream_t stream);
+/* clip_finalize: one workgroup adds the slots in a fixed order (double) and writes
+ * clip_dev[0] = coef = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_; a NaN norm
+ * gives a NaN coef), clip_dev[1] = norm = (float)sqrt(sum), and sum as ONE double over clip_dev[2..3]
+ * (clip_dev: 4 floats, 8-byte aligned).  max_norm > 0.  The host reads nothing back. */
+int iswm_clip_finalize(const double* slots, float max_norm, float* clip_dev, iswm_stream_t stream);
+/* The steps above with two optional operands.  clip_dev (or NULL): the step uses g * clip_dev[0], one
+ * fp32 multiply as g is loaded; the gradient arena is NOT modified.  ema (or NULL; the arena's layout):
+ * after the parameter update ema += hyper_dev[3] * (p_new - ema), hyper_dev[3] = 1 - decay_t.
+ * hyper_dev is the 4-float block {lr, bias_correction1, bias_correction2, 1 - decay_t} (SGD reads
+ * slots 0 and 3).  Otherwise the arithmetic is that of iswm_sgd_step / iswm_adam_step operation for
+ * operation: with coef == 1.0f and ema == NULL the results are bit-identical to theirs. */
+int iswm_sgd_step_ex(float* p, const float* g, float* buf, int64_t n, const float* hyper_dev, float momentum,
+                     float weight_decay, int nesterov, const float* clip_dev, float* ema, iswm_stream_t stream);
+int iswm_adam_step_ex(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper_dev,
+                      float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                      const float* clip_dev, float* ema, iswm_stream_t stream);
+/* swap_f32: a[i] <-> b[i] for i < n, in place; both 16-byte aligned, the ranges disjoint */
+int iswm_swap_f32(float* a, float* b, int64_t n, iswm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

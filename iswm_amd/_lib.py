@@ -204,6 +204,12 @@ _SIGS = {
     "iswm_qbilinear": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_double, P, c_int, P]),
     "iswm_sgd_step": (c_int, [P, P, P, c_int64, P, c_float, c_float, c_int, P]),
     "iswm_adam_step": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, c_int, P]),
+    "iswm_grad_sqnorm_slots": (c_int, []),
+    "iswm_grad_sqnorm": (c_int, [P, c_int64, P, c_int, P]),
+    "iswm_clip_finalize": (c_int, [P, c_float, P, P]),
+    "iswm_sgd_step_ex": (c_int, [P, P, P, c_int64, P, c_float, c_float, c_int, P, P, P]),
+    "iswm_adam_step_ex": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, c_int, P, P, P]),
+    "iswm_swap_f32": (c_int, [P, P, c_int64, P]),
 }
 
 EXPORTS = tuple(_SIGS)

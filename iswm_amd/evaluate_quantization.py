@@ -50,6 +50,8 @@ def get_argparser():
                         help="Directory to save visualization images.")
     parser.add_argument("--model", type=str, default='deeplabv3plus_resnet50', choices=_model_names(),
                         help="model name")
+    parser.add_argument("--use_ema", action='store_true',
+                        help="evaluate and quantize the checkpoint's EMA weights (a checkpoint of train --ema_decay)")
     return parser
 
 
@@ -143,7 +145,7 @@ def main(argv=None):
     print("Loading FP32 model...")
     model = network.modeling.__dict__[opts.model](num_classes=2, output_stride=opts.output_stride,
                                                   pretrained_backbone=False)
-    model = load_model(model, opts.fp32_ckpt).to(dev).eval()
+    model = load_model(model, opts.fp32_ckpt, use_ema=opts.use_ema).to(dev).eval()
 
     print("\nCreating INT8 model from FP32 model...")
     print("Running calibration for INT8 model...")

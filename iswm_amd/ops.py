@@ -1531,6 +1531,59 @@ def adam_step(p, g, m, v, hyper_dev, beta1, beta2, eps, weight_decay, decoupled)
          float(eps), float(weight_decay), int(bool(decoupled)), _stream())
 
 
+# ---- gradient-norm clipping and EMA weights inside the step (csrc/optim.hip) --------------------
+CLIP_COEF, CLIP_NORM = 0, 1          # slots of the 4-float clip block; floats 2..3 hold the sum of squares as one double
+
+
+def new_clip_state(device):
+    """(slots, clip): the double partials iswm_grad_sqnorm leaves and the 4-float block iswm_clip_finalize writes"""
+    return (torch.zeros(_lib.load().iswm_grad_sqnorm_slots(), dtype=torch.float64, device=device),
+            torch.zeros(4, dtype=torch.float32, device=device))
+
+
+def grad_sqnorm(g, slots, accumulate=False):
+    """adds sum(g^2) of a flat fp32 range into `slots` (accumulate) or starts a new total there; enqueues only"""
+    if g.dtype != torch.float32 or g.dim() != 1 or not g.is_contiguous() or slots.dtype != torch.float64 or \
+            slots.numel() < _lib.load().iswm_grad_sqnorm_slots() or not slots.is_contiguous():
+        raise ValueError("grad_sqnorm: a flat fp32 range and the fp64 slots of new_clip_state expected")
+    call("iswm_grad_sqnorm", _p(g), g.numel(), _p(slots), int(bool(accumulate)), _stream())
+
+
+def clip_finalize(slots, max_norm, clip):
+    """clip[0] = min(1, max_norm / (norm + 1e-6)), clip[1] = norm, clip[2:4] (as one double) = sum of squares"""
+    if clip.dtype != torch.float32 or clip.numel() != 4 or not clip.is_contiguous():
+        raise ValueError("clip_finalize: a 4-float device block expected")
+    call("iswm_clip_finalize", _p(slots), float(max_norm), _p(clip), _stream())
+
+
+def clip_sumsq(clip):
+    """the double sum of squares behind floats 2..3 of a clip block (a 0-dim view, no copy)"""
+    return clip[2:4].view(torch.float64)[0]
+
+
+def sgd_step_ex(p, g, buf, hyper_dev, momentum, weight_decay, nesterov, clip=None, ema=None):
+    """iswm_sgd_step with g * clip[0] at the load of g (g itself untouched) and ema += hyper_dev[3] * (p_new - ema)"""
+    if hyper_dev.numel() < 4 or (ema is not None and ema.numel() != p.numel()):
+        raise ValueError("sgd_step_ex: a 4-float hyper block and an ema range of p's size expected")
+    call("iswm_sgd_step_ex", _p(p), _p(g), _p(buf), p.numel(), _p(hyper_dev), float(momentum), float(weight_decay),
+         int(bool(nesterov)), _p(clip), _p(ema), _stream())
+
+
+def adam_step_ex(p, g, m, v, hyper_dev, beta1, beta2, eps, weight_decay, decoupled, clip=None, ema=None):
+    if hyper_dev.numel() < 4 or (ema is not None and ema.numel() != p.numel()):
+        raise ValueError("adam_step_ex: a 4-float hyper block and an ema range of p's size expected")
+    call("iswm_adam_step_ex", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper_dev), float(beta1), float(beta2),
+         float(eps), float(weight_decay), int(bool(decoupled)), _p(clip), _p(ema), _stream())
+
+
+def swap_f32(a, b):
+    """a <-> b in place (two disjoint flat fp32 ranges of one size)"""
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.numel() != b.numel() or \
+            not a.is_contiguous() or not b.is_contiguous():
+        raise ValueError("swap_f32: two contiguous fp32 ranges of one size expected")
+    call("iswm_swap_f32", _p(a), _p(b), a.numel(), _stream())
+
+
 # ---- INT8 post-training quantized inference (csrc/qconv.hip, csrc/quant.hip; iswm_amd/quant.py) ---------------------
 # int8 activations are NHWC torch.int8 tensors (pitched views allowed, pitch in bytes); one symmetric scale per tensor.
 def i8geom(t):

@@ -8,7 +8,18 @@ CosineAnnealingLR (train.py:446-452), ``state_dict()`` and ``zero_grad()`` work 
 but all parameters live in ONE fp32 allocation (ParamArena), gradients in a second and
 optimizer state in a third, so a step is a single kernel launch over 40-59 M elements and
 the gradient arena can be all-reduced in large contiguous buckets with no copies.
+
+Two things ride inside that launch, both off until asked for and neither a param-group key, so
+``state_dict()`` is the stock optimizer's either way:
+  * ``set_grad_clip(max_norm)`` -- torch.nn.utils.clip_grad_norm_'s global L2 norm over the stepped ranges, taken by a
+    deterministic two-stage double-precision reduction; the step multiplies g by the clip factor as it loads it.  UNLIKE
+    torch, the gradients themselves are not rescaled: ``p.grad`` after ``step()`` still holds the unclipped values.
+  * ``enable_ema(decay)`` -- a fourth flat buffer with the arena's layout that follows the weights,
+    ema += (1 - d_t) (p_new - ema); ``ema_weights()`` swaps it with the live weights for validation and prediction.
+    BatchNorm buffers (running statistics) are NOT averaged: evaluation under ``ema_weights()`` uses the live ones.
 """
+import collections
+import contextlib
 import math
 
 import torch
@@ -18,6 +29,29 @@ from . import ops
 
 def _align4(n):
     return (n + 3) // 4 * 4
+
+
+def ema_decay_at(decay, t, warmup=True):
+    """the decay d_t of EMA update number t (1-based): min(decay, (1 + t) / (10 + t)) while warming up, so the first updates
+    follow the weights closely (d_1 = 2/11) instead of averaging in the initialisation for ~1 / (1 - decay) steps"""
+    if t < 1:
+        raise ValueError("EMA updates are counted from 1 (got %r)" % (t,))
+    return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
+
+
+def ema_model_state(ckpt):
+    """``ckpt["model_state"]`` with the parameters replaced by the checkpoint's EMA weights (buffers -- BatchNorm running
+    statistics -- stay the live ones); a state dict for ``model.load_state_dict``"""
+    ema = ckpt.get("ema_state")
+    if ema is None:
+        raise KeyError("this checkpoint has no 'ema_state': it was not trained with EMA weights (train --ema_decay)")
+    strip = lambda k: k[7:] if k.startswith("module.") else k
+    state = collections.OrderedDict((strip(k), v) for k, v in ckpt["model_state"].items())
+    for k, v in ema["params"].items():
+        if strip(k) not in state:
+            raise KeyError("EMA parameter %r is not in the checkpoint's model_state" % (k,))
+        state[strip(k)] = v
+    return state
 
 
 class ParamArena:
@@ -91,6 +125,11 @@ class _FusedBase(torch.optim.Optimizer):
         self._hyper_events = [None] * self._nslots
         self._hyper_slot = 0
         self._hyper_dev = torch.zeros(4, dtype=torch.float32, device=dev)
+        self._max_norm = None       # set_grad_clip
+        self._clip_slots = self._clip = None
+        self._ema = None            # enable_ema: the flat EMA buffer
+        self._ema_decay, self._ema_warmup, self._ema_updates, self._ema_swapped = 0.0, True, 0, False
+        self._ema_weight = 0.0      # 1 - d_t of the step being enqueued (slot 3 of the hyper block)
 
     def _push_hyper(self, *vals):
         i = self._hyper_slot
@@ -100,6 +139,8 @@ class _FusedBase(torch.optim.Optimizer):
             ev.synchronize()                   # the copy that read this slot nslots steps ago has run
         for k, v in enumerate(vals):
             self._hyper_host[i, k] = v
+        if self._ema is not None:
+            self._hyper_host[i, 3] = self._ema_weight
         self._hyper_dev.copy_(self._hyper_host[i], non_blocking=True)
         if self._hyper_dev.is_cuda:
             ev = ev or torch.cuda.Event()
@@ -121,6 +162,118 @@ class _FusedBase(torch.optim.Optimizer):
         if start is not None:
             segs.append((start, a.numel))
         return segs
+
+    # ---- gradient-norm clipping ----------------------------------------------------------------------------------
+    def set_grad_clip(self, max_norm):
+        """clip the global L2 norm of the gradients to `max_norm` inside step() (None or 0: off).  The gradient arena keeps
+        the unclipped values; `last_grad_norm` is the norm before clipping"""
+        if max_norm is None or max_norm == 0:
+            self._max_norm = None
+            return
+        max_norm = float(max_norm)
+        if not (math.isfinite(max_norm) and max_norm > 0):
+            raise ValueError("set_grad_clip wants a positive finite norm, None or 0 (got %r)" % (max_norm,))
+        self._max_norm = max_norm
+
+    @property
+    def last_grad_norm(self):
+        """0-dim device tensor: the total gradient norm of the last clipped step, before clipping (None before the first).
+        Nothing is read back by step(); reading this is the caller's sync"""
+        return None if self._clip is None else self._clip[ops.CLIP_NORM]
+
+    def _clip_pass(self, segs):
+        """norm over the ranges the step updates, then the clip block; -> the block, or None with clipping off"""
+        if self._max_norm is None or not segs:
+            return None
+        if self._clip is None:
+            self._clip_slots, self._clip = ops.new_clip_state(self.arena.data.device)
+        for k, (a, b) in enumerate(segs):
+            ops.grad_sqnorm(self.arena.grad[a:b], self._clip_slots, accumulate=k > 0)
+        ops.clip_finalize(self._clip_slots, self._max_norm, self._clip)
+        return self._clip
+
+    # ---- EMA weights ---------------------------------------------------------------------------------------------
+    def enable_ema(self, decay, warmup=True):
+        """keep an exponential moving average of the weights, updated inside step(); starts at the current weights"""
+        decay = float(decay)
+        if not 0.0 < decay < 1.0:
+            raise ValueError("enable_ema wants 0 < decay < 1 (got %r)" % (decay,))
+        if self._ema_swapped:
+            raise RuntimeError("enable_ema inside ema_weights()")
+        self._ema = self.arena.data.clone()
+        self._ema_decay, self._ema_warmup, self._ema_updates = decay, bool(warmup), 0
+
+    @property
+    def ema_enabled(self):
+        return self._ema is not None
+
+    def _refuse_inside_ema(self):
+        """first thing in step(): a refused step must not have launched anything"""
+        if self._ema_swapped:
+            raise RuntimeError("optimizer.step() inside ema_weights(): the arena holds the EMA weights")
+
+    def _ema_pass(self, segs):
+        """called once per step that updates something: counts the update and sets 1 - d_t for _push_hyper"""
+        if self._ema is None or not segs:
+            return None
+        self._ema_updates += 1
+        self._ema_weight = 1.0 - ema_decay_at(self._ema_decay, self._ema_updates, self._ema_warmup)
+        return self._ema
+
+    def _swap_ema(self):
+        ops.swap_f32(self.arena.data, self._ema)
+        self._ema_swapped = not self._ema_swapped
+        ops.weights_changed()               # the packed-weight caches are keyed on it
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """inside the context the model's parameters ARE the EMA weights (the two flat buffers are swapped in place, no
+        third copy); leaving it restores the live weights bit for bit.  BatchNorm running statistics are the live ones"""
+        if self._ema is None:
+            raise RuntimeError("ema_weights() without enable_ema()")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() does not nest")
+        self._swap_ema()
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+
+    def _ema_names(self, model):
+        model = getattr(model, "module", model)
+        index = {id(p): i for i, p in enumerate(self.arena.params)}
+        names = [(name, index.get(id(p))) for name, p in model.named_parameters()]
+        missing = [name for name, i in names if i is None]
+        if missing or len(names) != len(index):
+            raise ValueError("the model's parameters are not this optimizer's (%d named, %d in the arena, not found: %s)" %
+                             (len(names), len(index), missing[:3]))
+        return names
+
+    def ema_state_dict(self, model):
+        """{"decay", "warmup", "num_updates", "params": {name: tensor}} -- names as in model.state_dict(), detached copies;
+        parameters only (BatchNorm buffers are not averaged)"""
+        if self._ema is None:
+            raise RuntimeError("ema_state_dict() without enable_ema()")
+        flat = self.arena.data if self._ema_swapped else self._ema
+        params = collections.OrderedDict((name, self.arena.view_of(flat, i).detach().clone())
+                                         for name, i in self._ema_names(model))
+        return {"decay": self._ema_decay, "warmup": self._ema_warmup, "num_updates": self._ema_updates, "params": params}
+
+    def load_ema_state_dict(self, model, sd):
+        """restore ema_state_dict(): decay, warmup, update count and every parameter's average (enables EMA if it is off)"""
+        if self._ema_swapped:
+            raise RuntimeError("load_ema_state_dict inside ema_weights()")
+        names = self._ema_names(model)
+        strip = lambda k: k[7:] if k.startswith("module.") else k
+        src = {strip(k): v for k, v in sd["params"].items()}
+        lost = [name for name, _ in names if name not in src]
+        if lost:
+            raise KeyError("EMA state lacks %d parameter(s): %s" % (len(lost), lost[:3]))
+        self.enable_ema(sd["decay"], sd["warmup"])
+        self._ema_updates = int(sd["num_updates"])
+        with torch.no_grad():
+            for name, i in names:
+                self.arena.view_of(self._ema, i).copy_(src[name])
 
     def load_state_dict(self, state_dict):
         """accepts the state of the stock torch optimizer of the same family (the reference's checkpoints,
@@ -159,13 +312,20 @@ class FusedSGD(_FusedBase):
 
     @torch.no_grad()
     def step(self, closure=None):
+        self._refuse_inside_ema()
         loss = closure() if closure is not None else None
         g = self.param_groups[0]
         self._grads_ready()
+        segs = self._segments()
+        clip, ema = self._clip_pass(segs), self._ema_pass(segs)
         self._push_hyper(g["lr"])
-        for a, b in self._segments():
-            ops.sgd_step(self.arena.data[a:b], self.arena.grad[a:b], self._buf[a:b], self._hyper_dev, g["momentum"],
-                         g["weight_decay"], g["nesterov"])
+        for a, b in segs:
+            if clip is None and ema is None:
+                ops.sgd_step(self.arena.data[a:b], self.arena.grad[a:b], self._buf[a:b], self._hyper_dev, g["momentum"],
+                             g["weight_decay"], g["nesterov"])
+            else:
+                ops.sgd_step_ex(self.arena.data[a:b], self.arena.grad[a:b], self._buf[a:b], self._hyper_dev, g["momentum"],
+                                g["weight_decay"], g["nesterov"], clip, None if ema is None else ema[a:b])
         ops.weights_changed()
         return loss
 
@@ -196,18 +356,25 @@ class FusedAdam(_FusedBase):
 
     @torch.no_grad()
     def step(self, closure=None):
+        self._refuse_inside_ema()
         loss = closure() if closure is not None else None
         g = self.param_groups[0]
         self._grads_ready()
         segs = self._segments()
         if not segs:
             return loss             # nothing has a gradient: torch's Adam leaves every step counter alone too
+        clip, ema = self._clip_pass(segs), self._ema_pass(segs)
         self._t += 1
         b1, b2 = g["betas"]
         self._push_hyper(g["lr"], 1.0 - b1 ** self._t, 1.0 - b2 ** self._t)
         for a, b in segs:
-            ops.adam_step(self.arena.data[a:b], self.arena.grad[a:b], self._m[a:b], self._v[a:b], self._hyper_dev, b1, b2,
-                          g["eps"], g["weight_decay"], g["decoupled"])
+            if clip is None and ema is None:
+                ops.adam_step(self.arena.data[a:b], self.arena.grad[a:b], self._m[a:b], self._v[a:b], self._hyper_dev, b1,
+                              b2, g["eps"], g["weight_decay"], g["decoupled"])
+            else:
+                ops.adam_step_ex(self.arena.data[a:b], self.arena.grad[a:b], self._m[a:b], self._v[a:b], self._hyper_dev,
+                                 b1, b2, g["eps"], g["weight_decay"], g["decoupled"], clip,
+                                 None if ema is None else ema[a:b])
         ops.weights_changed()
         for p in self.arena.params:
             if p.grad is not None:          # a frozen parameter's counter stays where it was (as in torch.optim.Adam)

@@ -119,6 +119,8 @@ def get_argparser():
                              "foreground probabilities are averaged (default: 1.0)")
     parser.add_argument("--tta_flip", action='store_true',
                         help="test-time augmentation: add the horizontally mirrored view of every scale")
+    parser.add_argument("--use_ema", action='store_true',
+                        help="predict with the checkpoint's EMA weights (a checkpoint of train --ema_decay)")
     return parser
 
 
@@ -446,14 +448,23 @@ class TTAPredictor:
         return wait
 
 
-def load_model(model, ckpt_path, ck=None):
+def load_model(model, ckpt_path, ck=None, use_ema=False):
     """predict.py:80-91 with the weights-only loader: {"model_state": ...} (this project's and the reference's
     checkpoints) or a bare state dict, `module.` prefixes stripped, strict load.  No file: initial weights.
-    `ck`: the file's contents when the caller has read it already."""
+    `ck`: the file's contents when the caller has read it already.  `use_ema`: load the checkpoint's EMA weights
+    (optim.ema_model_state: parameters from "ema_state", BatchNorm statistics from "model_state"); a checkpoint
+    without them, or no checkpoint, is an error."""
+    if use_ema and not (ckpt_path is not None and os.path.isfile(ckpt_path)):
+        raise FileNotFoundError("--use_ema needs a checkpoint (got %r)" % (ckpt_path,))
     if ckpt_path is not None and os.path.isfile(ckpt_path):
         if ck is None:
             from .train import load_checkpoint
             ck = load_checkpoint(ckpt_path)
+        if use_ema:
+            from .optim import ema_model_state
+            if not (isinstance(ck, dict) and "model_state" in ck):
+                raise KeyError("%s is a bare state dict: it has no 'ema_state'" % ckpt_path)
+            ck = {"model_state": ema_model_state(ck)}
         state = ck["model_state"] if isinstance(ck, dict) and "model_state" in ck else ck
         state = {(k[7:] if k.startswith("module.") else k): v for k, v in state.items()}
         model.load_state_dict(state, strict=True)
@@ -484,13 +495,15 @@ def main(argv=None):
     from . import quant
     q, ck = quant.read_checkpoint(opts.ckpt) if opts.ckpt is not None and os.path.isfile(opts.ckpt) else (None, None)
     if q is not None:
+        if opts.use_ema:
+            parser.error("--use_ema: %s is an INT8 checkpoint (export it from the EMA weights instead)" % opts.ckpt)
         model = quant.load_int8(q, device)
         print("INT8 model loaded from %s (%s, output stride %d)" % (opts.ckpt, q["arch"]["model"],
                                                                      q["arch"]["output_stride"]))
     else:
         model = network.modeling.__dict__[opts.model](num_classes=num_classes, output_stride=opts.output_stride,
                                                       pretrained_backbone=False)
-        model = load_model(model, opts.ckpt, ck).to(device)
+        model = load_model(model, opts.ckpt, ck, use_ema=opts.use_ema).to(device)
     model.eval()
 
     if tile_size > 0:                            # windows share a device batch; frames go one at a time

@@ -22,9 +22,13 @@ forced by the reference not being runnable as shipped:
   * ``--save_val_results`` defaults to False (the reference: True, train.py:297).  With it, every new best
     checkpoint -- and a ``--test_only`` run, into ``test_only_iter_<itr>_score_<weighted>`` -- writes the validation
     images of val_results.save_validation_results under ``--val_results_dir``; ``--save_confidence_map`` adds the
-    confidence map.  Without the flag nothing is written there.
+    confidence map.  Without the flag nothing is written there;
+  * ``--clip_grad_norm`` and ``--ema_decay`` (both off by default) run inside the fused optimizer step (DESIGN.md
+    section 18).  With EMA on, validation, best-model selection and the validation images use the EMA weights, the
+    checkpoint gains ``"ema_state"`` (``"model_state"`` stays the live weights) and ``--test_only --use_ema`` scores it.
 """
 import argparse
+import contextlib
 import math
 import os
 import random
@@ -37,7 +41,7 @@ import torch.distributed as dist
 from torch.utils import data
 
 from . import network, ops
-from .optim import FusedAdam, FusedAdamW, FusedSGD
+from .optim import FusedAdam, FusedAdamW, FusedSGD, ema_model_state
 from .parallel import DistributedDataParallelHIP
 from .utils.loss import CrossEntropyLoss, DiceLoss, TverskyLoss, calculate_class_weights, calculate_class_weights_resident
 from .val_results import save_validation_results
@@ -56,6 +60,12 @@ class _ArgParser(argparse.ArgumentParser):
             self.error("--overlap_smooth must be positive")
         if opts.tversky_alpha < 0 or opts.tversky_beta < 0 or not opts.tversky_gamma > 0:
             self.error("--tversky_alpha and --tversky_beta must not be negative, --tversky_gamma must be positive")
+        if not (math.isfinite(opts.clip_grad_norm) and opts.clip_grad_norm >= 0):
+            self.error("--clip_grad_norm must be a finite norm >= 0 (0 = off)")
+        if not 0 <= opts.ema_decay < 1:
+            self.error("--ema_decay must lie in [0, 1) (0 = off)")
+        if opts.use_ema and not (opts.test_only and opts.ckpt):
+            self.error("--use_ema evaluates the EMA weights of a checkpoint: it needs --test_only and --ckpt")
         return opts, rest
 
 
@@ -130,6 +140,16 @@ def get_argparser():
     parser.add_argument("--overlap_smooth", type=float, default=1.0, help="smoothing constant of the overlap term (> 0)")
     parser.add_argument("--overlap_classes", type=str, default='foreground', choices=['foreground', 'all'],
                         help="classes the overlap term averages over: every class but 0, or all")
+    parser.add_argument("--clip_grad_norm", type=float, default=0.0, metavar="NORM",
+                        help="clip the global L2 norm of the gradients to NORM inside the fused optimizer step "
+                             "(torch.nn.utils.clip_grad_norm_'s factor; the stored gradients stay unclipped); 0 = off")
+    parser.add_argument("--ema_decay", type=float, default=0.0, metavar="DECAY",
+                        help="keep an exponential moving average of the weights inside the optimizer step and validate, select "
+                             "and save the best checkpoint on it (BatchNorm statistics stay the live ones); 0 = off")
+    parser.add_argument("--ema_no_warmup", action='store_true', default=False,
+                        help="use DECAY from the first update instead of min(DECAY, (1 + t) / (10 + t))")
+    parser.add_argument("--use_ema", action='store_true', default=False,
+                        help="with --test_only --ckpt: evaluate the checkpoint's EMA weights")
     return parser
 
 
@@ -367,6 +387,8 @@ def save_best_model(model, optimizer, scheduler, opts, val_score, weighted_score
             "cur_itrs": cur_itrs, "best_score": best_score, "save_time": datetime.now().strftime('%Y%m%d_%H%M%S'),
             "model_config": {"model_name": opts.model, "dataset": opts.dataset,
                              "output_stride": opts.output_stride, "num_classes": opts.num_classes}}
+    if getattr(optimizer, "ema_enabled", False):            # called OUTSIDE ema_weights(): model_state is the live weights
+        ckpt["ema_state"] = optimizer.ema_state_dict(to_save)
     torch.save(ckpt, path + '.tmp')
     os.replace(path + '.tmp', path)
     return path
@@ -511,9 +533,12 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
     model = setup_model(opts)
     cur_itrs, best_score = 0, -1.0
     ckpt = None
+    if getattr(opts, "use_ema", False) and not os.path.isfile(opts.ckpt):
+        raise FileNotFoundError("--use_ema: no checkpoint at %r" % (opts.ckpt,))
     if opts.ckpt is not None and os.path.isfile(opts.ckpt):
         ckpt = load_checkpoint(opts.ckpt)
-        state = {(k[7:] if k.startswith('module.') else k): v for k, v in ckpt["model_state"].items()}
+        source = ema_model_state(ckpt) if getattr(opts, "use_ema", False) else ckpt["model_state"]
+        state = {(k[7:] if k.startswith('module.') else k): v for k, v in source.items()}
         ret = model.load_state_dict(state, strict=False)
         print("Model restored from %s (missing %d, unexpected %d)" % (opts.ckpt, len(ret.missing_keys),
                                                                      len(ret.unexpected_keys)))
@@ -525,6 +550,9 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
         torch.manual_seed(opts.random_seed + 1000003 * rank)       # dropout / augmentation streams differ per rank from here on
         random.seed(opts.random_seed + 1000003 * rank)
     optimizer = setup_optimizer(model, opts)
+    optimizer.set_grad_clip(getattr(opts, "clip_grad_norm", 0.0))
+    if getattr(opts, "ema_decay", 0.0):
+        optimizer.enable_ema(opts.ema_decay, warmup=not opts.ema_no_warmup)
     scheduler = setup_scheduler(optimizer, opts)
     group = dist.group.WORLD if world > 1 else None
     criterion = setup_criterion(opts, class_weights, group).to(device)
@@ -535,6 +563,12 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
     if ckpt is not None and opts.continue_training:
         optimizer.load_state_dict(ckpt["optimizer_state"])
         scheduler.load_state_dict(ckpt["scheduler_state"])
+        if optimizer.ema_enabled and "ema_state" in ckpt:   # the resumed average continues where the checkpoint's stopped
+            optimizer.load_ema_state_dict(model, ckpt["ema_state"])
+    # with EMA on, everything that scores or draws the model runs on the averaged weights; the checkpoint is written outside
+    # the context, from the live ones
+    ema_weights = optimizer.ema_weights if optimizer.ema_enabled else contextlib.nullcontext
+    clipping = bool(getattr(opts, "clip_grad_norm", 0.0))
 
     sequence_val = opts.val_metrics == 'sequence'
     if sequence_val:
@@ -572,15 +606,20 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
             if cur_itrs % opts.print_interval == 0 and rank == 0:
                 avg = float(interval_loss) / opts.print_interval
                 dt = time.time() - t_last
-                print("Epoch %d, Itrs %d/%d, Loss=%.6f, lr=%.3e, %.1f img/s" %
-                      (cur_epochs, cur_itrs, opts.total_itrs, avg, optimizer.param_groups[0]['lr'], n_last / dt))
+                norm = ""
+                if clipping:                                    # one read-back per interval; None until a step has clipped
+                    last = optimizer.last_grad_norm
+                    norm = ", grad norm=%s" % ("n/a" if last is None else "%.4e" % float(last))
+                print("Epoch %d, Itrs %d/%d, Loss=%.6f, lr=%.3e, %.1f img/s%s" %
+                      (cur_epochs, cur_itrs, opts.total_itrs, avg, optimizer.param_groups[0]['lr'], n_last / dt, norm))
                 interval_loss.zero_()
                 t_last, n_last = time.time(), 0
             if cur_itrs % opts.val_interval == 0 and world > 1:
                 dist.barrier()               # the other ranks wait HERE (not inside the next step's all-reduce) while rank 0 validates
             if cur_itrs % opts.val_interval == 0 and rank == 0:
                 if sequence_val:                                # train.py:686-731
-                    score = validate_sequence(model, val_loader, device, opts)
+                    with ema_weights():
+                        score = validate_sequence(model, val_loader, device, opts)
                     print("Validation @%d: %s" % (cur_itrs, score))
                     if is_best_score(score, best_score):
                         best_score = update_best_score(score)
@@ -588,9 +627,11 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
                         path = save_best_model(model, optimizer, scheduler, opts, score, weighted, cur_itrs, best_score)
                         print("saved", path)
                         if path and opts.save_val_results:          # train.py:733-737
-                            save_validation_results(model, val_loader, device, opts, cur_itrs, weighted)
+                            with ema_weights():
+                                save_validation_results(model, val_loader, device, opts, cur_itrs, weighted)
                 else:
-                    score = validate(model, val_loader, device, opts)
+                    with ema_weights():
+                        score = validate(model, val_loader, device, opts)
                     weighted = 0.5 * score["Foreground IoU"] + 0.5 * score["Foreground F1"]
                     print("Validation @%d: %s" % (cur_itrs, score))
                     if weighted > best_score:
@@ -598,7 +639,8 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
                         path = save_best_model(model, optimizer, scheduler, opts, score, weighted, cur_itrs, best_score)
                         print("saved", path)
                         if path and opts.save_val_results:
-                            save_validation_results(model, val_loader, device, opts, cur_itrs, weighted)
+                            with ema_weights():
+                                save_validation_results(model, val_loader, device, opts, cur_itrs, weighted)
             if cur_itrs % opts.val_interval == 0 and world > 1:
                 dist.barrier()
             scheduler.step()
