@@ -35,6 +35,12 @@ typedef void* iswm_stream_t; /* hipStream_t */
 const char* iswm_last_error(void);
 int iswm_version(void);
 
+/* `relu` of the iswm_bn_apply* / iswm_bn_backward* entry points: the activation behind the BatchNorm.  ReLU6 clamps to [0, 6]
+ * and its backward passes the gradient where 0 < out < 6. */
+enum { ISWM_ACT_NONE = 0, ISWM_ACT_RELU = 1, ISWM_ACT_RELU6 = 6 };
+/* `relu` of iswm_conv2d_dgrad_pl2_bn: the gate on dx before its sums are taken (described at that entry point) */
+enum { ISWM_GATE_NONE = 0, ISWM_GATE_RECOMPUTED = 2, ISWM_GATE_RESIDUAL = 3 };
+
 /* ---- convolution (implicit GEMM on v_mfma_f32_32x32x2_f32) ------------------
  * nn.Conv2d call sites: network/backbone/resnet.py:27-35,144,184-187;
  * network/_deeplab.py:37,44-51,124,134,149,162.  groups == 1, square dilation.
@@ -163,11 +169,11 @@ int iswm_conv2d_dgrad_pl2(const iswm_conv_desc* d, const void* dyp, int64_t plan
 /* The same data gradient, also emitting the first pass of the BatchNorm backward that CONSUMES dx (the BatchNorm of the stage
  * whose activation the conv read -- reference resnet.py:103-118: bn1 / bn2 of a Bottleneck): per tile row t and input channel c
  *   partials[0][t][c] = sum dz,  partials[1][t][c] = sum dz * xhat,   dz = dx * [ReLU pattern],  xhat = (y - mean) * invstd
- * over the finished dx (after accumulation).  y: that stage's raw conv output [N*H*W][ldy]; relu 0 = no activation, 2 = pattern
- * recomputed as (y - mean) * mask_scale + mask_shift > 0, exactly as iswm_bn_backward does; 3 = the producer is a RESIDUAL
- * stage (bn3 of a Bottleneck, resnet.py:110-118): pattern = hi plane of its saved output planes (mask_hi, pitch ld_mask bf16
- * elements) > 0, and dx is stored MASKED -- the one tensor is then both dout of that stage's BatchNorm backward (call it with
- * relu = 0) and the gradient of its identity branch: no reduction pass, no separate dres.  partials: 2 * tiles * Cin doubles,
+ * over the finished dx (after accumulation).  y: that stage's raw conv output [N*H*W][ldy]; relu: ISWM_GATE_NONE = no activation,
+ * ISWM_GATE_RECOMPUTED = pattern (y - mean) * mask_scale + mask_shift > 0, exactly as iswm_bn_backward does; ISWM_GATE_RESIDUAL =
+ * the producer is a RESIDUAL stage (bn3 of a Bottleneck, resnet.py:110-118): pattern = hi plane of its saved output planes (mask_hi,
+ * pitch ld_mask bf16 elements) > 0, and dx is stored MASKED -- the one tensor is then both dout of that stage's BatchNorm backward
+ * (call it with ISWM_ACT_NONE) and the gradient of its identity branch: no reduction pass, no separate dres.  partials: 2 * tiles * Cin doubles,
  * tiles = iswm_conv2d_dgrad_pl2_stat_tiles(d).  iswm_bn_backward_stats_pl then runs only the finalize and apply passes
  * (8 bytes per element of HBM traffic less than iswm_bn_backward_pl). */
 int iswm_conv2d_dgrad_pl2_stat_tiles(const iswm_conv_desc* d);
@@ -276,17 +282,17 @@ int iswm_bn_finalize_res(const float* partials, int tiles, int C, int64_t count,
 int iswm_bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,
                         const float* running_var, float eps, float* scale, float* shift,
                         float* save_mean, float* save_invstd, iswm_stream_t stream);
-/* out = act((y - mean[c])*scale[c] + shift[c] (+ residual)); act = relu if relu != 0  * relu: 0 none, 1 ReLU, 6 ReLU6 (clamp to [0, 6]; its backward passes the gradient where 0 < out < 6). */
+/* out = act((y - mean[c])*scale[c] + shift[c] (+ residual)); relu: ISWM_ACT_NONE, ISWM_ACT_RELU or ISWM_ACT_RELU6 */
 int iswm_bn_apply(const float* y, int64_t M, int C, int ldy, const float* scale, const float* shift,
                   const float* mean, const float* residual, int ldr, int relu, float* out, int ldo,
                   iswm_stream_t stream);
-/* backward of out = act(BN(y) (+ residual)):  dz = dout * (out > 0 if relu);
+/* backward of out = act(BN(y) (+ residual)), relu an ISWM_ACT_* code:  dz = dout * (out > 0 if ReLU, 0 < out < 6 if ReLU6);
  *   dbeta = sum dz, dgamma = sum dz*xhat (two deterministic stages, accumulated in double as
  *   ATen's CPU kernel does);
  *   dy = gamma*invstd*(dz - dbeta/M - xhat*dgamma/M) (training) or gamma*invstd*dz (eval);
  *   dres (optional) = dz, the gradient of the identity branch.
- * workspace: iswm_bn_bwd_workspace(M, C) bytes, 16-byte aligned.  * mask_scale / mask_shift (optional, ReLU without residual): the forward's scale and shift -- the ReLU sign pattern is
- * then recomputed as (y - mean)*scale + shift > 0 (bit-identical to iswm_bn_apply) and `out` is not read. */
+ * workspace: iswm_bn_bwd_workspace(M, C) bytes, 16-byte aligned.  mask_scale / mask_shift (optional, ISWM_ACT_RELU without
+ * residual): the forward's scale and shift -- the ReLU sign pattern is then recomputed as (y - mean)*scale + shift > 0 (bit-identical to iswm_bn_apply) and `out` is not read. */
 size_t iswm_bn_bwd_workspace(int64_t M, int C);
 int iswm_bn_backward(const float* dout, int ldd, const float* out, int ldo, const float* y, int ldy,
                      int64_t M, int C, const float* mean, const float* invstd, const float* gamma,

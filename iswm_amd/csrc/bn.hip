@@ -229,8 +229,16 @@ __global__ void k_bn_eval_coeffs(int C, const float* gamma, const float* beta, c
 }
 
 // ---- out = act(y*scale + shift (+ residual)) -------------------------------------------------
-// RELU: 0 none, 1 ReLU, 2 ReLU6 (clamp to [0, 6])
-template <int RELU, bool RES>
+// ACT, the activation of the forward kernels (the C ABI's ISWM_ACT_RELU6 = 6 maps to kActRelu6)
+constexpr int kActNone = 0, kActRelu = 1, kActRelu6 = 2;    // ReLU6: clamp to [0, 6]
+
+template <int ACT, typename... V>
+__device__ __forceinline__ void act4(V&... o) {       // every o clamped below, then every o above
+    if (ACT != kActNone) ((o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f))), ...);
+    if (ACT == kActRelu6) ((o = make_float4(fminf(o.x, 6.f), fminf(o.y, 6.f), fminf(o.z, 6.f), fminf(o.w, 6.f))), ...);
+}
+
+template <int ACT, bool RES>
 __global__ __launch_bounds__(256) void k_bn_apply(const float* __restrict__ y, int64_t M, int C4, int ldy,
                                                   const float* __restrict__ scale,
                                                   const float* __restrict__ shift,
@@ -250,18 +258,13 @@ __global__ __launch_bounds__(256) void k_bn_apply(const float* __restrict__ y, i
             float4 q = ld4x(res, r * ldr + c, rps);
             o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w;
         }
-        if (RELU) {
-            o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-        }
-        if (RELU == 2) {
-            o.x = fminf(o.x, 6.f); o.y = fminf(o.y, 6.f); o.z = fminf(o.z, 6.f); o.w = fminf(o.w, 6.f);
-        }
+        act4<ACT>(o);
         st4x(out, r * ldo + c, ops, o);
     }
 }
 
 // 8 channels per thread (two float4 of y, 16-byte plane stores): the form used whenever the output is pre-split
-template <int RELU, bool RES>
+template <int ACT, bool RES>
 __global__ __launch_bounds__(256) void k_bn_apply8(const float* __restrict__ y, int64_t M, int C8, int ldy,
                                                    const float* __restrict__ scale, const float* __restrict__ shift,
                                                    const float* __restrict__ mean, const void* __restrict__ res, int ldr,
@@ -281,14 +284,7 @@ __global__ __launch_bounds__(256) void k_bn_apply8(const float* __restrict__ y, 
             o0.x += q0.x; o0.y += q0.y; o0.z += q0.z; o0.w += q0.w;
             o1.x += q1.x; o1.y += q1.y; o1.z += q1.z; o1.w += q1.w;
         }
-        if (RELU) {
-            o0.x = fmaxf(o0.x, 0.f); o0.y = fmaxf(o0.y, 0.f); o0.z = fmaxf(o0.z, 0.f); o0.w = fmaxf(o0.w, 0.f);
-            o1.x = fmaxf(o1.x, 0.f); o1.y = fmaxf(o1.y, 0.f); o1.z = fmaxf(o1.z, 0.f); o1.w = fmaxf(o1.w, 0.f);
-        }
-        if (RELU == 2) {
-            o0.x = fminf(o0.x, 6.f); o0.y = fminf(o0.y, 6.f); o0.z = fminf(o0.z, 6.f); o0.w = fminf(o0.w, 6.f);
-            o1.x = fminf(o1.x, 6.f); o1.y = fminf(o1.y, 6.f); o1.z = fminf(o1.z, 6.f); o1.w = fminf(o1.w, 6.f);
-        }
+        act4<ACT>(o0, o1);
         st8x(out, r * ldo + c, ops, o0, o1);
     };
     // two rows per iteration: twice the loads in flight per thread (the one-row loop ran at 3.8 TB/s)
@@ -319,10 +315,28 @@ __global__ __launch_bounds__(256) void k_bn_apply8(const float* __restrict__ y, 
 // (acc_type<float, false>), and over a handful of samples (the ASPP image-pooling branch
 // normalises over N x 1 x 1) dy = dz - mean(dz) - xhat*mean(dz*xhat) cancels to ~eps/(var+eps) of
 // its terms, so fp32 rounding of xhat would show up at the 1e-3 level.  The kernels stay HBM-bound.
-// RELU: 0 = no activation, 1 = ReLU mask read from the saved output (out > 0), 2 = ReLU mask RECOMPUTED from y with the
-// forward's own expression (y - mean) * scale + shift > 0 (bit-identical to k_bn_apply, which has no residual in this
-// case) -- the saved output is then never read: 8 instead of 12 bytes per element in this pass
-template <int RELU, bool DBL>
+// GATE, how the backward kernels apply the activation's pattern to dout: kGateNone = no activation, kGateOut = ReLU mask read
+// from the saved output (out > 0), kGateRecomputed = ReLU mask RECOMPUTED from y with the forward's own expression
+// (y - mean) * scale + shift > 0 (bit-identical to k_bn_apply, which has no residual in this case) -- the saved output is then
+// never read: 8 instead of 12 bytes per element in this pass; kGateOut6 = ReLU6: the gradient passes where 0 < out < 6
+constexpr int kGateNone = 0, kGateOut = 1, kGateRecomputed = 2, kGateOut6 = 3;
+
+// dz = g where the activation passed the gradient, 0 elsewhere.  v = y at the element; the saved output is read at offset `at`
+template <int GATE>
+__device__ __forceinline__ float4 gate4(float4 g, const float4 v, const float4 mu, const float4 msc, const float4 msh,
+                                        const void* __restrict__ out, int64_t at, int64_t ops) {
+    if (GATE == kGateNone) return g;
+    float4 z;
+    if (GATE == kGateRecomputed)
+        z = make_float4((v.x - mu.x) * msc.x + msh.x, (v.y - mu.y) * msc.y + msh.y, (v.z - mu.z) * msc.z + msh.z,
+                        (v.w - mu.w) * msc.w + msh.w);
+    else
+        z = ld4x_hi(out, at, ops);
+    auto pass = [](float z) { return z > 0.f && (GATE != kGateOut6 || z < 6.f); };
+    return make_float4(pass(z.x) ? g.x : 0.f, pass(z.y) ? g.y : 0.f, pass(z.z) ? g.z : 0.f, pass(z.w) ? g.w : 0.f);
+}
+
+template <int GATE, bool DBL>
 __global__ __launch_bounds__(256) void k_bn_bwd_reduce(const float* __restrict__ dout, int ldd,
                                                        const void* __restrict__ out, int ldo, int64_t ops,
                                                        const float* __restrict__ y, int ldy, int64_t M,
@@ -338,7 +352,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_reduce(const float* __restrict__
         const int c = rt.c4 * 4;
         const float4 mu = ld4(mean + c), is = ld4(invstd + c);
         float4 msc = make_float4(0.f, 0.f, 0.f, 0.f), msh = msc;
-        if (RELU == 2) {
+        if (GATE == kGateRecomputed) {
             msc = ld4(mscale + c);
             msh = ld4(mshift + c);
         }
@@ -350,22 +364,8 @@ __global__ __launch_bounds__(256) void k_bn_bwd_reduce(const float* __restrict__
             for (int u = 0; u < 8; ++u) {
                 const int64_t rr = r + u * rt.rstep;
                 if (rr < M) {
-                    float4 g = ld4(dout + rr * ldd + c);
-                    float4 v = ld4(y + rr * ldy + c);
-                    if (RELU == 1) {
-                        float4 o = ld4x_hi(out, rr * ldo + c, ops);
-                        g.x = o.x > 0.f ? g.x : 0.f; g.y = o.y > 0.f ? g.y : 0.f;
-                        g.z = o.z > 0.f ? g.z : 0.f; g.w = o.w > 0.f ? g.w : 0.f;
-                    } else if (RELU == 3) {         // ReLU6: the gradient passes where 0 < out < 6
-                        float4 o = ld4x_hi(out, rr * ldo + c, ops);
-                        g.x = (o.x > 0.f && o.x < 6.f) ? g.x : 0.f; g.y = (o.y > 0.f && o.y < 6.f) ? g.y : 0.f;
-                        g.z = (o.z > 0.f && o.z < 6.f) ? g.z : 0.f; g.w = (o.w > 0.f && o.w < 6.f) ? g.w : 0.f;
-                    } else if (RELU == 2) {
-                        g.x = (v.x - mu.x) * msc.x + msh.x > 0.f ? g.x : 0.f;
-                        g.y = (v.y - mu.y) * msc.y + msh.y > 0.f ? g.y : 0.f;
-                        g.z = (v.z - mu.z) * msc.z + msh.z > 0.f ? g.z : 0.f;
-                        g.w = (v.w - mu.w) * msc.w + msh.w > 0.f ? g.w : 0.f;
-                    }
+                    const float4 g0 = ld4(dout + rr * ldd + c), v = ld4(y + rr * ldy + c);
+                    const float4 g = gate4<GATE>(g0, v, mu, msc, msh, out, rr * ldo + c, ops);
                     if (DBL) {   // few rows per channel (image-pooling branch): everything in double
                         const double gd[4] = {g.x, g.y, g.z, g.w}, vd[4] = {v.x, v.y, v.z, v.w};
                         const double mud[4] = {mu.x, mu.y, mu.z, mu.w}, isd[4] = {is.x, is.y, is.z, is.w};
@@ -451,7 +451,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_finalize(const T* __restrict__ p
 }
 
 // ---- backward stage 2 ---------------------------------------------------------------------------
-template <int RELU, bool TRAIN, bool DRES>
+template <int GATE, bool TRAIN, bool DRES>
 __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ dout, int ldd,
                                                       const void* __restrict__ out, int ldo, int64_t ops,
                                                       const float* __restrict__ y, int ldy, int64_t M,
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ 
     const double mud[4] = {mu.x, mu.y, mu.z, mu.w}, isd[4] = {is.x, is.y, is.z, is.w};
     const double gi[4] = {(double)ga.x * is.x, (double)ga.y * is.y, (double)ga.z * is.z, (double)ga.w * is.w};
     float4 msc = make_float4(0.f, 0.f, 0.f, 0.f), msh = msc;
-    if (RELU == 2) {
+    if (GATE == kGateRecomputed) {
         msc = ld4(mscale + c);
         msh = ld4(mshift + c);
     }
@@ -484,23 +484,10 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ 
         }
     }
     for (int64_t r = rt.row0; r < M; r += rt.rstep) {
-        float4 g = ld4(dout + r * ldd + c);
+        const float4 g0 = ld4(dout + r * ldd + c);
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (TRAIN || RELU == 2) v = ld4(y + r * ldy + c);
-        if (RELU == 1) {
-            float4 o = ld4x_hi(out, r * ldo + c, ops);
-            g.x = o.x > 0.f ? g.x : 0.f; g.y = o.y > 0.f ? g.y : 0.f;
-            g.z = o.z > 0.f ? g.z : 0.f; g.w = o.w > 0.f ? g.w : 0.f;
-        } else if (RELU == 3) {
-            float4 o = ld4x_hi(out, r * ldo + c, ops);
-            g.x = (o.x > 0.f && o.x < 6.f) ? g.x : 0.f; g.y = (o.y > 0.f && o.y < 6.f) ? g.y : 0.f;
-            g.z = (o.z > 0.f && o.z < 6.f) ? g.z : 0.f; g.w = (o.w > 0.f && o.w < 6.f) ? g.w : 0.f;
-        } else if (RELU == 2) {
-            g.x = (v.x - mu.x) * msc.x + msh.x > 0.f ? g.x : 0.f;
-            g.y = (v.y - mu.y) * msc.y + msh.y > 0.f ? g.y : 0.f;
-            g.z = (v.z - mu.z) * msc.z + msh.z > 0.f ? g.z : 0.f;
-            g.w = (v.w - mu.w) * msc.w + msh.w > 0.f ? g.w : 0.f;
-        }
+        if (TRAIN || GATE == kGateRecomputed) v = ld4(y + r * ldy + c);
+        const float4 g = gate4<GATE>(g0, v, mu, msc, msh, out, r * ldo + c, ops);
         if (DRES) st4(dres + r * lddres + c, g);
         const double gd[4] = {g.x, g.y, g.z, g.w};
         float d[4];
@@ -571,18 +558,10 @@ extern "C" int iswm_bn_finalize(const float* partials, int tiles, int C, int64_t
                      tile_rows >= 0 && (tile_rows == 0 || (int64_t)tiles == (count + tile_rows - 1) / tile_rows),
                  "bn_finalize: bad argument (tiles %d, count %lld, tile_rows %lld)", tiles, (long long)count,
                  (long long)tile_rows);
-    if (tiles > 512)
-        hipLaunchKernelGGL((k_bn_finalize<1>), dim3(C), dim3(256), 0, (hipStream_t)stream, partials, tiles, C,
-                           (double)count, (double)tile_rows, gamma, beta, running_mean, running_var, momentum, eps,
-                           scale, shift, save_mean, save_invstd);
-    else if (tiles > 32)
-        hipLaunchKernelGGL((k_bn_finalize<4>), dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, partials, tiles, C,
-                           (double)count, (double)tile_rows, gamma, beta, running_mean, running_var, momentum, eps,
-                           scale, shift, save_mean, save_invstd);
-    else
-        hipLaunchKernelGGL((k_bn_finalize<16>), dim3((C + 15) / 16), dim3(256), 0, (hipStream_t)stream, partials, tiles,
-                           C, (double)count, (double)tile_rows, gamma, beta, running_mean, running_var, momentum, eps,
-                           scale, shift, save_mean, save_invstd);
+    const int cpb = tiles > 512 ? 1 : tiles > 32 ? 4 : 16;      // channels per block: more tiles want more lanes per channel
+    hipLaunchKernelGGL((cpb == 1 ? k_bn_finalize<1> : cpb == 4 ? k_bn_finalize<4> : k_bn_finalize<16>), dim3((C + cpb - 1) / cpb),
+                       dim3(256), 0, (hipStream_t)stream, partials, tiles, C, (double)count, (double)tile_rows, gamma, beta,
+                       running_mean, running_var, momentum, eps, scale, shift, save_mean, save_invstd);
     return check_launch("bn_finalize");
 }
 
@@ -630,40 +609,22 @@ extern "C" int iswm_bn_apply_pl(const float* y, int64_t M, int C, int ldy, const
     ISWM_REQUIRE(!residual || (ldr % 4 == 0 && ldr >= C), "bn_apply: bad residual pitch");
     if (int e = chk_ps("bn_apply(out)", out, M, ldo, out_ps)) return e;
     if (residual) if (int e = chk_ps("bn_apply(residual)", residual, M, ldr, res_ps)) return e;
-    const int64_t rps = res_ps, ops = out_ps;
-    hipStream_t s = (hipStream_t)stream;
-    if (out_ps != 0 && C % 8 == 0 && ldy % 8 == 0 && ldo % 8 == 0 && aligned16(out) && (out_ps < 0 || out_ps % 8 == 0) &&
-        (!residual || (ldr % 8 == 0 && aligned16(residual) && (res_ps <= 0 || res_ps % 8 == 0)))) {
-        RowPlan p = plan_rows(M, C / 2);       // C / 8 groups of 8 channels
-        dim3 grid(p.rowblocks, p.colblocks), blk(256);
-#define LAUNCH8(R, S) \
-    hipLaunchKernelGGL((k_bn_apply8<R, S>), grid, blk, 0, s, y, M, p.C4, ldy, scale, shift, mean, residual, ldr, rps, out, \
-                       ldo, ops, p.CQ, p.RL)
-        ISWM_REQUIRE(relu == 0 || relu == 1 || relu == 6, "bn_apply: relu must be 0 (none), 1 (ReLU) or 6 (ReLU6)");
-        if (relu == 6 && residual) LAUNCH8(2, true);
-        else if (relu == 6) LAUNCH8(2, false);
-        else if (relu && residual) LAUNCH8(1, true);
-        else if (relu) LAUNCH8(1, false);
-        else if (residual) LAUNCH8(0, true);
-        else LAUNCH8(0, false);
-#undef LAUNCH8
-        return check_launch("bn_apply8");
-    }
-    RowPlan p = plan_rows(M, C);
-    dim3 grid(p.rowblocks, p.colblocks), blk(256);
-#define LAUNCH(R, S) \
-    hipLaunchKernelGGL((k_bn_apply<R, S>), grid, blk, 0, s, y, M, p.C4, ldy, scale, shift, mean, residual, ldr, rps, out, \
-                       ldo, ops, \
-                       p.CQ, p.RL)
-    ISWM_REQUIRE(relu == 0 || relu == 1 || relu == 6, "bn_apply: relu must be 0 (none), 1 (ReLU) or 6 (ReLU6)");
-    if (relu == 6 && residual) LAUNCH(2, true);
-    else if (relu == 6) LAUNCH(2, false);
-    else if (relu && residual) LAUNCH(1, true);
-    else if (relu) LAUNCH(1, false);
-    else if (residual) LAUNCH(0, true);
-    else LAUNCH(0, false);
-#undef LAUNCH
-    return check_launch("bn_apply");
+    ISWM_REQUIRE(relu == ISWM_ACT_NONE || relu == ISWM_ACT_RELU || relu == ISWM_ACT_RELU6,
+                 "bn_apply: relu must be 0 (none), 1 (ReLU) or 6 (ReLU6)");
+    // 8 channels per thread whenever the output is pre-split and every pitch and pointer allows it
+    const bool wide = out_ps != 0 && C % 8 == 0 && ldy % 8 == 0 && ldo % 8 == 0 && aligned16(out) &&
+                      (out_ps < 0 || out_ps % 8 == 0) &&
+                      (!residual || (ldr % 8 == 0 && aligned16(residual) && (res_ps <= 0 || res_ps % 8 == 0)));
+#define ROW(K, A) {K<A, false>, K<A, true>}
+    static const decltype(&k_bn_apply<kActNone, false>) kernels[2][3][2] = {          // [wide][ACT][residual]
+        {ROW(k_bn_apply, kActNone), ROW(k_bn_apply, kActRelu), ROW(k_bn_apply, kActRelu6)},
+        {ROW(k_bn_apply8, kActNone), ROW(k_bn_apply8, kActRelu), ROW(k_bn_apply8, kActRelu6)}};
+#undef ROW
+    RowPlan p = plan_rows(M, wide ? C / 2 : C);       // wide: C / 8 groups of 8 channels
+    hipLaunchKernelGGL(kernels[wide][relu == ISWM_ACT_RELU6 ? kActRelu6 : relu][residual != nullptr], dim3(p.rowblocks, p.colblocks),
+                       dim3(256), 0, (hipStream_t)stream, y, M, p.C4, ldy, scale, shift, mean, residual, ldr, (int64_t)res_ps,
+                       out, ldo, (int64_t)out_ps, p.CQ, p.RL);
+    return check_launch(wide ? "bn_apply8" : "bn_apply");
 }
 
 extern "C" size_t iswm_bn_bwd_workspace(int64_t M, int C) {
@@ -693,9 +654,10 @@ static int bn_backward_impl(const float* dout, int ldd, const void* out, int ldo
     if (out) if (int e = chk_ps("bn_backward(out)", out, M, ldo, out_ps)) return e;
     const int64_t ops = out_ps, dyps = dy_ps;
     // ReLU without a residual: the sign pattern is recomputed from y when the forward's scale / shift are given
-    ISWM_REQUIRE(relu == 0 || relu == 1 || relu == 6, "bn_backward: relu must be 0 (none), 1 (ReLU) or 6 (ReLU6)");
-    const bool relu6 = relu == 6;
-    const bool masky = relu == 1 && !dres && mask_scale && mask_shift;
+    ISWM_REQUIRE(relu == ISWM_ACT_NONE || relu == ISWM_ACT_RELU || relu == ISWM_ACT_RELU6,
+                 "bn_backward: relu must be 0 (none), 1 (ReLU) or 6 (ReLU6)");
+    const bool masky = relu == ISWM_ACT_RELU && !dres && mask_scale && mask_shift;
+    const int gate = relu == ISWM_ACT_RELU6 ? kGateOut6 : masky ? kGateRecomputed : relu ? kGateOut : kGateNone;
     ISWM_REQUIRE(dout && y && mean && invstd && dgamma && dbeta && dy && workspace && (!relu || out || masky),
                  "bn_backward: null pointer");
     ISWM_REQUIRE(ldd % 4 == 0 && ldd >= C && lddy % 4 == 0 && lddy >= C && (!relu || (ldo % 4 == 0 && ldo >= C)) &&
@@ -711,56 +673,35 @@ static int bn_backward_impl(const float* dout, int ldd, const void* out, int ldo
         double* partials = (double*)workspace;
         RowPlan p = plan_rows(M, C, tiles);
         dim3 grid(p.rowblocks, p.colblocks), blk(256);
-#define RLAUNCH(R, D)                                                                                           \
-    hipLaunchKernelGGL((k_bn_bwd_reduce<R, D>), grid, blk, 0, s, dout, ldd, out, ldo, ops, y, ldy, M, p.C4, C, mean, invstd, \
-                       mask_scale, mask_shift, p.CQ, p.RL, tiles, partials)
-        const bool dbl = M <= 8192;
-        if (relu6 && dbl) RLAUNCH(3, true);
-        else if (relu6) RLAUNCH(3, false);
-        else if (masky && dbl) RLAUNCH(2, true);
-        else if (masky) RLAUNCH(2, false);
-        else if (relu && dbl) RLAUNCH(1, true);
-        else if (relu) RLAUNCH(1, false);
-        else if (dbl) RLAUNCH(0, true);
-        else RLAUNCH(0, false);
-#undef RLAUNCH
+#define ROW(G) {k_bn_bwd_reduce<G, false>, k_bn_bwd_reduce<G, true>}
+        static const decltype(&k_bn_bwd_reduce<kGateNone, false>) kernels[4][2] = {      // [GATE][double accumulation]
+            ROW(kGateNone), ROW(kGateOut), ROW(kGateRecomputed), ROW(kGateOut6)};
+#undef ROW
+        hipLaunchKernelGGL(kernels[gate][M <= 8192], grid, blk, 0, s, dout, ldd, out, ldo, ops, y, ldy, M, p.C4, C, mean, invstd,
+                           mask_scale, mask_shift, p.CQ, p.RL, tiles, partials);
         if (int e = check_launch("bn_bwd_reduce")) return e;
     }
-    if (tiles > 32)
-        hipLaunchKernelGGL((k_bn_bwd_finalize<double, 4>), dim3((C + 3) / 4), dim3(256), 0, s, partials, tiles, C,
-                           dgamma, dbeta, sums);
-    else
-        hipLaunchKernelGGL((k_bn_bwd_finalize<double, 16>), dim3((C + 15) / 16), dim3(256), 0, s, partials, tiles, C,
-                           dgamma, dbeta, sums);
+    const int cpb = tiles > 32 ? 4 : 16;
+    hipLaunchKernelGGL((cpb == 4 ? k_bn_bwd_finalize<double, 4> : k_bn_bwd_finalize<double, 16>), dim3((C + cpb - 1) / cpb),
+                       dim3(256), 0, s, partials, tiles, C, dgamma, dbeta, sums);
     if (int e = check_launch("bn_bwd_finalize")) return e;
     const double inv = 1.0 / (double)M;
     // (an 8-channel form of the backward apply pass -- 16-byte plane stores -- measured 1.7 ms/step SLOWER: its double-precision
     // per-channel coefficients cost the occupancy the wider stores buy)
     RowPlan p = plan_rows(M, C);
     dim3 grid(p.rowblocks, p.colblocks), blk(256);
-#define LAUNCH(R, T, D)                                                                                          \
-    hipLaunchKernelGGL((k_bn_bwd_apply<R, T, D>), grid, blk, 0, s, dout, ldd, out, ldo, ops, y, ldy, M, p.C4, C, mean,    \
-                       invstd, gamma, mask_scale, mask_shift, sums, inv, dy, lddy, dyps, dres, lddres, p.CQ, p.RL)
-    const int key = (relu ? 4 : 0) | (training ? 2 : 0) | (dres ? 1 : 0);
-    if (relu6) {
-        if (training && dres) LAUNCH(3, true, true);
-        else if (training) LAUNCH(3, true, false);
-        else if (dres) LAUNCH(3, false, true);
-        else LAUNCH(3, false, false);
-    } else if (masky) {
-        if (training) LAUNCH(2, true, false);
-        else LAUNCH(2, false, false);
-    } else switch (key) {
-        case 0: LAUNCH(0, false, false); break;
-        case 1: LAUNCH(0, false, true); break;
-        case 2: LAUNCH(0, true, false); break;
-        case 3: LAUNCH(0, true, true); break;
-        case 4: LAUNCH(1, false, false); break;
-        case 5: LAUNCH(1, false, true); break;
-        case 6: LAUNCH(1, true, false); break;
-        default: LAUNCH(1, true, true); break;
-    }
-#undef LAUNCH
+#define ROW(G) {{k_bn_bwd_apply<G, false, false>, k_bn_bwd_apply<G, false, true>}, \
+                {k_bn_bwd_apply<G, true, false>, k_bn_bwd_apply<G, true, true>}}
+    // [GATE][training][dres]; the recomputed pattern is the forward's only without a residual, so it has no dres form
+    static const decltype(&k_bn_bwd_apply<kGateNone, false, false>) kernels[4][2][2] = {
+        ROW(kGateNone), ROW(kGateOut),
+        {{k_bn_bwd_apply<kGateRecomputed, false, false>, nullptr}, {k_bn_bwd_apply<kGateRecomputed, true, false>, nullptr}},
+        ROW(kGateOut6)};
+#undef ROW
+    const auto kernel = kernels[gate][training != 0][dres != nullptr];
+    ISWM_REQUIRE(kernel, "bn_backward: no kernel for gate %d with dres", gate);
+    hipLaunchKernelGGL(kernel, grid, blk, 0, s, dout, ldd, out, ldo, ops, y, ldy, M, p.C4, C, mean, invstd, gamma, mask_scale,
+                       mask_shift, sums, inv, dy, lddy, dyps, dres, lddres, p.CQ, p.RL);
     return check_launch("bn_bwd_apply");
 }
 

@@ -21,11 +21,11 @@ struct BnFuse {
     const float* y;            // raw conv output of the producer stage at the data gradient's pixels [P][ldy]
     const float* mean;
     const float* invstd;
-    const float* mscale;       // relu == 2: pattern recomputed as (y - mean) * mscale + mshift > 0
+    const float* mscale;       // gate == ISWM_GATE_RECOMPUTED: pattern recomputed as (y - mean) * mscale + mshift > 0
     const float* mshift;
     double* part;              // [2][tiles][C]; nullptr = off
-    int ldy, relu;
-    // relu == 3: the producer stage is a RESIDUAL stage (out = relu(bn(y) + identity)): its ReLU pattern is read from the hi
+    int ldy, gate;             // gate: ISWM_GATE_*
+    // ISWM_GATE_RESIDUAL: the producer stage is a RESIDUAL stage (out = relu(bn(y) + identity)): its ReLU pattern is read from the hi
     // plane of its saved output (`mask`, pitch ldm bf16 elements) and the epilogue stores the MASKED gradient dz = dx * [out > 0]
     // -- that tensor is at once the input of the producer's BatchNorm backward and the gradient of its identity branch
     const unsigned short* mask;

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
         const int col = n0 + 16 * wn + 4 * lq;
         const bool cok = col < NC;
         const bool bnf = DGRAD && a.bnf.part != nullptr;
-        const bool mk = bnf && a.bnf.relu == 3;
+        const bool mk = bnf && a.bnf.gate == ISWM_GATE_RESIDUAL;
         if (DGRAD && a.accumulate && zero && !bnf) return;           // ... adds nothing
         float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
         if (!DGRAD && a.bias != nullptr && cok) bv = *reinterpret_cast<const float4*>(a.bias + col);
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
         if (bnf && cok) {
             f_mu = *reinterpret_cast<const float4*>(a.bnf.mean + col);
             f_is = *reinterpret_cast<const float4*>(a.bnf.invstd + col);
-            if (a.bnf.relu == 2) {
+            if (a.bnf.gate == ISWM_GATE_RECOMPUTED) {
                 f_sc = *reinterpret_cast<const float4*>(a.bnf.mscale + col);
                 f_sh = *reinterpret_cast<const float4*>(a.bnf.mshift + col);
             }
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2(const ConvArgs a) {
         const uint2* const zero2 = reinterpret_cast<const uint2*>(g_zero_row_pl2);
         float4* const dump = g_dump_pl2 + lane;
         const bool acc_old = DGRAD && a.accumulate;
-        const bool relu2 = bnf && a.bnf.relu == 2;
+        const bool relu2 = bnf && a.bnf.gate == ISWM_GATE_RECOMPUTED;
         constexpr int EH = (RBW + 1) / 2;
 #pragma unroll
         for (int h0 = 0; h0 < RBW; h0 += EH) {

@@ -218,7 +218,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
     auto epilogue = [&](int tile, int m0, int n0, bool zero) __attribute__((always_inline)) {
         const int mt = tile / a.NT;
         const bool bnf = DGRAD && a.bnf.part != nullptr;
-        const bool mk = bnf && a.bnf.relu == 3;
+        const bool mk = bnf && a.bnf.gate == ISWM_GATE_RESIDUAL;
         if (DGRAD && a.accumulate && zero && !bnf) return;
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
             if (bnf && cok) {
                 f_mu = *reinterpret_cast<const float4*>(a.bnf.mean + col);
                 f_is = *reinterpret_cast<const float4*>(a.bnf.invstd + col);
-                if (a.bnf.relu == 2) {
+                if (a.bnf.gate == ISWM_GATE_RECOMPUTED) {
                     f_sc = *reinterpret_cast<const float4*>(a.bnf.mscale + col);
                     f_sh = *reinterpret_cast<const float4*>(a.bnf.mshift + col);
                 }
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pl2w(const ConvArgs a) {
                                 // same expressions as k_bn_bwd_reduce (bn.hip) and k_conv_pl2
                                 const float4 yv = yvv[j];
                                 float4 g = v;
-                                if (a.bnf.relu == 2) {
+                                if (a.bnf.gate == ISWM_GATE_RECOMPUTED) {
                                     g.x = (yv.x - f_mu.x) * f_sc.x + f_sh.x > 0.f ? g.x : 0.f;
                                     g.y = (yv.y - f_mu.y) * f_sc.y + f_sh.y > 0.f ? g.y : 0.f;
                                     g.z = (yv.z - f_mu.z) * f_sc.z + f_sh.z > 0.f ? g.z : 0.f;

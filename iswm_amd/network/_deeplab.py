@@ -19,6 +19,7 @@ import torch.nn as nn
 from . import _hip
 from .utils import _SimpleSegmentationModel
 from .. import ops
+from ..ops import Act
 
 __all__ = ["DeepLabV3"]
 
@@ -59,7 +60,7 @@ class ASPPPooling(_hip.HipSequential):
     def fwd(self, x, save, out=None):
         n, h, w, c = x.shape
         pooled = ops.gap_fwd(x)                                            # [N,1,1,C]
-        v, ctx = _hip.cba_fwd(self[1], self[2], True, pooled, save, out_fmt="f32")   # BN over N x 1 x 1 (needs N >= 2)
+        v, ctx = _hip.cba_fwd(self[1], self[2], Act.RELU, pooled, save, out_fmt="f32")   # BN over N x 1 x 1 (needs N >= 2)
         if out is None:
             out = ops.new_act(n, h, w, v.shape[3], x.device)
         ops.bcast_fwd(v, out)                                              # bilinear from 1x1 == broadcast
@@ -70,7 +71,7 @@ class ASPPPooling(_hip.HipSequential):
         ctx, shape = self._saved
         self._saved = None
         dv = ops.bcast_bwd(dy)
-        dpooled, _ = _hip.cba_bwd(self[1], self[2], ctx, dv, sink)
+        dpooled, _ = _hip.cba_bwd(ctx, dv, sink)
         if dx is None:
             dx = ops.new_act(*shape, dy.device)
             accumulate = False
@@ -119,17 +120,19 @@ class ASPP(_hip.HipModule):
     # ---- the parallel conv branches (convs[0..3]: 1x1 and the three atrous 3x3) as ONE launch each way (ops.aspp_fwd / aspp_dgrad:
     # rows sorted by in-bounds tap set, one tile table over all branches, the data gradient a single GEMM over the 28 taps)
     def _branch_convs(self):
+        """the [Conv2d -> BatchNorm2d -> ReLU] stages of convs[:-1], or None when one of them is anything else"""
         out = []
         for m in list(self.convs)[:-1]:
             st = m._stages() if isinstance(m, _hip.HipSequential) else []
-            if len(st) != 1 or st[0][0] != "cba" or not isinstance(st[0][1], _hip.Conv2d) or not st[0][3] or st[0][3] == 6:
+            if len(st) != 1 or st[0].kind != "cba" or not isinstance(st[0].conv, _hip.Conv2d) or st[0].act is not Act.RELU:
                 return None
-            c = st[0][1]
+            c = st[0].conv
             k = c.kernel_size[0]
             if c.bias is not None or c.stride[0] != 1 or k % 2 == 0 or c.padding[0] != c.dilation[0] * (k - 1) // 2 or c.needs_pack():
                 return None
-            out.append((c, st[0][2]))
-        if not out or any(c.in_channels != out[0][0].in_channels or c.out_channels != out[0][0].out_channels for c, _ in out):
+            out.append(st[0])
+        c0 = out[0].conv if out else None
+        if not out or any(s.conv.in_channels != c0.in_channels or s.conv.out_channels != c0.out_channels for s in out):
             return None
         return out
 
@@ -137,7 +140,7 @@ class ASPP(_hip.HipModule):
     def _branch_weights(br, x, kind, ldx, ldy):
         """the branches' weights packed for the planes kernels (kind 0 forward, 1 data gradient) at these pitches"""
         out = []
-        for c, _ in br:
+        for c in (s.conv for s in br):
             d = c.geometry(x).desc(ldx, ldy)
             p = ops.conv_plan(d, ("fwd", "dgrad")[kind], True)
             assert p.wform == "pl2", "the fused ASPP kernels take the planes kernels' weight form"
@@ -152,21 +155,22 @@ class ASPP(_hip.HipModule):
         if not ops.is_planes(x):
             x = ops.split_planes(x)           # a stand-alone ASPP over an fp32 map (inside the network the backbone hands over planes)
         br = self._branch_convs()
-        if br is None or len(br) > 4 or br[0][0].out_channels != oc:
+        if br is None or len(br) > 4 or br[0].conv.out_channels != oc:
             return None
-        ksize = [c.kernel_size[0] for c, _ in br]
-        dil = [c.dilation[0] for c, _ in br]
-        training = br[0][1].training
-        if any(bn.training != training for _, bn in br):
+        ksize = [s.conv.kernel_size[0] for s in br]
+        dil = [s.conv.dilation[0] for s in br]
+        training = br[0].bn.training
+        if any(s.bn.training != training for s in br):
             return None
         res = ops.aspp_fwd(x, ksize, dil, oc, self._branch_weights(br, x, 0, ops.pgeom(x)[4], oc), training)
         if res is None:
             return None
         ys, parts, tiles = res
         ctxs = []
-        for i, (c, bn) in enumerate(br):
-            _, ctx = _hip._cba_finish(c, bn, True, x, ys[i], c.geometry(x), parts[i] if parts else None,
-                                      (tiles, ops.ASPP_TILE_ROWS), training, save, None, cat[..., i * oc:(i + 1) * oc], None, False)
+        for i, s in enumerate(br):
+            _, ctx = _hip._cba_finish(s, x=x, y=ys[i], g=s.conv.geometry(x), partials=parts[i] if parts else None,
+                                      tiles=(tiles, ops.ASPP_TILE_ROWS), training=training, save=save,
+                                      out=cat[..., i * oc:(i + 1) * oc])
             ctxs.append(ctx)
         return ctxs
 
@@ -186,19 +190,19 @@ class ASPP(_hip.HipModule):
         return dx
 
     def _bwd_fused(self, dcat, sink, oc, ctxs, xshape):
-        br = self._branch_convs()
+        br = [c.stage for c in ctxs]
         n, h, w, cin = xshape
         nb = len(ctxs)
         # the four BatchNorm backwards write their dy (gradient of the raw conv outputs) into ONE planes buffer
         dyc = ops.new_planes(n, h, w, nb * oc, dcat.device)
-        for i, (c, bn) in enumerate(br):
-            dy_i, _ = _hip.cba_bwd_bn(c, bn, ctxs[i], dcat[..., i * oc:(i + 1) * oc], sink, dy_out=dyc[..., i * oc:(i + 1) * oc])
-            c.write_wgrad(ctxs[i]["x"], dy_i, ctxs[i]["g"], sink)
-        wpks = self._branch_weights(br, ctxs[0]["x"], 1, cin, nb * oc)
-        dx = ops.aspp_dgrad(dyc, [c.kernel_size[0] for c, _ in br], [c.dilation[0] for c, _ in br], cin, oc, wpks)
+        for i, c in enumerate(ctxs):
+            dy_i, _ = _hip.cba_bwd_bn(c, dcat[..., i * oc:(i + 1) * oc], sink, dy_out=dyc[..., i * oc:(i + 1) * oc])
+            c.stage.conv.write_wgrad(c.x, dy_i, c.g, sink)
+        wpks = self._branch_weights(br, ctxs[0].x, 1, cin, nb * oc)
+        dx = ops.aspp_dgrad(dyc, [s.conv.kernel_size[0] for s in br], [s.conv.dilation[0] for s in br], cin, oc, wpks)
         if dx is None:                                   # (cannot happen when the forward plan existed; keep the path honest)
-            for i, (c, _) in enumerate(br):
-                dx = ops.conv2d_dgrad(dyc[..., i * oc:(i + 1) * oc], c.weight_for(1), ctxs[i]["g"], xshape, dx, dx is not None)
+            for i, c in enumerate(ctxs):
+                dx = ops.conv2d_dgrad(dyc[..., i * oc:(i + 1) * oc], c.stage.conv.weight_for(1), c.g, xshape, dx, dx is not None)
         return dx
 
     def out_channels_of(self, cin):

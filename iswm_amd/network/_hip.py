@@ -13,11 +13,14 @@ and the whole model is ONE node in torch's autograd graph (``_Bridge``), so
 ``loss.backward()`` / ``optimizer.step()`` in train.py work unchanged while no
 torch op ever touches an activation.  All compute is libiswm_hip.so kernels.
 """
+import dataclasses
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from .. import ops
+from ..ops import Act
 
 
 # Test hook: when set to a dict, cba_fwd records {bn_module: (out > 0)} for every fused ReLU so a
@@ -355,34 +358,68 @@ class Dropout(HipModule, nn.Dropout):
 # ---------------------------------------------------------------------------------------
 # conv -> BatchNorm -> (+residual) -> ReLU, the unit every stage of the net is made of
 # ---------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class Stage(object):
+    """One fused unit of a module, as its `_stages()` describes it; it holds modules only, never a call's state.
+    kind "cba": conv -> bn -> act (`conv` may be a SeparableBase or a DepthwiseConv2d); "conv": a Conv2d (+ bias) alone;
+    "mod": any other HipModule, in `conv`."""
+    kind: str
+    conv: nn.Module
+    bn: Optional[nn.Module] = None
+    act: Act = Act.NONE
+
+    def __post_init__(self):
+        if self.kind not in ("cba", "conv", "mod") or not isinstance(self.act, Act):
+            raise ValueError("bad stage: kind %r, act %r" % (self.kind, self.act))
+
+    @property
+    def bn_conv(self):
+        """the convolution whose output the BatchNorm reads: the pointwise half of a separable conv, else `conv`"""
+        return self.conv.body[1] if isinstance(self.conv, SeparableBase) else self.conv
+
+
+class StageCtx(object):
+    """What one forward of a "cba" stage keeps for its backward: x the input of `stage.bn_conv`, y its raw output, out the stage's
+    output (None behind a folded classifier), coef [4, C] of the BatchNorm, g the conv geometry, res whether a residual was
+    added, sep the SeparableBase / dw whether the conv is depthwise (both follow from the stage), bn_stats the ops.BnStats a
+    consumer's data gradient filled for this stage's BatchNorm backward, cls / wc4 the classifier folded into the stage and its
+    padded weight."""
+    __slots__ = ("stage", "x", "y", "out", "coef", "g", "training", "res", "sep", "dw", "bn_stats", "cls", "wc4")
+
+    def __init__(self, stage, x, y, coef, g, training, out=None, res=False, cls=None, wc4=None):
+        self.stage, self.x, self.y, self.out, self.coef, self.g, self.training, self.res = stage, x, y, out, coef, g, training, res
+        self.sep = stage.conv if isinstance(stage.conv, SeparableBase) else None
+        self.dw = isinstance(stage.bn_conv, DepthwiseConv2d)
+        self.bn_stats, self.cls, self.wc4 = None, cls, wc4
+
+
 def cba_fwd(conv, bn, relu, x, save, residual=None, out=None, out_fmt=None):
-    """Returns (out, ctx).  Training-mode BN statistics come from the conv epilogue's
+    """Returns (out, ctx).  relu: an ops.Act, or True / False / 6.  Training-mode BN statistics come from the conv epilogue's
     per-tile partial sums (no extra pass over y).  The output is written pre-split (ops.Planes) when a convolution
     will consume it: `out` (a buffer slice) decides, else out_fmt ("planes" / "f32"), else the channel count."""
-    sep = None
+    stage = Stage("cba", conv, bn, Act.of(relu))
     if isinstance(conv, SeparableBase):         # depthwise first, then the pointwise conv carries the fused BN
-        sep, conv = conv, conv.body[1]
-        x = sep.body[0].fwd(x, save)
+        x = conv.body[0].fwd(x, save)
+        conv = stage.bn_conv
     training = bn.training
     if bn.momentum is None or not bn.track_running_stats or not bn.affine:
         raise NotImplementedError("HIP BatchNorm2d supports affine=True, momentum!=None, running stats")
+    g = conv.geometry(x)
     if isinstance(conv, DepthwiseConv2d):       # depthwise conv -> BN (MobileNetV2)
-        g = conv.geometry(x)
         if conv.is_dw3x3():                     # statistics from the convolution's own launch (csrc/dwconv3.hip)
             y, partials, tiles = conv.fwd_stats(x, save, training)
         else:                                   # other filter sizes: statistics from a column pass
             y = conv.fwd(x, save)
             partials, tiles = _colstat_partials(y, training)
-        return _cba_finish(conv, bn, relu, x, y, g, partials, tiles, training, save, residual, out, sep, True, out_fmt)
-    g = conv.geometry(x)
-    if conv.bias is None:
+    elif conv.bias is None:
         y, partials, tiles = ops.conv2d_fwd(x, conv.weight_for(0), g, want_stats=training)
     else:
         # a biased conv in front of a BatchNorm (only reachable through convert_to_separable_conv on a biased
         # conv): the fused epilogue statistics do not include the bias, so take them in a separate column pass
         y, _, _ = ops.conv2d_fwd(x, conv.weight_for(0), g, bias=conv.bias_p())
         partials, tiles = _colstat_partials(y, training)
-    return _cba_finish(conv, bn, relu, x, y, g, partials, tiles, training, save, residual, out, sep, False, out_fmt)
+    return _cba_finish(stage, x=x, y=y, g=g, partials=partials, tiles=tiles, training=training, save=save, residual=residual,
+                       out=out, out_fmt=out_fmt)
 
 
 def _colstat_partials(y, training):
@@ -420,22 +457,20 @@ def _bn_grads_done(bn, sink):
             sink.done(p)
 
 
-def _cba_finish(conv, bn, relu, x, y, g, partials, tiles, training, save, residual, out, sep, dw, out_fmt=None):
-    coef = _bn_coef(bn, y, partials, tiles, training)
+def _cba_finish(stage, *, x, y, g, partials, tiles, training, save, residual=None, out=None, out_fmt=None):
+    """BatchNorm coefficients from the tile statistics of y, then the apply pass (+ residual, activation): (out, ctx)"""
+    coef = _bn_coef(stage.bn, y, partials, tiles, training)
     if out_fmt is None:
         want_planes = ops.planes_on() and y.shape[3] % 64 == 0
     else:
         want_planes = out_fmt == "planes" and ops.planes_on() and y.shape[3] % 64 == 0
-    o = ops.bn_apply(y, coef, relu, residual, out, planes=want_planes)
-    if MASK_RECORDER is not None and relu:
+    o = ops.bn_apply(y, coef, stage.act, residual, out, planes=want_planes)
+    if MASK_RECORDER is not None and stage.act is not Act.NONE:
         of = ops.as_f32(o)
-        MASK_RECORDER[bn] = (of > 0) & (of < 6) if relu == 6 and relu is not True else (of > 0)
+        MASK_RECORDER[stage.bn] = (of > 0) & (of < 6) if stage.act is Act.RELU6 else (of > 0)
     if CALIB_RECORDER is not None:
-        CALIB_RECORDER.record(conv, o)
-    ctx = None
-    if save:
-        ctx = dict(x=x, y=y, out=o, coef=coef, g=g, relu=relu, training=training, res=residual is not None, sep=sep, dw=dw)
-    return o, ctx
+        CALIB_RECORDER.record(stage.bn_conv, o)
+    return o, StageCtx(stage, x, y, coef, g, training, out=o, res=residual is not None) if save else None
 
 
 _BN3_FUSE = True      # False: residual stages reduce themselves (tests compare both paths)
@@ -444,53 +479,47 @@ _BN3_FUSE = True      # False: residual stages reduce themselves (tests compare 
 def _bn_stats_request(up):
     """`up` = ctx of the stage that produced this stage's input, when ITS BatchNorm backward is the only consumer of the dx this
     stage returns: the planes data gradient then takes that backward's reduction pass in its epilogue (ops.BnStats)."""
-    if up is None or not ops.planes_on() or up.get("bn_stats") is not None:
+    if up is None or not ops.planes_on() or up.bn_stats is not None:
         return None
-    if ops._relu_code(up["relu"]) not in (0, 1):
+    act = up.stage.act
+    # a residual stage (bn3 + identity + ReLU): the pattern is read from its saved output planes and the data gradient
+    # stores dx masked -- see ops.BnStats.mask
+    if act is Act.RELU6 or (up.res and not (_BN3_FUSE and act is Act.RELU and ops.is_planes(up.out) and up.training)):
         return None
-    if up.get("res"):
-        # a residual stage (bn3 + identity + ReLU): the pattern is read from its saved output planes and the data gradient
-        # stores dx masked -- see ops.BnStats.mask
-        if not (_BN3_FUSE and ops._relu_code(up["relu"]) == 1 and ops.is_planes(up["out"]) and up["training"]):
-            return None
-        return ops.BnStats(up["y"], up["coef"], up["relu"], mask=up["out"])
-    return ops.BnStats(up["y"], up["coef"], up["relu"])
+    return ops.BnStats(up.y, up.coef, act, mask=up.out if up.res else None)
 
 
-def cba_bwd_bn(conv, bn, ctx, dout, sink, dy_out=None, need_dx=True):
-    """the BatchNorm (+ activation) backward of a stage: parameter gradients into the sink, returns (dy, dres) with dy the
-    gradient of the raw conv output -- pre-split when the conv's gradient kernels take planes; dy_out: write it there (a Planes
-    slice of a wider buffer: the fused ASPP data gradient reads the four branches' gradients from one tensor)"""
-    y, o = ctx["y"], ctx["out"]
-    sep = ctx.get("sep")
-    if sep is not None:
-        conv = sep.body[1]
+def cba_bwd_bn(ctx, dout, sink, dy_out=None, need_dx=True, want_dres=True):
+    """the BatchNorm (+ activation) backward of the stage that made `ctx`: parameter gradients into the sink, returns (dy, dres)
+    with dy the gradient of the raw conv output -- pre-split when the conv's gradient kernels take planes; dy_out: write it there
+    (a Planes slice of a wider buffer: the fused ASPP data gradient reads the four branches' gradients from one tensor);
+    want_dres=False: the caller takes no gradient of the residual input from this stage"""
+    conv, bn, act = ctx.stage.bn_conv, ctx.stage.bn, ctx.stage.act
+    res = ctx.res and want_dres
     gw = bn.weight
     dgamma, dbeta = _bn_grad_targets(bn, sink)
     # planes only when a planes kernel will read them: the data gradient, or the weight gradient of a pre-split input (the stem
     # has neither: its gradient stays fp32 instead of being split here and joined again for the weight gradient)
-    dyp = (not ctx.get("dw")) and ops.planes_conv_ok(conv.cin_p, conv.cout_p, 1) and (need_dx or ops.is_planes(ctx["x"]))
-    st = ctx.pop("bn_stats", None)
+    dyp = (not ctx.dw) and ops.planes_conv_ok(conv.cin_p, conv.cout_p, 1) and (need_dx or ops.is_planes(ctx.x))
+    st, ctx.bn_stats = ctx.bn_stats, None
     if st is not None and st.partials is not None and st.masked:
         dout = ops.as_f32(dout)
-        dy, _ = ops.bn_backward(dout, None, y, ctx["coef"], gw, False, ctx["training"], dgamma, dbeta, want_dres=False,
+        dy, _ = ops.bn_backward(dout, None, ctx.y, ctx.coef, gw, Act.NONE, ctx.training, dgamma, dbeta, want_dres=False,
                                 dy=dy_out, dy_planes=dyp, stats=st)
-        dres = dout if ctx["res"] else None
+        dres = dout if res else None
     else:
-        dy, dres = ops.bn_backward(ops.as_f32(dout), o if ctx["relu"] else None, y, ctx["coef"], gw, ctx["relu"], ctx["training"],
-                                   dgamma, dbeta, want_dres=ctx["res"], dy=dy_out, dy_planes=dyp, stats=st)
+        dy, dres = ops.bn_backward(ops.as_f32(dout), ctx.out if act is not Act.NONE else None, ctx.y, ctx.coef, gw, act,
+                                   ctx.training, dgamma, dbeta, want_dres=res, dy=dy_out, dy_planes=dyp, stats=st)
     _bn_grads_done(bn, sink)
     return dy, dres
 
 
-def cba_bwd(conv, bn, ctx, dout, sink, need_dx=True, dx=None, accumulate=False, up=None):
-    """Returns (dx, dres): dres is the gradient of the residual input (if any).  up: see _bn_stats_request."""
-    x, g = ctx["x"], ctx["g"]
-    sep = ctx.get("sep")
-    dy, dres = cba_bwd_bn(conv, bn, ctx, dout, sink, need_dx=need_dx or sep is not None)
-    if sep is not None:
-        conv = sep.body[1]
-    if ctx.get("dw"):
+def cba_bwd(ctx, dout, sink, need_dx=True, dx=None, accumulate=False, up=None, want_dres=True):
+    """Backward of the stage that made `ctx`.  Returns (dx, dres): dres is the gradient of the residual input (if any; never with
+    want_dres=False).  up: see _bn_stats_request."""
+    x, g, sep, conv = ctx.x, ctx.g, ctx.sep, ctx.stage.bn_conv
+    dy, dres = cba_bwd_bn(ctx, dout, sink, need_dx=need_dx or sep is not None, want_dres=want_dres)
+    if ctx.dw:
         if conv.is_dw3x3():
             return conv.bwd_fused(dy, sink, need_dx, dx, accumulate), dres
         return conv.bwd(dy, sink, need_dx, dx, accumulate), dres
@@ -500,10 +529,10 @@ def cba_bwd(conv, bn, ctx, dout, sink, need_dx=True, dx=None, accumulate=False, 
         dmid = ops.conv2d_dgrad(dy, conv.weight_for(1), g, tuple(x.shape))
         return sep.body[0].bwd(dmid, sink, need_dx, dx, accumulate), dres
     if need_dx:
-        req = _bn_stats_request(up) if (up is not None and tuple(up["y"].shape) == tuple(x.shape)) else None
+        req = _bn_stats_request(up) if (up is not None and tuple(up.y.shape) == tuple(x.shape)) else None
         dx = ops.conv2d_dgrad(dy, conv.weight_for(1), g, tuple(x.shape), dx, accumulate, bn_stats=req)
         if req is not None and req.partials is not None:
-            up["bn_stats"] = req
+            up.bn_stats = req
     else:
         dx = None
     return dx, dres
@@ -601,19 +630,21 @@ class WeightPacker(object):
 _CLS_FUSE = True      # False: the classifier as a conv of its own (tests compare both paths)
 
 
-def cls_fusable(conv, bn, relu, cls):
+def cls_fusable(stage, cls):
     """[Conv2d(.., 256, k) -> BatchNorm2d -> ReLU] followed by the 1x1 classifier Conv2d(256, num_classes <= 4, 1): the tail of both
     DeepLab heads (network/_deeplab.py:44-52, 84-90).  The classifier is then folded into the stage's BatchNorm passes
     (csrc/bn_classify.hip).  Not while a calibration records ranges (it needs the stage's stored output); a test's ReLU-pattern
     recorder is served by cba_cls_fwd itself."""
-    return (_CLS_FUSE and CALIB_RECORDER is None and relu is True and type(conv) is Conv2d and conv.out_channels == 256 and
+    conv, bn = stage.conv, stage.bn
+    return (_CLS_FUSE and CALIB_RECORDER is None and stage.act is Act.RELU and type(conv) is Conv2d and conv.out_channels == 256 and
             conv.bias is None and type(cls) is Conv2d and cls.in_channels == 256 and cls.out_channels <= 4 and
             tuple(cls.kernel_size) == (1, 1) and tuple(cls.stride) == (1, 1) and tuple(cls.padding) == (0, 0) and
             bn.momentum is not None and bn.track_running_stats and bn.affine)
 
 
-def cba_cls_fwd(conv, bn, cls, x, save):
+def cba_cls_fwd(stage, cls, x, save):
     """conv -> BatchNorm -> ReLU -> 1x1 classifier with the activation never stored: returns (logits [N,H,W,4], ctx)"""
+    conv, bn = stage.conv, stage.bn
     g = conv.geometry(x)
     training = bn.training
     y, partials, tiles = ops.conv2d_fwd(x, conv.weight_for(0), g, want_stats=training)
@@ -624,21 +655,21 @@ def cba_cls_fwd(conv, bn, cls, x, save):
     if MASK_RECORDER is not None:
         # the stage's ReLU pattern, as _cba_finish records it: the unfused apply on the same y and coefficients evaluates the
         # fold's (y - mean) * scale + shift (tests/test_cls_fuse.py pins all of the fold's decisions to it bit for bit)
-        MASK_RECORDER[bn] = ops.bn_apply(y, coef, True) > 0
-    ctx = dict(x=x, y=y, coef=coef, g=g, training=training, wc4=wc4, cls=cls, cls_fused=True) if save else None
-    return logits, ctx
+        MASK_RECORDER[bn] = ops.bn_apply(y, coef, Act.RELU) > 0
+    return logits, StageCtx(stage, x, y, coef, g, training, cls=cls, wc4=wc4) if save else None
 
 
-def cba_cls_bwd(conv, bn, ctx, dlogit, sink, need_dx=True, dx=None, accumulate=False):
+def cba_cls_bwd(ctx, dlogit, sink, need_dx=True, dx=None, accumulate=False):
     """backward of cba_cls_fwd: classifier bias / weight gradients, the stage's BatchNorm backward fed by dlogit, then the
     conv's weight and data gradients as in cba_bwd"""
-    cls, x, y, g = ctx["cls"], ctx["x"], ctx["y"], ctx["g"]
+    conv, bn = ctx.stage.conv, ctx.stage.bn
+    cls, x, y, g = ctx.cls, ctx.x, ctx.y, ctx.g
     dlogit = ops.as_f32(dlogit)
     _bias_grad(cls.bias, dlogit, sink)
     gw = bn.weight
     dgamma, dbeta = _bn_grad_targets(bn, sink)
     dyp = ops.planes_conv_ok(conv.cin_p, conv.cout_p, 1)
-    dy, dwc4 = ops.bn_backward_classify(dlogit, ctx["wc4"], y, ctx["coef"], gw, ctx["training"], dgamma, dbeta, dyp)
+    dy, dwc4 = ops.bn_backward_classify(dlogit, ctx.wc4, y, ctx.coef, gw, ctx.training, dgamma, dbeta, dyp)
     _bn_grads_done(bn, sink)
     if cls.weight.requires_grad:
         ops.unpad_weights(dwc4.view(4, 1, 1, 256), sink.target(cls.weight))
@@ -666,15 +697,15 @@ class HipSequential(HipModule, nn.Sequential):
             m = mods[i]
             if isinstance(m, (Conv2d, SeparableBase, DepthwiseConv2d)) and i + 1 < len(mods) and \
                     isinstance(mods[i + 1], nn.BatchNorm2d):
-                act = mods[i + 2] if i + 2 < len(mods) else None
-                relu = 6 if isinstance(act, nn.ReLU6) else isinstance(act, nn.ReLU)
-                st.append(("cba", m, mods[i + 1], relu))
-                i += 3 if relu else 2
+                nxt = mods[i + 2] if i + 2 < len(mods) else None
+                act = Act.RELU6 if isinstance(nxt, nn.ReLU6) else Act.RELU if isinstance(nxt, nn.ReLU) else Act.NONE
+                st.append(Stage("cba", m, mods[i + 1], act))
+                i += 2 if act is Act.NONE else 3
             elif isinstance(m, Conv2d):
-                st.append(("conv", m))
+                st.append(Stage("conv", m))
                 i += 1
             elif isinstance(m, HipModule):
-                st.append(("mod", m))
+                st.append(Stage("mod", m))
                 i += 1
             else:
                 raise NotImplementedError("no HIP implementation for %s inside a Sequential" % type(m).__name__)
@@ -685,15 +716,12 @@ class HipSequential(HipModule, nn.Sequential):
         ctxs = []
         for k, s in enumerate(st):
             last = k == len(st) - 1
-            if ctxs and ctxs[-1] == "FOLDED" and last:
-                break                                   # the classifier conv was folded into the stage in front of it
-            if (s[0] == "cba" and k == len(st) - 2 and st[k + 1][0] == "conv" and out is None and
-                    cls_fusable(s[1], s[2], s[3], st[k + 1][1])):
-                x, c = cba_cls_fwd(s[1], s[2], st[k + 1][1], x, save)
-                ctxs.append(c)
-                ctxs.append("FOLDED")
-                continue
-            if s[0] == "cba":
+            if (s.kind == "cba" and k == len(st) - 2 and st[k + 1].kind == "conv" and out is None and
+                    cls_fusable(s, st[k + 1].conv)):
+                x, c = cba_cls_fwd(s, st[k + 1].conv, x, save)
+                ctxs += [c, None]
+                break                                   # the classifier conv, the last stage, is folded into this one (c.cls)
+            if s.kind == "cba":
                 # the stage's output is pre-split when the next stage is a convolution; the last stage follows `out`
                 # / out_fmt (default fp32: the caller is not a conv unless it says so)
                 if last:
@@ -701,14 +729,14 @@ class HipSequential(HipModule, nn.Sequential):
                     if out is None and out_fmt is None:
                         fmt = "f32"
                 else:
-                    fmt = "planes" if st[k + 1][0] in ("cba", "conv") else "f32"
-                x, c = cba_fwd(s[1], s[2], s[3], x, save, out=out if last else None, out_fmt=fmt)
+                    fmt = "planes" if st[k + 1].kind in ("cba", "conv") else "f32"
+                x, c = cba_fwd(s.conv, s.bn, s.act, x, save, out=out if last else None, out_fmt=fmt)
                 ctxs.append(c)
-            elif s[0] == "conv":
-                x = s[1].fwd(x, save, out=out if last else None)
+            elif s.kind == "conv":
+                x = s.conv.fwd(x, save, out=out if last else None)
                 ctxs.append(None)
             else:
-                x = s[1].fwd(x, save)
+                x = s.conv.fwd(x, save)
                 ctxs.append(None)
         self._saved = (st, ctxs) if save else None
         return x
@@ -717,20 +745,18 @@ class HipSequential(HipModule, nn.Sequential):
         st, ctxs = self._saved
         self._saved = None
         for k in range(len(st) - 1, -1, -1):
-            s = st[k]
-            first = k == 0
-            if ctxs[k] == "FOLDED":
-                continue
-            if s[0] == "cba" and ctxs[k] is not None and ctxs[k].get("cls_fused"):
-                dy = cba_cls_bwd(s[1], s[2], ctxs[k], dy, sink, need_dx or not first, dx if first else None, accumulate and first)
-                continue
-            if s[0] == "cba":
-                dy, _ = cba_bwd(s[1], s[2], ctxs[k], dy, sink, need_dx or not first, dx if first else None,
-                                accumulate and first)
-            elif s[0] == "conv":
-                dy = s[1].bwd(dy, sink, need_dx or not first, dx if first else None, accumulate and first)
+            s, c = st[k], ctxs[k]
+            rest = (need_dx or k > 0, dx if k == 0 else None, accumulate and k == 0)
+            if s.kind == "conv" and k > 0 and ctxs[k - 1] is not None and ctxs[k - 1].cls is s.conv:
+                continue                                # folded into the stage in front of it: cba_cls_bwd there covers it
+            if s.kind == "cba" and c.cls is not None:
+                dy = cba_cls_bwd(c, dy, sink, *rest)
+            elif s.kind == "cba":
+                dy, _ = cba_bwd(c, dy, sink, *rest)
+            elif s.kind == "conv":
+                dy = s.conv.bwd(dy, sink, *rest)
             else:
-                dy = s[1].bwd(dy, sink)
+                dy = s.conv.bwd(dy, sink)
         return dy
 
     def out_channels_of(self, cin):

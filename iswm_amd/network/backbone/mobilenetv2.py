@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from .. import _hip
 from ... import ops
+from ...ops import Act
 
 __all__ = ['MobileNetV2', 'InvertedResidual', 'mobilenet_v2']
 
@@ -64,39 +65,39 @@ class InvertedResidual(_hip.HipModule):
         m = list(self.conv)
         st = []
         if self.expand:
-            st.append((m[0], m[1], 6))
+            st.append(_hip.Stage("cba", m[0], m[1], Act.RELU6))
             m = m[3:]
-        st.append((m[0], m[1], 6))
-        st.append((m[3], m[4], False))
+        st.append(_hip.Stage("cba", m[0], m[1], Act.RELU6))
+        st.append(_hip.Stage("cba", m[3], m[4], Act.NONE))
         return st
 
     def fwd(self, x, save):
         st = self._stages()
         ctxs = []
         h = x
-        for k, (conv, bn, relu) in enumerate(st):
+        for k, s in enumerate(st):
             last = k == len(st) - 1
             # the depthwise kernels read fp32; the depthwise stage's own output goes pre-split to the projection when the
             # planes kernels take it, and the block's output follows its channel count (the next block's 1x1 reads it)
-            fmt = "f32" if (not last and isinstance(st[k + 1][0], _hip.DepthwiseConv2d)) else None
-            h, c = _hip.cba_fwd(conv, bn, relu, h, save, residual=x if (last and self.use_res_connect) else None, out_fmt=fmt)
+            fmt = "f32" if (not last and isinstance(st[k + 1].conv, _hip.DepthwiseConv2d)) else None
+            h, c = _hip.cba_fwd(s.conv, s.bn, s.act, h, save, residual=x if (last and self.use_res_connect) else None,
+                                out_fmt=fmt)
             ctxs.append(c)
         self._saved = ctxs if save else None
         return h
 
     def bwd(self, dout, sink):
-        st, ctxs = self._stages(), self._saved
+        ctxs = self._saved
         self._saved = None
         dres = None
         if self.use_res_connect:
-            # no activation after the add: the gradient of the identity branch IS the incoming gradient; the first
-            # stage's data gradient accumulates into it
+            # no activation after the add: the gradient of the identity branch IS the incoming gradient (the last stage is asked
+            # for none, want_dres=False); the first stage's data gradient accumulates into it
             dout = dres = ops.as_f32(dout)
-            ctxs[-1]["res"] = False
         d = dout
-        for k in range(len(st) - 1, 0, -1):
-            d, _ = _hip.cba_bwd(st[k][0], st[k][1], ctxs[k], d, sink)
-        dx, _ = _hip.cba_bwd(st[0][0], st[0][1], ctxs[0], d, sink, dx=dres, accumulate=dres is not None)
+        for k in range(len(ctxs) - 1, 0, -1):
+            d, _ = _hip.cba_bwd(ctxs[k], d, sink, want_dres=False)
+        dx, _ = _hip.cba_bwd(ctxs[0], d, sink, dx=dres, accumulate=dres is not None)
         return dx
 
     def out_channels_of(self, cin):

@@ -11,6 +11,7 @@ import torch.nn as nn
 from .. import _hip
 from ..._hip_compat import FloatFunctional
 from ... import ops
+from ...ops import Act
 
 __all__ = ['ResNet', 'resnet50', 'resnet101', 'resnet152']
 
@@ -48,13 +49,13 @@ class Bottleneck(_hip.HipModule):
         self._saved = None
 
     def fwd(self, x, save):
-        o1, c1 = _hip.cba_fwd(self.conv1, self.bn1, True, x, save)
-        o2, c2 = _hip.cba_fwd(self.conv2, self.bn2, True, o1, save)
+        o1, c1 = _hip.cba_fwd(self.conv1, self.bn1, Act.RELU, x, save)
+        o2, c2 = _hip.cba_fwd(self.conv2, self.bn2, Act.RELU, o1, save)
         identity, cd = x, None
         if self.downsample is not None:
-            identity, cd = _hip.cba_fwd(self.downsample[0], self.downsample[1], False, x, save)
+            identity, cd = _hip.cba_fwd(self.downsample[0], self.downsample[1], Act.NONE, x, save)
         # conv3 -> bn3 -> (+identity) -> relu in one fused elementwise pass (reference :110-118)
-        out, c3 = _hip.cba_fwd(self.conv3, self.bn3, True, o2, save, residual=identity)
+        out, c3 = _hip.cba_fwd(self.conv3, self.bn3, Act.RELU, o2, save, residual=identity)
         self._saved = (c1, c2, c3, cd) if save else None
         return out
 
@@ -67,16 +68,16 @@ class Bottleneck(_hip.HipModule):
         c1, c2, c3, cd = self._saved
         self._saved = None
         # conv3's / conv2's data gradients are consumed by bn2's / bn1's backward alone: they take its reduction pass along
-        d2, dres = _hip.cba_bwd(self.conv3, self.bn3, c3, dout, sink, up=c2)
-        d1, _ = _hip.cba_bwd(self.conv2, self.bn2, c2, d2, sink, up=c1)
+        d2, dres = _hip.cba_bwd(c3, dout, sink, up=c2)
+        d1, _ = _hip.cba_bwd(c2, d2, sink, up=c1)
         if cd is not None:
             # conv1 (1x1, stride 1) writes every input pixel; the strided downsample conv then only touches the
             # pixels it reaches (its data gradient skips the other parity classes when accumulating)
-            dx, _ = _hip.cba_bwd(self.conv1, self.bn1, c1, d1, sink, dx=dx0, accumulate=dx0 is not None)
-            dx, _ = _hip.cba_bwd(self.downsample[0], self.downsample[1], cd, dres, sink, dx=dx, accumulate=True)
+            dx, _ = _hip.cba_bwd(c1, d1, sink, dx=dx0, accumulate=dx0 is not None)
+            dx, _ = _hip.cba_bwd(cd, dres, sink, dx=dx, accumulate=True)
         else:
             # identity branch: the residual gradient IS dx; conv1's dgrad accumulates into it
-            dx, _ = _hip.cba_bwd(self.conv1, self.bn1, c1, d1, sink, dx=dres, accumulate=True, up=up)
+            dx, _ = _hip.cba_bwd(c1, d1, sink, dx=dres, accumulate=True, up=up)
             if dx0 is not None:
                 dx = ops.add_inplace(dx, dx0)
         return dx

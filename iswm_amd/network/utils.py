@@ -157,7 +157,7 @@ class IntermediateLayerGetter(nn.ModuleDict):
             if name == "conv1":
                 # the max-pool reads the stem's output as fp32
                 fmt = "f32" if "maxpool" in self._modules else None
-                x, stem_ctx = _hip.cba_fwd(self["conv1"], self["bn1"], True, x, save, out_fmt=fmt)
+                x, stem_ctx = _hip.cba_fwd(self["conv1"], self["bn1"], ops.Act.RELU, x, save, out_fmt=fmt)
             elif name in ("bn1", "relu"):
                 pass                                   # fused into the conv1 stage above
             else:
@@ -180,7 +180,7 @@ class IntermediateLayerGetter(nn.ModuleDict):
             if name in ("relu", "bn1"):
                 continue
             if name == "conv1":
-                dy, _ = _hip.cba_bwd(self["conv1"], self["bn1"], self._saved, dy, sink, need_dx=need_dx)
+                dy, _ = _hip.cba_bwd(self._saved, dy, sink, need_dx=need_dx)
             else:
                 # a tapped feature right below this layer (low_level under layer2): the layer's first block accumulates its data
                 # gradient into the tap's gradient instead of a separate 800-MB add pass

@@ -11,6 +11,7 @@ slice of a wider buffer -- that is how torch.cat disappears from the graph).
 """
 import collections
 import ctypes
+import enum
 import functools
 
 import numpy as np
@@ -20,6 +21,26 @@ from . import _lib
 from ._lib import ConvDesc, call
 
 BN_EPS = 1e-5
+
+
+class Act(enum.IntEnum):
+    """activation fused behind a BatchNorm.  The values are the C ABI codes (include/iswm_hip.h, ISWM_ACT_*): int(act) is what
+    the iswm_bn_apply* / iswm_bn_backward* entry points take."""
+    NONE = 0
+    RELU = 1
+    RELU6 = 6
+
+    @classmethod
+    def of(cls, v):
+        """the only coercion: an Act; None / False / 0 -> NONE; True / 1 -> RELU; 6 -> RELU6.  Exactly bool and int count, so
+        2, 6.0, "relu" or an instance of another int subclass are a ValueError, not an activation."""
+        if isinstance(v, cls):
+            return v
+        if v is None:
+            return cls.NONE
+        if type(v) in (bool, int) and v in (0, 1, 6):
+            return cls(int(v))
+        raise ValueError("not an activation: %r (expected an Act, None, False, True, 0, 1 or 6)" % (v,))
 
 
 def _stream():
@@ -464,13 +485,19 @@ def conv2d_fwd(x, w, g, bias=None, out=None, want_stats=False):
     return out, partials, tiles
 
 
+# what iswm_conv2d_dgrad_pl2_bn applies to dx before it takes the sums (include/iswm_hip.h, ISWM_GATE_*)
+GATE_NONE = 0          # the producer stage has no activation
+GATE_RECOMPUTED = 2    # ReLU, no residual: the pattern recomputed from the producer's y and scale / shift
+GATE_RESIDUAL = 3      # ReLU behind a residual add: the pattern read from the saved output's hi plane, dx stored masked
+
+
 class BnStats(object):
     """Request / result of the BatchNorm-backward statistics a planes data gradient can take in its epilogue: `y`, `coef`
-    (scale, shift, mean, invstd) and `relu` describe the stage that PRODUCED the conv's input (whose BatchNorm backward will
+    (scale, shift, mean, invstd) and `act` describe the stage that PRODUCED the conv's input (whose BatchNorm backward will
     consume dx); conv2d_dgrad fills `partials`, `tiles` when its kernel supports the fusion (they stay None otherwise)."""
 
     def __init__(self, y, coef, relu, mask=None):
-        self.y, self.coef, self.relu = y, coef, relu
+        self.y, self.coef, self.act = y, coef, Act.of(relu)
         self.partials, self.tiles = None, 0
         # a RESIDUAL producer stage (out = relu(bn(y) + identity)): `mask` = its saved output (Planes); the data gradient then
         # stores dx MASKED by (out > 0) and sets `masked` -- that tensor is the stage's dout (relu already applied) AND the
@@ -492,14 +519,14 @@ def conv2d_dgrad(dy, w, g, x_like_shape, dx=None, accumulate=False, bn_stats=Non
     args = [ctypes.byref(d), _p(dy)] + ([ps] if p.planes else []) + [_p(wk), _p(dx), int(bool(accumulate))]
     if b is not None:                     # the BnStats epilogue, on top of the plan
         part = torch.empty((2, p.stat_tiles, g.cin), dtype=torch.float64, device=dx.device)
-        masky = _relu_code(b.relu) == 1 and b.mask is None
-        pm, ldm, code = None, 0, 2 if masky else 0
+        masky = b.act is Act.RELU and b.mask is None
+        pm, ldm, gate = None, 0, GATE_RECOMPUTED if masky else GATE_NONE
         if b.mask is not None:
             pm, _, _, ldm, _ = xrows(b.mask)            # plane 0 = hi
-            code = 3
+            gate = GATE_RESIDUAL
         entry += "_bn"
         args += [_p(b.y), rows(b.y)[2], _p(b.coef[2]), _p(b.coef[3]), _p(b.coef[0]) if masky else None,
-                 _p(b.coef[1]) if masky else None, code, _p(pm), ldm, _p(part), p.stat_tiles]
+                 _p(b.coef[1]) if masky else None, gate, _p(pm), ldm, _p(part), p.stat_tiles]
     with _timed(p.name, [g]):
         call(entry, *args, _stream())
     if b is not None:
@@ -753,14 +780,10 @@ def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps=BN_EPS):
     return coef
 
 
-def _relu_code(relu):
-    """activation after a BatchNorm: False / 0 none, True / 1 ReLU, 6 ReLU6"""
-    return 6 if (relu == 6 and relu is not True) else int(bool(relu))
-
-
 def bn_apply(y, coef, relu, residual=None, out=None, planes=False):
     """out = act((y - mean) * scale + beta (+ residual)); `out` (fp32 or Planes, possibly a channel slice) decides the
     output format, else `planes` does"""
+    act = Act.of(relu)
     m, c, ldy = rows(y)
     if out is None:
         out = new_planes(*y.shape, y.device) if planes else torch.empty(y.shape, dtype=torch.float32, device=y.device)
@@ -770,7 +793,7 @@ def bn_apply(y, coef, relu, residual=None, out=None, planes=False):
     if residual is not None:
         pr, mr, cr, ldr, psr = xrows(residual)
         assert (mr, cr) == (m, c)
-    call("iswm_bn_apply_pl", _p(y), m, c, ldy, _p(coef[0]), _p(coef[1]), _p(coef[2]), _p(pr), ldr, psr, _relu_code(relu),
+    call("iswm_bn_apply_pl", _p(y), m, c, ldy, _p(coef[0]), _p(coef[1]), _p(coef[2]), _p(pr), ldr, psr, int(act),
          _p(po), ldo, pso, _stream())
     return out
 
@@ -782,6 +805,7 @@ def bn_backward(dout, out, y, coef, gamma, relu, training, dgamma, dbeta, want_d
     take it pre-split).  stats: a filled BnStats from the data gradient that produced dout -- the reduction pass is skipped.
     want_dres also tells whether the stage added a residual: with ReLU and want_dres=False the pattern is recomputed from y alone,
     which is the forward's only if it added none -- a residual stage's backward must ask for dres."""
+    act = Act.of(relu)
     m, c, ldy = rows(y)
     _, _, ldd = rows(dout)
     po, ldo, pso = None, 0, 0
@@ -795,17 +819,14 @@ def bn_backward(dout, out, y, coef, gamma, relu, training, dgamma, dbeta, want_d
     dres = torch.empty(y.shape, dtype=torch.float32, device=y.device) if want_dres else None
     # ReLU without a residual: hand over the forward's scale / shift so the sign pattern is recomputed from y and the
     # saved output is never read (a residual stage's pattern depends on the identity tensor: read `out` there)
-    masky = _relu_code(relu) == 1 and not want_dres
-    if stats is not None and stats.partials is not None:
-        call("iswm_bn_backward_stats_pl", _p(dout), ldd, _p(po), ldo, pso, _p(y), ldy, m, c, _p(coef[2]), _p(coef[3]), _p(gamma),
-             _p(coef[0]) if masky else None, _p(coef[1]) if masky else None,
-             _relu_code(relu), int(bool(training)), _p(dgamma), _p(dbeta), _p(pdy), lddy, psdy, _p(dres),
-             rows(dres)[2] if dres is not None else 0, _p(stats.partials), stats.tiles, _p(ws), need, _stream())
-        return dy, dres
-    call("iswm_bn_backward_pl", _p(dout), ldd, _p(po), ldo, pso, _p(y), ldy, m, c, _p(coef[2]), _p(coef[3]), _p(gamma),
-         _p(coef[0]) if masky else None, _p(coef[1]) if masky else None,
-         _relu_code(relu), int(bool(training)), _p(dgamma), _p(dbeta), _p(pdy), lddy, psdy, _p(dres),
-         rows(dres)[2] if dres is not None else 0, _p(ws), need, _stream())
+    masky = act is Act.RELU and not want_dres
+    fused = stats is not None and stats.partials is not None
+    args = [_p(dout), ldd, _p(po), ldo, pso, _p(y), ldy, m, c, _p(coef[2]), _p(coef[3]), _p(gamma),
+            _p(coef[0]) if masky else None, _p(coef[1]) if masky else None, int(act), int(bool(training)), _p(dgamma),
+            _p(dbeta), _p(pdy), lddy, psdy, _p(dres), rows(dres)[2] if dres is not None else 0]
+    if fused:
+        args += [_p(stats.partials), stats.tiles]
+    call("iswm_bn_backward_stats_pl" if fused else "iswm_bn_backward_pl", *args, _p(ws), need, _stream())
     return dy, dres
 
 
