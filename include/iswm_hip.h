@@ -416,6 +416,38 @@ int iswm_overlap_loss_coeffs(const double* sums, int C, double ce_weight, double
 int iswm_overlap_loss_bwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
                           const float* class_weight, int ignore_index, const float* coef, const float* upstream,
                           float* grad, iswm_stream_t stream);
+/* ---- hard-pixel mining (OHEM / bootstrapped cross-entropy) ---------------------------
+ * Over the valid pixels V (label != ignore_index and 0 <= label < C), nll as iswm_loss_fwd forms it:
+ *   k = min(min_kept, |V|),  nu = min(nu0, k-th largest nll over V)  (nu0 = float(-ln thresh); nu = nu0 if k == 0),
+ *   K = {i in V : nll_i >= nu} (ties at nu all kept),  L = sum_K w nll / sum_K w  (0 if K is empty),
+ *   dL/dz = upstream w (p - onehot) / sum_K w on K, exactly 0 elsewhere.  1 <= C <= 8.
+ * keys: one int32 per pixel = the bit pattern of nll (-0.0 and NaN stored as +0), -1 at an invalid pixel; non-negative
+ *   floats order as these integers.  counts [iswm_loss_blocks(B * HW)] is a workspace (the blocks' valid counts);
+ *   nvalid[1] (int64) = |V|, their sum.
+ * hist / scan: an exact radix select over the keys, iswm_ohem_digits() = 3 digits of 11 + 10 + 10 bits from the top.
+ *   hist(digit) ADDS to hist[iswm_ohem_bins() = 2048] (int64, zeroed by the caller) the counts of that digit among the keys that carry
+ *   the prefix chosen so far; scan(digit) picks the bin holding the wanted rank and leaves state[4] (int64) =
+ *   {prefix, remaining rank, k, -} for the next digit; scan(0) forms k from nvalid and min_kept, scan(2) writes nu[1].
+ *   Call hist(0), scan(0), hist(1), scan(1), hist(2), scan(2).  Nothing is read back by the host.
+ * sums: partials [3 * iswm_loss_blocks(npix)] and sums[3] (double) = {sum_K w nll, sum_K w, |K|}; kept is decided as
+ *   key >= bits(nu) on the stored keys.  With nu = 0 sums[0..1] are iswm_loss_fwd's mode-0 sums bit for bit.
+ * loss: out[2] = {L, 1 / sum_K w} (both 0 if K is empty).   bwd: the finished gradient, written once.
+ * Under data parallelism the host all-reduces nvalid (before scan(0)), each hist (before its scan) and sums (before
+ * loss); every result is then the global batch's.  All results are bit-reproducible (integer counts, fixed-order sums). */
+int iswm_ohem_digits(void);
+int iswm_ohem_bins(void);
+int iswm_ohem_keys(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
+                   int ignore_index, int32_t* keys, int32_t* counts, int64_t* nvalid, iswm_stream_t stream);
+int iswm_ohem_hist(const int32_t* keys, int64_t npix, const int64_t* state, int digit, int64_t* hist,
+                   iswm_stream_t stream);
+int iswm_ohem_scan(const int64_t* hist, const int64_t* nvalid, int digit, int64_t min_kept, float nu0,
+                   int64_t* state, float* nu, iswm_stream_t stream);
+int iswm_ohem_sums(const int32_t* keys, const void* labels, int label_bytes, int64_t npix, int C,
+                   const float* class_weight, const float* nu, float* partials, double* sums, iswm_stream_t stream);
+int iswm_ohem_loss(const double* sums, float* out, iswm_stream_t stream);
+int iswm_ohem_bwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
+                  const float* class_weight, const int32_t* keys, const float* nu, const float* lossinv,
+                  const float* upstream, float* grad, iswm_stream_t stream);
 /* logits.max(1)[1], train.py:644,659 -- ties resolve to the lowest class index */
 int iswm_argmax_nchw(const float* logits, int B, int C, int64_t HW, int64_t* out, iswm_stream_t stream);
 

@@ -154,6 +154,14 @@ _SIGS = {
     "iswm_overlap_loss_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, P, P, P]),
     "iswm_overlap_loss_coeffs": (c_int, [P, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_int, P, P, P]),
     "iswm_overlap_loss_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, P, P, P, P]),
+    "iswm_ohem_digits": (c_int, []),
+    "iswm_ohem_bins": (c_int, []),
+    "iswm_ohem_keys": (c_int, [P, P, c_int, c_int, c_int, c_int64, c_int, P, P, P, P]),
+    "iswm_ohem_hist": (c_int, [P, c_int64, P, c_int, P, P]),
+    "iswm_ohem_scan": (c_int, [P, P, c_int, c_int64, c_float, P, P, P]),
+    "iswm_ohem_sums": (c_int, [P, P, c_int, c_int64, c_int, P, P, P, P, P]),
+    "iswm_ohem_loss": (c_int, [P, P, P]),
+    "iswm_ohem_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, P, P, P, P, P, P]),
     "iswm_argmax_nchw": (c_int, [P, c_int, c_int, c_int64, P, P]),
     "iswm_augment_batch": (c_int, [P, P, P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P, P]),
     "iswm_aug_rotate": (c_int, [P, P, P, P, c_int, c_int64, P, c_size_t, P, c_size_t, P]),

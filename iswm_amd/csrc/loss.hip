@@ -440,6 +440,281 @@ __global__ __launch_bounds__(256) void k_overlap_bwd(const float* __restrict__ l
     }
 }
 
+// ---- hard-pixel mining (OHEM / bootstrapped CE): the weighted CE over the pixels the model still gets wrong ---------------------
+//   V = valid pixels (loss_pixel's rule), nll_i as k_loss_fwd forms it, k = min(min_kept, |V|)
+//   nu = min(float32(-ln thresh), k-th largest nll over V)   (+inf for the second term if k == 0)
+//   K = {i in V : nll_i >= nu},  L = sum_K w nll / sum_K w,  dL/dz = upstream w (p - g) / sum_K w on K, exactly 0 elsewhere
+// The gradient hangs on a global order statistic, so nothing can be written in the pass that forms the sums:
+//   k_ohem_keys   logits + labels -> one int32 key per pixel (the bit pattern of nll, -1 for an invalid pixel) and |V|
+//   k_ohem_hist   keys -> the histogram of one digit of the keys that carry the prefix selected so far (LDS bins, integer atomics)
+//   k_ohem_scan   one workgroup: the bin that holds rank r -> prefix and remaining rank for the next digit; after the last
+//                 digit nu as a device scalar.  Three digits of 11 + 10 + 10 bits from the top of the 31 significant bits.
+//   k_ohem_sums   keys + labels -> per-block partials {sum_K w nll, sum_K w, |K|} on k_loss_fwd's walk, then k_overlap_finalize
+//   k_ohem_loss   sums -> {loss, 1 / sum_K w}
+//   k_ohem_bwd    logits + labels + keys + nu -> the finished gradient, once
+// Key order: nll >= 0 always (log se >= 0 because the largest class contributes exp(0) = 1; both forms of log_softmax are then
+// <= 0), except that -log_softmax(..) of +0 is -0.0, whose bit pattern would sort above everything: the key is
+// nll > 0 ? nll : +0 (a NaN becomes 0 as well).  Non-negative floats order as their bit patterns, read as int32; the invalid
+// pixels' -1 lies below every valid key and below every nu >= 0, so it is never counted, selected or kept.
+// The kept decision is key >= bits(nu) on the STORED keys in the sums and the backward pass alike -- never on an nll formed again.
+// Integer counts are order-independent, the float sums run in k_loss_fwd's fixed order: every result is bit-reproducible, and with
+// thresh = 1 (nu = 0) the first two sums are iswm_loss_fwd's mode-0 sums bit for bit (0 + w * -0.0 and 0 + w * 0.0 are both +0).
+// Under data parallelism the host all-reduces |V|, every histogram and the three sums between the kernels.
+// Per pixel at C = 2, uint8 labels: keys 9 B read + 4 written, 3 x 4 B histogram reads, sums 5 B read, backward 5 B read +
+// (8 B read only where a pixel is kept) + 8 written: 43 B + 8 B per kept pixel; the CE path moves 33 B.
+constexpr int OHEM_DIGITS = 3, OHEM_BINS = 2048, OHEM_HIST_UNR = 8;
+__host__ __device__ constexpr int ohem_shift(int d) { return d == 0 ? 20 : (d == 1 ? 10 : 0); }
+__host__ __device__ constexpr int ohem_width(int d) { return d == 0 ? 11 : 10; }
+
+template <typename LabelT, int CT>
+__global__ __launch_bounds__(256) void k_ohem_keys(const float* __restrict__ logits, const LabelT* __restrict__ labels, int Crt,
+                                                   int64_t HW, int64_t npix, int ignore_index, int* __restrict__ keys,
+                                                   int* __restrict__ counts) {
+    constexpr int UNR = 4, CMAX = CT > 0 ? CT : OVL_CMAX;
+    const int C = CT > 0 ? CT : Crt;
+    __shared__ int red[4];
+    int cnt = 0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i0 < npix; i0 += UNR * stride) {
+        float z[UNR][CMAX];
+        long long y[UNR];
+        bool in[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int64_t i = i0 + u * stride;
+            in[u] = i < npix;
+            const int64_t ii = in[u] ? i : 0;
+            const int64_t b = ii / HW, p = ii - b * HW;
+            y[u] = in[u] ? (long long)labels[ii] : (long long)ignore_index;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) z[u][c] = (in[u] && c < C) ? logits[b * C * HW + c * HW + p] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            if (!in[u]) continue;
+            float s1 = 0.f, s2 = 0.f, coef, m, lg;      // s1 = 0 + 1 * nll: loss_pixel's own nll
+            bool valid;
+            loss_pixel(z[u], C, y[u], nullptr, ignore_index, 1.f, 0.f, 0, s1, s2, coef, m, lg, valid);
+            keys[i0 + u * stride] = valid ? __float_as_int(s1 > 0.f ? s1 : 0.f) : -1;
+            cnt += valid ? 1 : 0;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// |V| = the sum of the blocks' counts.  One workgroup: 4112 atomics on one address from k_ohem_keys itself took longer (35 us
+// in the kernel trace) than the pass.
+__global__ __launch_bounds__(256) void k_ohem_count(const int* __restrict__ counts, int blocks, unsigned long long* __restrict__ nvalid) {
+    __shared__ unsigned long long red[4];
+    unsigned long long n = 0;
+    for (int i = threadIdx.x; i < blocks; i += 256) n += (unsigned long long)counts[i];
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) nvalid[0] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// Few, long-lived workgroups (two per compute unit, 8 keys in flight per thread): every workgroup flushes its non-empty bins with
+// one global atomic each, and the keys of a batch crowd into a few dozen bins of the top digit -- 2048 workgroups meant 2048
+// atomics on each of those addresses and 48 us for the digit-0 pass in the kernel trace.  hist is ADDED to (the caller zeroes it).
+// state = {prefix, rank, k, -}: digit 0 counts every valid key, a later digit the keys that agree with prefix above its own bits
+// (an arithmetic shift keeps the invalid pixels' -1 apart from every prefix, which is never negative)
+__global__ __launch_bounds__(256) void k_ohem_hist(const int* __restrict__ keys, int64_t npix, const long long* __restrict__ state,
+                                                   int digit, unsigned long long* __restrict__ hist) {
+    __shared__ unsigned int bins[OHEM_BINS];
+    const int shift = ohem_shift(digit), width = ohem_width(digit), nb = 1 << width;
+    for (int j = threadIdx.x; j < nb; j += blockDim.x) bins[j] = 0u;
+    __syncthreads();
+    const int top = shift + width;                                      // 31 at digit 0: key >> 31 is 0 (valid) or -1
+    const int want = digit == 0 ? 0 : (int)(state[0] >> top);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i0 < npix; i0 += OHEM_HIST_UNR * stride) {
+        int k[OHEM_HIST_UNR];
+#pragma unroll
+        for (int u = 0; u < OHEM_HIST_UNR; ++u) k[u] = i0 + u * stride < npix ? keys[i0 + u * stride] : -1;
+#pragma unroll
+        for (int u = 0; u < OHEM_HIST_UNR; ++u)
+            if ((k[u] >> top) == want) atomicAdd(&bins[(k[u] >> shift) & (nb - 1)], 1u);
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < nb; j += blockDim.x)
+        if (bins[j]) atomicAdd(&hist[j], (unsigned long long)bins[j]);
+}
+
+// one workgroup.  Thread t owns the bins nb-1 - t*per .. nb-1 - (t+1)*per + 1 (descending: rank 1 is the largest key); an
+// inclusive scan of the threads' totals finds the one thread whose run holds rank r, which walks its bins.  r == 0 (k == 0:
+// nothing is asked for) selects nothing.  r never exceeds the histogram's total: at digit 0 that is |V| >= k, later it is the
+// count of the bin chosen before.
+__global__ __launch_bounds__(256) void k_ohem_scan(const unsigned long long* __restrict__ hist,
+                                                   const unsigned long long* __restrict__ nvalid, int digit, long long min_kept,
+                                                   float nu0, long long* __restrict__ state, float* __restrict__ nu) {
+    __shared__ unsigned long long tot[2][256];
+    const int shift = ohem_shift(digit), width = ohem_width(digit), nb = 1 << width, per = nb / 256;
+    const int t = threadIdx.x;
+    long long prefix = 0, k, r;
+    if (digit == 0) {
+        const long long nv = (long long)nvalid[0];
+        k = min_kept < nv ? min_kept : nv;
+        r = k;
+    } else {
+        prefix = state[0];
+        r = state[1];
+        k = state[2];
+    }
+    unsigned long long h[8], mine = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        h[j] = j < per ? hist[nb - 1 - (t * per + j)] : 0ull;
+        mine += h[j];
+    }
+    __syncthreads();                                    // every thread has read state before anyone writes it
+    tot[0][t] = mine;
+    __syncthreads();
+    int cur = 0;
+    for (int o = 1; o < 256; o <<= 1) {                 // inclusive scan, integers: exact
+        tot[cur ^ 1][t] = tot[cur][t] + (t >= o ? tot[cur][t - o] : 0ull);
+        cur ^= 1;
+        __syncthreads();
+    }
+    const unsigned long long incl = tot[cur][t], excl = incl - mine, rr = (unsigned long long)r;
+    if (r > 0 && excl < rr && rr <= incl) {
+        unsigned long long above = excl;
+        int bin = 0;
+        bool found = false;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (j < per && !found) {
+                if (rr <= above + h[j]) {
+                    bin = nb - 1 - (t * per + j);
+                    found = true;
+                } else {
+                    above += h[j];
+                }
+            }
+        }
+        prefix |= (long long)bin << shift;
+        r = (long long)(rr - above);
+        state[0] = prefix;
+        state[1] = r;
+        state[2] = k;
+        if (digit == OHEM_DIGITS - 1) nu[0] = fminf(nu0, __int_as_float((int)prefix));
+    } else if (t == 0 && r <= 0) {
+        state[0] = 0;
+        state[1] = 0;
+        state[2] = k;
+        if (digit == OHEM_DIGITS - 1) nu[0] = nu0;      // min(nu0, +inf)
+    }
+}
+
+// k_loss_fwd's walk, per-thread order and block reduction over the kept pixels; the count rides along as a float (exact: a block
+// sees fewer than 2^24 pixels, the launcher checks it)
+template <typename LabelT>
+__global__ __launch_bounds__(256) void k_ohem_sums(const int* __restrict__ keys, const LabelT* __restrict__ labels, int C,
+                                                   int64_t npix, const float* __restrict__ cw, const int* __restrict__ nu_bits,
+                                                   float* __restrict__ partials, int nblocks) {
+    constexpr int UNR = 4;
+    __shared__ float red[3][4];
+    const int nb = nu_bits[0];
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i0 < npix; i0 += UNR * stride) {
+        int k[UNR];
+        long long y[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int64_t i = i0 + u * stride;
+            const bool in = i < npix;
+            k[u] = in ? keys[i] : -1;
+            y[u] = in ? (long long)labels[i] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            if (k[u] >= 0 && k[u] >= nb && y[u] >= 0 && y[u] < C) {
+                const float w = cw ? cw[y[u]] : 1.f;
+                s1 += w * __int_as_float(k[u]);
+                s2 += w;
+                s3 += 1.f;
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        s1 += __shfl_down(s1, o);
+        s2 += __shfl_down(s2, o);
+        s3 += __shfl_down(s3, o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[0][wave] = s1;
+        red[1][wave] = s2;
+        red[2][wave] = s3;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int v = threadIdx.x;
+        partials[(int64_t)v * nblocks + blockIdx.x] = (red[v][0] + red[v][1]) + (red[v][2] + red[v][3]);
+    }
+}
+
+// out = {loss, 1 / sum_K w}; both 0 when nothing is kept (or the kept pixels' weights sum to 0)
+__global__ void k_ohem_loss(const double* __restrict__ sums, float* __restrict__ out) {
+    const bool any = sums[2] > 0.0 && sums[1] > 0.0;
+    out[0] = any ? (float)(sums[0] / sums[1]) : 0.f;
+    out[1] = any ? (float)(1.0 / sums[1]) : 0.f;
+}
+
+template <typename LabelT, int CT>
+__global__ __launch_bounds__(256) void k_ohem_bwd(const float* __restrict__ logits, const LabelT* __restrict__ labels, int Crt,
+                                                  int64_t HW, int64_t npix, const float* __restrict__ cw,
+                                                  const int* __restrict__ keys, const int* __restrict__ nu_bits,
+                                                  const float* __restrict__ lossinv, const float* __restrict__ upstream,
+                                                  float* __restrict__ grad) {
+    constexpr int UNR = 4, CMAX = CT > 0 ? CT : OVL_CMAX;
+    const int C = CT > 0 ? CT : Crt;
+    const int nb = nu_bits[0];
+    const float f = upstream[0] * lossinv[1];
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i0 < npix; i0 += UNR * stride) {
+        float z[UNR][CMAX];
+        long long y[UNR];
+        int64_t off[UNR];
+        bool kept[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int64_t i = i0 + u * stride;
+            const bool in = i < npix;
+            const int64_t ii = in ? i : 0;
+            const int64_t b = ii / HW, p = ii - b * HW;
+            off[u] = in ? b * C * HW + p : -1;
+            const int k = in ? keys[ii] : -1;
+            y[u] = in ? (long long)labels[ii] : -1;
+            kept[u] = k >= 0 && k >= nb && y[u] >= 0 && y[u] < C;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) z[u][c] = (kept[u] && c < C) ? logits[b * C * HW + c * HW + p] : 0.f;   // dropped: not read
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            if (off[u] < 0) continue;
+            float m = z[u][0];
+#pragma unroll
+            for (int c = 1; c < CMAX; ++c) m = c < C ? fmaxf(m, z[u][c]) : m;
+            float se = 0.f;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) se += c < C ? expf(z[u][c] - m) : 0.f;
+            const float lg = logf(se);
+            const float wf = kept[u] ? (cw ? cw[y[u]] : 1.f) * f : 0.f;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+                if (c < C) {
+                    const float pc = expf(log_softmax(z[u][c], m, lg));
+                    grad[off[u] + c * HW] = kept[u] ? wf * (pc - (c == (int)y[u] ? 1.f : 0.f)) : 0.f;
+                }
+        }
+    }
+}
+
 }  // namespace iswm
 
 using namespace iswm;
@@ -563,4 +838,102 @@ extern "C" int iswm_overlap_loss_bwd(const float* logits, const void* labels, in
     }
 #undef OLAUNCH
     return check_launch("overlap_loss_bwd");
+}
+
+extern "C" int iswm_ohem_keys(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
+                              int ignore_index, int32_t* keys, int32_t* counts, int64_t* nvalid, iswm_stream_t stream) {
+    ISWM_REQUIRE(logits && labels && keys && counts && nvalid, "ohem_keys: null pointer");
+    ISWM_REQUIRE(B > 0 && HW > 0, "ohem_keys: bad shape");
+    ISWM_REQUIRE(C >= 1 && C <= OVL_CMAX, "ohem_keys: %d classes (hard-pixel mining takes 1 to %d)", C, OVL_CMAX);
+    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "ohem_keys: labels must be uint8 or int64");
+    const int64_t npix = (int64_t)B * HW;
+    const int blocks = iswm_loss_blocks(npix);
+    hipStream_t s = (hipStream_t)stream;
+#define KLAUNCH(T, CT)                                                                                             \
+    hipLaunchKernelGGL((k_ohem_keys<T, CT>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C, HW, npix, \
+                       ignore_index, keys, counts)
+    if (label_bytes == 1) {
+        if (C == 2) KLAUNCH(uint8_t, 2);
+        else KLAUNCH(uint8_t, 0);
+    } else {
+        if (C == 2) KLAUNCH(int64_t, 2);
+        else KLAUNCH(int64_t, 0);
+    }
+#undef KLAUNCH
+    hipLaunchKernelGGL(k_ohem_count, dim3(1), dim3(256), 0, s, counts, blocks, (unsigned long long*)nvalid);
+    return check_launch("ohem_keys");
+}
+
+extern "C" int iswm_ohem_digits(void) { return OHEM_DIGITS; }
+extern "C" int iswm_ohem_bins(void) { return OHEM_BINS; }
+
+extern "C" int iswm_ohem_hist(const int32_t* keys, int64_t npix, const int64_t* state, int digit, int64_t* hist,
+                              iswm_stream_t stream) {
+    ISWM_REQUIRE(keys && state && hist && npix > 0, "ohem_hist: bad argument");
+    ISWM_REQUIRE(digit >= 0 && digit < OHEM_DIGITS, "ohem_hist: digit %d (there are %d)", digit, OHEM_DIGITS);
+    int64_t blocks = (npix + 256 * OHEM_HIST_UNR - 1) / (256 * OHEM_HIST_UNR);
+    if (blocks > 2 * device_cus()) blocks = 2 * device_cus();
+    hipLaunchKernelGGL(k_ohem_hist, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, keys, npix,
+                       (const long long*)state, digit, (unsigned long long*)hist);
+    return check_launch("ohem_hist");
+}
+
+extern "C" int iswm_ohem_scan(const int64_t* hist, const int64_t* nvalid, int digit, int64_t min_kept, float nu0,
+                              int64_t* state, float* nu, iswm_stream_t stream) {
+    ISWM_REQUIRE(hist && nvalid && state && nu, "ohem_scan: null pointer");
+    ISWM_REQUIRE(digit >= 0 && digit < OHEM_DIGITS, "ohem_scan: digit %d (there are %d)", digit, OHEM_DIGITS);
+    ISWM_REQUIRE(min_kept >= 0, "ohem_scan: min_kept must not be negative");
+    ISWM_REQUIRE(nu0 >= 0.f && nu0 < INFINITY, "ohem_scan: nu0 = -ln(thresh) must be finite and not negative (thresh in (0, 1])");
+    hipLaunchKernelGGL(k_ohem_scan, dim3(1), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)hist,
+                       (const unsigned long long*)nvalid, digit, (long long)min_kept, nu0 + 0.f, (long long*)state, nu);
+    return check_launch("ohem_scan");
+}
+
+extern "C" int iswm_ohem_sums(const int32_t* keys, const void* labels, int label_bytes, int64_t npix, int C,
+                              const float* class_weight, const float* nu, float* partials, double* sums,
+                              iswm_stream_t stream) {
+    ISWM_REQUIRE(keys && labels && nu && partials && sums, "ohem_sums: null pointer");
+    ISWM_REQUIRE(npix > 0 && npix <= ((int64_t)1 << 36), "ohem_sums: bad pixel count");
+    ISWM_REQUIRE(C >= 1 && C <= OVL_CMAX, "ohem_sums: %d classes (hard-pixel mining takes 1 to %d)", C, OVL_CMAX);
+    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "ohem_sums: labels must be uint8 or int64");
+    const int blocks = iswm_loss_blocks(npix);
+    hipStream_t s = (hipStream_t)stream;
+    if (label_bytes == 1)
+        hipLaunchKernelGGL((k_ohem_sums<uint8_t>), dim3(blocks), dim3(256), 0, s, keys, (const uint8_t*)labels, C, npix,
+                           class_weight, (const int*)nu, partials, blocks);
+    else
+        hipLaunchKernelGGL((k_ohem_sums<int64_t>), dim3(blocks), dim3(256), 0, s, keys, (const int64_t*)labels, C, npix,
+                           class_weight, (const int*)nu, partials, blocks);
+    hipLaunchKernelGGL(k_overlap_finalize, dim3(3), dim3(64), 0, s, partials, blocks, sums);
+    return check_launch("ohem_sums");
+}
+
+extern "C" int iswm_ohem_loss(const double* sums, float* out, iswm_stream_t stream) {
+    ISWM_REQUIRE(sums && out, "ohem_loss: null pointer");
+    hipLaunchKernelGGL(k_ohem_loss, dim3(1), dim3(1), 0, (hipStream_t)stream, sums, out);
+    return check_launch("ohem_loss");
+}
+
+extern "C" int iswm_ohem_bwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
+                             const float* class_weight, const int32_t* keys, const float* nu, const float* lossinv,
+                             const float* upstream, float* grad, iswm_stream_t stream) {
+    ISWM_REQUIRE(logits && labels && keys && nu && lossinv && upstream && grad, "ohem_bwd: null pointer");
+    ISWM_REQUIRE(B > 0 && HW > 0, "ohem_bwd: bad shape");
+    ISWM_REQUIRE(C >= 1 && C <= OVL_CMAX, "ohem_bwd: %d classes (hard-pixel mining takes 1 to %d)", C, OVL_CMAX);
+    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "ohem_bwd: labels must be uint8 or int64");
+    const int64_t npix = (int64_t)B * HW;
+    const int blocks = iswm_loss_blocks(npix);
+    hipStream_t s = (hipStream_t)stream;
+#define BLAUNCH(T, CT)                                                                                            \
+    hipLaunchKernelGGL((k_ohem_bwd<T, CT>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C, HW, npix, \
+                       class_weight, keys, (const int*)nu, lossinv, upstream, grad)
+    if (label_bytes == 1) {
+        if (C == 2) BLAUNCH(uint8_t, 2);
+        else BLAUNCH(uint8_t, 0);
+    } else {
+        if (C == 2) BLAUNCH(int64_t, 2);
+        else BLAUNCH(int64_t, 0);
+    }
+#undef BLAUNCH
+    return check_launch("ohem_bwd");
 }

@@ -13,6 +13,7 @@ import collections
 import ctypes
 import enum
 import functools
+import math
 
 import numpy as np
 import torch
@@ -1069,6 +1070,118 @@ def overlap_loss_bwd(logits, labels, weight, ignore_index, coef, upstream):
     grad = torch.empty_like(logits)
     call("iswm_overlap_loss_bwd", _p(logits), _p(labels), labels.element_size(), b, c, hw, _p(weight), int(ignore_index),
          _p(coef), _p(upstream), _p(grad), _stream())
+    return grad
+
+
+def _ohem_args(logits, labels, weight):
+    if not (logits.dim() == 4 and logits.dtype == torch.float32 and logits.is_cuda):
+        raise ValueError("hard-pixel mining expects fp32 CUDA logits [B,C,H,W] (there is no CPU fallback)")
+    logits = logits.contiguous()
+    b, c, h, w = logits.shape
+    if c > 8:
+        raise ValueError("hard-pixel mining takes at most 8 classes (got %d)" % c)
+    assert labels.shape == (b, h, w) and labels.dtype in (torch.uint8, torch.int64)
+    assert weight is None or (weight.dtype == torch.float32 and weight.numel() == c and weight.is_cuda)
+    return logits, labels.contiguous(), b, c, h * w
+
+
+def ohem_nu0(thresh):
+    """float32(-ln thresh): a pixel whose true-class probability is at most thresh has nll >= this (thresh 1 -> +0)"""
+    if not 0.0 < thresh <= 1.0:
+        raise ValueError("thresh must lie in (0, 1] (got %r)" % (thresh,))
+    return float(torch.tensor(-math.log(thresh) + 0.0, dtype=torch.float32))
+
+
+def ohem_keys(logits, labels, ignore_index):
+    """-> (keys int32 [B,H,W]: the bit pattern of the pixel's nll, -1 at an invalid pixel; nvalid int64 [1] = |V|), on the device"""
+    logits, labels, b, c, hw = _ohem_args(logits, labels, None)
+    keys = torch.empty(labels.shape, dtype=torch.int32, device=logits.device)
+    nvalid = torch.empty((1,), dtype=torch.int64, device=logits.device)
+    counts = torch.empty((_lib.load().iswm_loss_blocks(b * hw),), dtype=torch.int32, device=logits.device)
+    call("iswm_ohem_keys", _p(logits), _p(labels), labels.element_size(), b, c, hw, int(ignore_index), _p(keys), _p(counts),
+         _p(nvalid), _stream())
+    return keys, nvalid
+
+
+def ohem_state(device):
+    """the select state {prefix, remaining rank, k, -} (int64 [4]) and nu (fp32 [1]); scan(0) initialises the state"""
+    return torch.zeros((4,), dtype=torch.int64, device=device), torch.empty((1,), dtype=torch.float32, device=device)
+
+
+def ohem_hist(keys, state, digit, out=None):
+    """-> hist int64 [2048]: the counts of digit `digit` among the keys carrying the prefix in `state` (digit 0: every valid
+    key), ADDED to `out` (a zeroed buffer of the caller's; a fresh one without)"""
+    assert keys.dtype == torch.int32 and keys.is_cuda and keys.is_contiguous()
+    assert state.dtype == torch.int64 and state.numel() == 4 and state.is_cuda
+    bins = _lib.load().iswm_ohem_bins()
+    hist = torch.zeros((bins,), dtype=torch.int64, device=keys.device) if out is None else out
+    assert hist.dtype == torch.int64 and hist.numel() == bins and hist.is_cuda and hist.is_contiguous()
+    call("iswm_ohem_hist", _p(keys), keys.numel(), _p(state), int(digit), _p(hist), _stream())
+    return hist
+
+
+def ohem_scan(hist, nvalid, digit, min_kept, nu0, state, nu):
+    """picks the bin of `hist` that holds the wanted rank: updates `state` in place; the last digit writes `nu`"""
+    assert hist.dtype == torch.int64 and hist.is_cuda and hist.numel() == _lib.load().iswm_ohem_bins()
+    assert nvalid.dtype == torch.int64 and nvalid.numel() == 1 and nvalid.is_cuda
+    assert state.dtype == torch.int64 and state.numel() == 4 and nu.dtype == torch.float32 and nu.numel() == 1
+    if min_kept < 0:
+        raise ValueError("min_kept must not be negative (got %r)" % (min_kept,))
+    call("iswm_ohem_scan", _p(hist), _p(nvalid), int(digit), int(min_kept), float(nu0), _p(state), _p(nu), _stream())
+    return state
+
+
+def ohem_select(keys, nvalid, min_kept, thresh, group=None):
+    """nu = min(float32(-ln thresh), the min(min_kept, |V|)-th largest key) as an fp32 device scalar [1]: three histogram /
+    scan rounds, nothing read back.  With `group`, |V| (in place) and every histogram are all-reduced: nu is the global batch's."""
+    nu0 = ohem_nu0(thresh)
+    state, nu = ohem_state(keys.device)
+    if group is not None:
+        import torch.distributed as dist
+        dist.all_reduce(nvalid, group=group)
+    digits = _lib.load().iswm_ohem_digits()
+    hists = torch.zeros((digits, _lib.load().iswm_ohem_bins()), dtype=torch.int64, device=keys.device)   # one fill for all three
+    for digit in range(digits):
+        hist = ohem_hist(keys, state, digit, out=hists[digit])
+        if group is not None:
+            dist.all_reduce(hist, group=group)
+        ohem_scan(hist, nvalid, digit, min_kept, nu0, state, nu)
+    return nu
+
+
+def ohem_sums(keys, labels, weight, nu):
+    """-> float64 [3] on the device: {sum_K w nll, sum_K w, |K|}, K = the pixels whose stored key is >= the bits of nu"""
+    assert keys.dtype == torch.int32 and keys.is_cuda and keys.is_contiguous() and keys.shape == labels.shape
+    assert labels.dtype in (torch.uint8, torch.int64) and nu.dtype == torch.float32 and nu.numel() == 1 and nu.is_cuda
+    labels = labels.contiguous()
+    c = 8 if weight is None else weight.numel()
+    assert weight is None or (weight.dtype == torch.float32 and weight.is_cuda and c <= 8)
+    npix = keys.numel()
+    blocks = _lib.load().iswm_loss_blocks(npix)
+    partials = torch.empty((3, blocks), dtype=torch.float32, device=keys.device)
+    sums = torch.empty((3,), dtype=torch.float64, device=keys.device)
+    call("iswm_ohem_sums", _p(keys), _p(labels), labels.element_size(), npix, c, _p(weight), _p(nu), _p(partials), _p(sums),
+         _stream())
+    return sums
+
+
+def ohem_loss(sums):
+    """sums (this process's, or all-reduced) -> fp32 [2] on the device: {loss, 1 / sum_K w}, both 0 if nothing is kept"""
+    assert sums.dtype == torch.float64 and sums.numel() == 3 and sums.is_cuda and sums.is_contiguous()
+    out = torch.empty((2,), dtype=torch.float32, device=sums.device)
+    call("iswm_ohem_loss", _p(sums), _p(out), _stream())
+    return out
+
+
+def ohem_bwd(logits, labels, weight, keys, nu, lossinv, upstream):
+    """upstream[0] * dL/dlogits, written once: w (p - onehot) / sum_K w on the kept pixels, exactly 0 elsewhere"""
+    logits, labels, b, c, hw = _ohem_args(logits, labels, weight)
+    assert keys.dtype == torch.int32 and keys.is_cuda and keys.is_contiguous() and keys.shape == labels.shape
+    assert nu.dtype == torch.float32 and nu.numel() == 1 and lossinv.dtype == torch.float32 and lossinv.numel() == 2
+    assert upstream.dtype == torch.float32 and upstream.numel() == 1 and upstream.is_cuda
+    grad = torch.empty_like(logits)
+    call("iswm_ohem_bwd", _p(logits), _p(labels), labels.element_size(), b, c, hw, _p(weight), _p(keys), _p(nu), _p(lossinv),
+         _p(upstream), _p(grad), _stream())
     return grad
 
 

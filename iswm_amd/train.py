@@ -25,7 +25,9 @@ forced by the reference not being runnable as shipped:
     confidence map.  Without the flag nothing is written there;
   * ``--clip_grad_norm`` and ``--ema_decay`` (both off by default) run inside the fused optimizer step (DESIGN.md
     section 18).  With EMA on, validation, best-model selection and the validation images use the EMA weights, the
-    checkpoint gains ``"ema_state"`` (``"model_state"`` stays the live weights) and ``--test_only --use_ema`` scores it.
+    checkpoint gains ``"ema_state"`` (``"model_state"`` stays the live weights) and ``--test_only --use_ema`` scores it;
+  * ``--ohem_thresh P`` (off by default) averages the CE over the hard pixels only: those predicted below P and at least
+    ``--ohem_min_kept`` per process, selected on the device.
 """
 import argparse
 import contextlib
@@ -43,7 +45,8 @@ from torch.utils import data
 from . import network, ops
 from .optim import FusedAdam, FusedAdamW, FusedSGD, ema_model_state
 from .parallel import DistributedDataParallelHIP
-from .utils.loss import CrossEntropyLoss, DiceLoss, TverskyLoss, calculate_class_weights, calculate_class_weights_resident
+from .utils.loss import (CrossEntropyLoss, DiceLoss, OhemCrossEntropyLoss, TverskyLoss, calculate_class_weights,
+                         calculate_class_weights_resident)
 from .val_results import save_validation_results
 
 
@@ -64,6 +67,13 @@ class _ArgParser(argparse.ArgumentParser):
             self.error("--clip_grad_norm must be a finite norm >= 0 (0 = off)")
         if not 0 <= opts.ema_decay < 1:
             self.error("--ema_decay must lie in [0, 1) (0 = off)")
+        if not 0 <= opts.ohem_thresh <= 1:
+            self.error("--ohem_thresh must lie in [0, 1] (0 = off, 1 = every valid pixel)")
+        if opts.ohem_min_kept < 0:
+            self.error("--ohem_min_kept must not be negative")
+        if opts.ohem_thresh > 0 and opts.overlap_loss != 'none':
+            self.error("--ohem_thresh with --overlap_loss %s: hard-pixel mining inside the combined criterion is not "
+                       "supported" % opts.overlap_loss)
         if opts.use_ema and not (opts.test_only and opts.ckpt):
             self.error("--use_ema evaluates the EMA weights of a checkpoint: it needs --test_only and --ckpt")
         return opts, rest
@@ -140,6 +150,13 @@ def get_argparser():
     parser.add_argument("--overlap_smooth", type=float, default=1.0, help="smoothing constant of the overlap term (> 0)")
     parser.add_argument("--overlap_classes", type=str, default='foreground', choices=['foreground', 'all'],
                         help="classes the overlap term averages over: every class but 0, or all")
+    parser.add_argument("--ohem_thresh", type=float, default=0.0, metavar="P",
+                        help="online hard-example mining: average the CE over the pixels whose true-class probability is at "
+                             "most P, and over at least the --ohem_min_kept hardest ones; --loss_type still selects the class "
+                             "weights; 0 = off, 1 = every valid pixel")
+    parser.add_argument("--ohem_min_kept", type=int, default=100000, metavar="N",
+                        help="pixels per process that hard-example mining always keeps (the N x world-size hardest of the "
+                             "global batch)")
     parser.add_argument("--clip_grad_norm", type=float, default=0.0, metavar="NORM",
                         help="clip the global L2 norm of the gradients to NORM inside the fused optimizer step "
                              "(torch.nn.utils.clip_grad_norm_'s factor; the stored gradients stay unclipped); 0 = off")
@@ -256,7 +273,8 @@ def setup_scheduler(optimizer, opts):
 
 
 def setup_criterion(opts, class_weights, group=None):
-    """train.py:454-459; with --overlap_loss the same CE (times --ce_weight) plus a Dice / Tversky / focal-Tversky term"""
+    """train.py:454-459; with --overlap_loss the same CE (times --ce_weight) plus a Dice / Tversky / focal-Tversky term; with
+    --ohem_thresh the same CE over the hard pixels only"""
     weight = None if opts.loss_type == 'ce_loss' else class_weights
     kind = getattr(opts, 'overlap_loss', 'none')
     if kind != 'none':
@@ -266,6 +284,10 @@ def setup_criterion(opts, class_weights, group=None):
             return DiceLoss(**common)
         return TverskyLoss(alpha=opts.tversky_alpha, beta=opts.tversky_beta,
                            gamma=opts.tversky_gamma if kind == 'focal_tversky' else 1.0, **common)
+    if getattr(opts, 'ohem_thresh', 0.0) > 0:
+        world = dist.get_world_size(group) if group is not None else 1      # --ohem_min_kept is per process, like --batch_size
+        return OhemCrossEntropyLoss(thresh=opts.ohem_thresh, min_kept=opts.ohem_min_kept * world, weight=weight,
+                                    ignore_index=255, group=group)
     if opts.loss_type == 'ce_loss':
         return CrossEntropyLoss(ignore_index=255, reduction='mean', group=group)
     return CrossEntropyLoss(weight=class_weights, ignore_index=255, reduction='mean', group=group)
@@ -569,6 +591,7 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
     # the context, from the live ones
     ema_weights = optimizer.ema_weights if optimizer.ema_enabled else contextlib.nullcontext
     clipping = bool(getattr(opts, "clip_grad_norm", 0.0))
+    mining = isinstance(criterion, OhemCrossEntropyLoss)
 
     sequence_val = opts.val_metrics == 'sequence'
     if sequence_val:
@@ -610,6 +633,9 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
                 if clipping:                                    # one read-back per interval; None until a step has clipped
                     last = optimizer.last_grad_norm
                     norm = ", grad norm=%s" % ("n/a" if last is None else "%.4e" % float(last))
+                if mining:                                      # the last step's kept pixels of the global batch: one read-back
+                    kept = int(criterion.last_kept)
+                    norm += ", kept=%d (%.2f%%)" % (kept, 100.0 * kept / (labels.numel() * world))
                 print("Epoch %d, Itrs %d/%d, Loss=%.6f, lr=%.3e, %.1f img/s%s" %
                       (cur_epochs, cur_itrs, opts.total_itrs, avg, optimizer.param_groups[0]['lr'], n_last / dt, norm))
                 interval_loss.zero_()

@@ -154,6 +154,63 @@ class DiceLoss(TverskyLoss):
         super().__init__(alpha=0.5, beta=0.5, **kw)
 
 
+class _OhemLossFn(torch.autograd.Function):
+    """The weighted CE over the hard pixels (csrc/loss.hip): keys, an exact radix select of nu on the device, the kept sums;
+    the backward pass decides `kept` from the stored keys and writes the finished gradient once.  Nothing is read back.  With
+    `group`, |V|, every digit's histogram and the three sums are all-reduced between the kernel that writes and the kernel
+    that reads them: nu, K and sum_K w are the global batch's, and the SUM gradient all-reduce of parallel.py yields the
+    gradient of the global loss."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, ignore_index, thresh, min_kept, group):
+        keys, nvalid = ops.ohem_keys(logits, labels, ignore_index)
+        nu = ops.ohem_select(keys, nvalid, min_kept, thresh, group)
+        sums = ops.ohem_sums(keys, labels, weight, nu)
+        if group is not None:
+            import torch.distributed as dist
+            dist.all_reduce(sums, group=group)
+        out = ops.ohem_loss(sums)
+        ctx.save_for_backward(logits, labels, weight, keys, nu, out)
+        ctx.mark_non_differentiable(sums, nu)
+        return out[0].clone(), sums, nu
+
+    @staticmethod
+    def backward(ctx, upstream, _sums, _nu):
+        logits, labels, weight, keys, nu, out = ctx.saved_tensors
+        up = upstream.reshape(1).contiguous().to(torch.float32)
+        grad = ops.ohem_bwd(logits, labels, weight, keys, nu, out, up)
+        return grad, None, None, None, None, None, None
+
+
+class OhemCrossEntropyLoss(nn.Module):
+    """Online hard-example mining (bootstrapped cross-entropy): CrossEntropyLoss(weight, ignore_index) averaged over the
+    pixels whose true-class probability is at most `thresh`, and over at least the `min_kept` hardest valid pixels of the
+    batch (ties at the threshold are all kept).  thresh = 1 keeps every valid pixel: the plain weighted CE.  `min_kept`
+    counts pixels of the whole batch (under `group`: of all ranks together).  At most 8 classes.
+
+    `last_kept` is a 0-dim device view of the number of kept pixels of the last call and `last_nu` one of the loss threshold
+    it selected; reading either synchronises."""
+
+    def __init__(self, thresh=0.7, min_kept=100000, weight=None, ignore_index=255, group=None):
+        super().__init__()
+        if not 0.0 < thresh <= 1.0:
+            raise ValueError("thresh must lie in (0, 1] (got %r)" % (thresh,))
+        if int(min_kept) != min_kept or min_kept < 0:
+            raise ValueError("min_kept must be a non-negative integer (got %r)" % (min_kept,))
+        self.register_buffer('weight', None if weight is None else weight.detach().float().clone())
+        self.thresh, self.min_kept = float(thresh), int(min_kept)
+        self.ignore_index = ignore_index
+        self.group = group
+        self.last_kept = self.last_nu = None
+
+    def forward(self, inputs, targets):
+        targets = _check(inputs, targets)
+        w = None if self.weight is None else self.weight.to(inputs.device)
+        loss, sums, nu = _OhemLossFn.apply(inputs, targets, w, self.ignore_index, self.thresh, self.min_kept, self.group)
+        self.last_kept, self.last_nu = sums[2], nu[0]
+        return loss
+
+
 def create_loss(loss_type="focal", temporal_loss="none", temporal_weight=0.5, **kwargs):
     """reference utils/loss.py:37-39"""
     return FocalLoss(**kwargs)
