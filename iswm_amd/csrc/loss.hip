@@ -14,6 +14,8 @@
 // (double precision, bit-reproducible) and iswm_loss_bwd_scale applies upstream/normaliser.
 // Under data parallelism the host all-reduces sums[2] between the two so that the
 // normaliser is the GLOBAL sum of weights, as the reference's gathered-logits loss has it.
+#include <type_traits>
+
 #include "common.h"
 
 namespace iswm {
@@ -33,48 +35,118 @@ __device__ __forceinline__ float log_softmax(float z, float m, float lg) {
     return fabsf(m) < LSE_SPLIT ? z - (m + lg) : (z - m) - lg;
 }
 
-// one pixel: value terms and the unnormalised gradient coefficient
-__device__ __forceinline__ void loss_pixel(const float* zc, int C, long long y, const float* __restrict__ cw, int ignore_index,
-                                           float alpha, float gamma, int mode, float& s1, float& s2, float& coef, float& m,
-                                           float& lg, bool& valid) {
-    m = zc[0];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, zc[c]);
+// the pixels every criterion counts: a label that is ignore_index or no class index adds no term and has a gradient of exactly 0
+__device__ __forceinline__ bool valid_label(long long y, int C, int ignore_index) {
+    return (y != (long long)ignore_index) && y >= 0 && y < C;
+}
+
+// m = the largest of the pixel's C logits (a register array) and lg = log sum exp(z - m), both in the order c = 0 .. C-1
+__device__ __forceinline__ void softmax_stats(const float* z, int C, float& m, float& lg) {
+    m = z[0];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, z[c]);
     float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(zc[c] - m);
+    for (int c = 0; c < C; ++c) se += expf(z[c] - m);
     lg = logf(se);
-    valid = (y != (long long)ignore_index) && y >= 0 && y < C;
-    coef = 0.f;  // dL_i/dce_i * w[y]
-    if (valid) {
-        const float w = cw ? cw[y] : 1.f;
-        float zy = zc[0];
-        for (int c = 1; c < C; ++c) zy = (c == (int)y) ? zc[c] : zy;
-        const float nll = -log_softmax(zy, m, lg);
-        if (mode == 0) {
-            s1 += w * nll;
-            s2 += w;
-            coef = w;
+}
+
+// one valid pixel of weight w: its value terms, and coef = dL_i/dce_i * w (the gradient is coef * (p - onehot), unnormalised)
+__device__ __forceinline__ void loss_terms(float nll, float w, float alpha, float gamma, int mode, float& s1, float& s2, float& coef) {
+    if (mode == 0) {
+        s1 = fmaf(w, nll, s1);      // spelt out: the focal branch's w * nll must not draw this product out of the fused add
+        s2 += w;
+        coef = w;
+    } else {
+        const float ce = w * nll;
+        float f, dfdce;
+        if (gamma == 0.f) {
+            f = alpha * ce;
+            dfdce = alpha;
         } else {
-            const float ce = w * nll;
-            float f, dfdce;
-            if (gamma == 0.f) {
-                f = alpha * ce;
-                dfdce = alpha;
-            } else {
-                const float pt = expf(-ce);
-                const float om = 1.f - pt;
-                const float pw = powf(om, gamma);
-                f = alpha * pw * ce;
-                dfdce = (ce > 0.f && om > 0.f) ? alpha * (pw + gamma * powf(om, gamma - 1.f) * pt * ce) : 0.f;
-            }
-            s1 += f;
-            s2 += w;
-            coef = dfdce * w;
+            const float pt = expf(-ce);
+            const float om = 1.f - pt;
+            const float pw = powf(om, gamma);
+            f = alpha * pw * ce;
+            dfdce = (ce > 0.f && om > 0.f) ? alpha * (pw + gamma * powf(om, gamma - 1.f) * pt * ce) : 0.f;
         }
+        s1 += f;
+        s2 += w;
+        coef = dfdce * w;
     }
 }
 
-// UNR independent pixels per thread and iteration (consecutive threads take consecutive pixels: every load and store of
-// a wave is one contiguous 256-B run): 4x the bytes in flight of the one-pixel loop, which ran at 1.7 TB/s.
+// one pixel with its logits in registers: value terms and the unnormalised gradient coefficient (0 at an invalid pixel)
+__device__ __forceinline__ void loss_pixel(const float* zc, int C, long long y, const float* __restrict__ cw,
+                                           int ignore_index, float alpha, float gamma, int mode, float& s1, float& s2,
+                                           float& coef, float& m, float& lg, bool& valid) {
+    softmax_stats(zc, C, m, lg);
+    valid = valid_label(y, C, ignore_index);
+    coef = 0.f;
+    if (valid) {
+        float zy = zc[0];
+        for (int c = 1; c < C; ++c) zy = (c == (int)y) ? zc[c] : zy;
+        loss_terms(-log_softmax(zy, m, lg), cw ? cw[y] : 1.f, alpha, gamma, mode, s1, s2, coef);
+    }
+}
+
+// The pixel walk of every kernel that reads logits: thread t of the grid takes the pixels i0 + u * stride, u < LOSS_UNR, of one
+// iteration of `for (i0 = global thread index; i0 < npix; i0 += LOSS_UNR * stride)`, stride = the grid's thread count.
+// LOSS_UNR independent pixels per thread and iteration (consecutive threads take consecutive pixels: every load and store of
+// a wave is one contiguous 256-B run): 4x the bytes in flight of the one-pixel loop, which ran at 1.7 TB/s.  Kernels on this
+// walk add their pixels in the same per-thread order, which is what makes their sums agree bit for bit.
+// -> per pixel u: z[u] (the C logits, 0 beyond C), y[u] (the label; ypad past the end), off[u] (the offset of class 0 in
+// logits / grad; -1 past the end) and in[u] (i < npix).  A kernel that writes no gradient passes no_offsets() for off and
+// tests in[u]: an offset that is formed and then dropped still costs it two scalar registers.
+// read(u, i, y) says whether pixel i's logits are wanted: where it is false they are not loaded (z[u] = 0) -- the backward
+// pass of the hard-pixel loss reads 8 B only where a pixel is kept.
+constexpr int LOSS_UNR = 4;
+struct every_pixel {
+    __device__ bool operator()(int, int64_t, long long) const { return true; }
+};
+struct no_offsets {
+    struct sink {
+        __device__ void operator=(int64_t) const {}
+    };
+    __device__ sink operator[](int) const { return sink(); }
+};
+template <int CMAX, typename LabelT, typename Read, typename Off>
+__device__ __forceinline__ void gather_pixels(const float* logits, const LabelT* labels, int C, int64_t HW, int64_t npix, int64_t i0,
+                                              int64_t stride, long long ypad, Read read, float (&z)[LOSS_UNR][CMAX],
+                                              long long (&y)[LOSS_UNR], Off&& off, bool (&in)[LOSS_UNR]) {
+#pragma unroll
+    for (int u = 0; u < LOSS_UNR; ++u) {
+        const int64_t i = i0 + u * stride;
+        in[u] = i < npix;
+        const int64_t ii = in[u] ? i : 0;
+        const int64_t b = ii / HW, p = ii - b * HW;
+        off[u] = in[u] ? b * C * HW + p : -1;
+        y[u] = in[u] ? (long long)labels[ii] : ypad;
+        const bool rd = in[u] && read(u, ii, y[u]);
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) z[u][c] = (rd && c < C) ? logits[b * C * HW + c * HW + p] : 0.f;
+    }
+}
+
+// Block sums of N values per thread in a fixed order, no atomics: shuffle tree within each of the 4 waves, lane 0 -> red[k][wave],
+// barrier.  block_total(red[k]) is then value k's sum over the 256 threads, (wave 0 + wave 1) + (wave 2 + wave 3).
+// Callers accumulate in scalars and pack them into v right before the call: as one array across the pixel loop the sums of
+// k_overlap_sums reached registers late and the kernel went from 81 to 320 VGPRs.
+template <typename T, int N>
+__device__ __forceinline__ void block_reduce(T (&v)[N], T (&red)[N][4]) {
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] += __shfl_down(v[k], o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) red[k][threadIdx.x >> 6] = v[k];
+    }
+    __syncthreads();
+}
+template <typename T>
+__device__ __forceinline__ T block_total(const T (&r)[4]) {
+    return (r[0] + r[1]) + (r[2] + r[3]);
+}
+
 // CT > 0: class count known at compile time (2: the binary internal-wave masks), logits held in registers.
 template <typename LabelT, int CT>
 __global__ __launch_bounds__(256) void k_loss_fwd(const float* __restrict__ logits,
@@ -83,7 +155,7 @@ __global__ __launch_bounds__(256) void k_loss_fwd(const float* __restrict__ logi
                                                   float alpha, float gamma, int mode,
                                                   float* __restrict__ grad, float* __restrict__ partials,
                                                   int nblocks) {
-    constexpr int UNR = 4, CMAX = CT > 0 ? CT : 8;
+    constexpr int UNR = LOSS_UNR, CMAX = CT > 0 ? CT : 8;
     const int C = CT > 0 ? CT : Crt;
     __shared__ float red[2][4];
     float s1 = 0.f, s2 = 0.f;
@@ -93,17 +165,8 @@ __global__ __launch_bounds__(256) void k_loss_fwd(const float* __restrict__ logi
             float z[UNR][CMAX];
             long long y[UNR];
             int64_t off[UNR];
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const int64_t i = i0 + u * stride;
-                const bool in = i < npix;
-                const int64_t ii = in ? i : 0;
-                const int64_t b = ii / HW, p = ii - b * HW;
-                off[u] = in ? b * C * HW + p : -1;
-                y[u] = in ? (long long)labels[ii] : (long long)ignore_index;
-#pragma unroll
-                for (int c = 0; c < CMAX; ++c) z[u][c] = (in && c < C) ? logits[b * C * HW + c * HW + p] : 0.f;
-            }
+            bool in[UNR];
+            gather_pixels(logits, labels, C, HW, npix, i0, stride, (long long)ignore_index, every_pixel(), z, y, off, in);
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 if (off[u] < 0) continue;
@@ -129,34 +192,9 @@ __global__ __launch_bounds__(256) void k_loss_fwd(const float* __restrict__ logi
                 for (int c = 0; c < C; ++c) se += expf(zp[c * HW] - m);
                 const float lg = logf(se);
                 const long long yy = (long long)labels[i];
-                const bool valid = (yy != (long long)ignore_index) && yy >= 0 && yy < C;
+                const bool valid = valid_label(yy, C, ignore_index);
                 float coef = 0.f;
-                if (valid) {
-                    const float zy = zp[yy * HW];
-                    const float w = cw ? cw[yy] : 1.f;
-                    const float nll = -log_softmax(zy, m, lg);
-                    if (mode == 0) {
-                        s1 += w * nll;
-                        s2 += w;
-                        coef = w;
-                    } else {
-                        const float ce = w * nll;
-                        float f, dfdce;
-                        if (gamma == 0.f) {
-                            f = alpha * ce;
-                            dfdce = alpha;
-                        } else {
-                            const float pt = expf(-ce);
-                            const float om = 1.f - pt;
-                            const float pw = powf(om, gamma);
-                            f = alpha * pw * ce;
-                            dfdce = (ce > 0.f && om > 0.f) ? alpha * (pw + gamma * powf(om, gamma - 1.f) * pt * ce) : 0.f;
-                        }
-                        s1 += f;
-                        s2 += w;
-                        coef = dfdce * w;
-                    }
-                }
+                if (valid) loss_terms(-log_softmax(zp[yy * HW], m, lg), cw ? cw[yy] : 1.f, alpha, gamma, mode, s1, s2, coef);
                 float* g = grad + b * C * HW + p;
                 for (int c = 0; c < C; ++c) {
                     const float pc = expf(log_softmax(zp[c * HW], m, lg));
@@ -165,20 +203,11 @@ __global__ __launch_bounds__(256) void k_loss_fwd(const float* __restrict__ logi
             }
         }
     }
-    // block reduction: wave shuffle, then across the 4 waves (fixed order)
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_down(s1, o);
-        s2 += __shfl_down(s2, o);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][wave] = s1;
-        red[1][wave] = s2;
-    }
-    __syncthreads();
+    float s[2] = {s1, s2};
+    block_reduce(s, red);
     if (threadIdx.x == 0) {
-        partials[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        partials[nblocks + blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        partials[blockIdx.x] = block_total(red[0]);
+        partials[nblocks + blockIdx.x] = block_total(red[1]);
     }
 }
 
@@ -236,7 +265,7 @@ __global__ __launch_bounds__(256) void k_argmax_nchw(const float* __restrict__ l
 }
 
 // ---- region-overlap losses (soft Dice / Tversky / focal-Tversky) next to the weighted CE: two passes -------------------------
-//   V = valid pixels (loss_pixel's rule), p = softmax(z), g = one-hot(y)
+//   V = valid pixels (valid_label), p = softmax(z), g = one-hot(y)
 //   I_c = sum_V p_ic g_ic,  P_c = sum_V p_ic,  G_c = sum_V g_ic (an exact count)
 //   D_c = I_c + alpha (P_c - I_c) + beta (G_c - I_c) + s,  T_c = (I_c + s) / D_c,  l_c = max(1 - T_c, 0)^gamma
 //   L   = lambda_ce sum(w nll) / sum(w) + lambda_ov mean_{c in S} l_c
@@ -254,28 +283,19 @@ template <typename LabelT, int CT>
 __global__ __launch_bounds__(256) void k_overlap_sums(const float* __restrict__ logits, const LabelT* __restrict__ labels,
                                                       int Crt, int64_t HW, int64_t npix, const float* __restrict__ cw,
                                                       int ignore_index, float* __restrict__ partials, int nblocks) {
-    constexpr int UNR = 4, CMAX = CT > 0 ? CT : OVL_CMAX;
+    constexpr int UNR = LOSS_UNR, CMAX = CT > 0 ? CT : OVL_CMAX;
     const int C = CT > 0 ? CT : Crt;
     __shared__ float red[2 + 3 * CMAX][4];
     float s1 = 0.f, s2 = 0.f, si[CMAX], sp[CMAX], sg[CMAX];
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) si[c] = sp[c] = sg[c] = 0.f;
-    // the pixel walk of k_loss_fwd: the two CE partials come out bit for bit as iswm_loss_fwd writes them
+    // gather_pixels, loss_pixel and block_reduce as in k_loss_fwd: the two CE partials are iswm_loss_fwd's bit for bit
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i0 < npix; i0 += UNR * stride) {
         float z[UNR][CMAX];
         long long y[UNR];
         bool in[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const int64_t i = i0 + u * stride;
-            in[u] = i < npix;
-            const int64_t ii = in[u] ? i : 0;
-            const int64_t b = ii / HW, p = ii - b * HW;
-            y[u] = in[u] ? (long long)labels[ii] : (long long)ignore_index;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) z[u][c] = (in[u] && c < C) ? logits[b * C * HW + c * HW + p] : 0.f;
-        }
+        gather_pixels(logits, labels, C, HW, npix, i0, stride, (long long)ignore_index, every_pixel(), z, y, no_offsets(), in);
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             if (!in[u]) continue;
@@ -294,33 +314,18 @@ __global__ __launch_bounds__(256) void k_overlap_sums(const float* __restrict__ 
                 }
         }
     }
-    // lanes -> LDS -> one partial per block and value, fixed order, no atomics
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_down(s1, o);
-        s2 += __shfl_down(s2, o);
+    float s[2 + 3 * CMAX] = {s1, s2};          // {s1, s2, I[CMAX], P[CMAX], G[CMAX]}
 #pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            si[c] += __shfl_down(si[c], o);
-            sp[c] += __shfl_down(sp[c], o);
-            sg[c] += __shfl_down(sg[c], o);
-        }
+    for (int c = 0; c < CMAX; ++c) {
+        s[2 + c] = si[c];
+        s[2 + CMAX + c] = sp[c];
+        s[2 + 2 * CMAX + c] = sg[c];
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][wave] = s1;
-        red[1][wave] = s2;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            red[2 + c][wave] = si[c];
-            red[2 + CMAX + c][wave] = sp[c];
-            red[2 + 2 * CMAX + c][wave] = sg[c];
-        }
-    }
-    __syncthreads();
+    block_reduce(s, red);
     const int v = threadIdx.x;                  // value index in the [2 + 3C] layout {s1, s2, I[C], P[C], G[C]}
     if (v < 2 + 3 * C) {
         const int k = v < 2 ? v : 2 + ((v - 2) / C) * CMAX + (v - 2) % C;
-        partials[(int64_t)v * nblocks + blockIdx.x] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+        partials[(int64_t)v * nblocks + blockIdx.x] = block_total(red[k]);
     }
 }
 
@@ -384,7 +389,7 @@ __global__ __launch_bounds__(256) void k_overlap_bwd(const float* __restrict__ l
                                                      int64_t HW, int64_t npix, const float* __restrict__ cw, int ignore_index,
                                                      const float* __restrict__ coef, const float* __restrict__ upstream,
                                                      float* __restrict__ grad) {
-    constexpr int UNR = 4, CMAX = CT > 0 ? CT : OVL_CMAX;
+    constexpr int UNR = LOSS_UNR, CMAX = CT > 0 ? CT : OVL_CMAX;
     const int C = CT > 0 ? CT : Crt;
     const float up = upstream ? upstream[0] : 1.f;
     const float a = coef[0];
@@ -399,22 +404,15 @@ __global__ __launch_bounds__(256) void k_overlap_bwd(const float* __restrict__ l
         float z[UNR][CMAX];
         long long y[UNR];
         int64_t off[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const int64_t i = i0 + u * stride;
-            const bool in = i < npix;
-            const int64_t ii = in ? i : 0;
-            const int64_t b = ii / HW, p = ii - b * HW;
-            off[u] = in ? b * C * HW + p : -1;
-            y[u] = in ? (long long)labels[ii] : (long long)ignore_index;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) z[u][c] = (in && c < C) ? logits[b * C * HW + c * HW + p] : 0.f;
-        }
+        bool in[UNR];
+        gather_pixels(logits, labels, C, HW, npix, i0, stride, (long long)ignore_index, every_pixel(), z, y, off, in);
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             if (off[u] < 0) continue;
             const long long yy = y[u];
-            const bool valid = (yy != (long long)ignore_index) && yy >= 0 && yy < C;
+            const bool valid = valid_label(yy, C, ignore_index);
+            // softmax_stats, unrolled by hand: on the shared loops this kernel takes 75 VGPRs at runtime C (6 waves per SIMD,
+            // not 7); same operations in the same order
             float m = z[u][0];
 #pragma unroll
             for (int c = 1; c < CMAX; ++c) m = c < C ? fmaxf(m, z[u][c]) : m;
@@ -441,7 +439,7 @@ __global__ __launch_bounds__(256) void k_overlap_bwd(const float* __restrict__ l
 }
 
 // ---- hard-pixel mining (OHEM / bootstrapped CE): the weighted CE over the pixels the model still gets wrong ---------------------
-//   V = valid pixels (loss_pixel's rule), nll_i as k_loss_fwd forms it, k = min(min_kept, |V|)
+//   V = valid pixels (valid_label), nll_i as loss_pixel forms it, k = min(min_kept, |V|)
 //   nu = min(float32(-ln thresh), k-th largest nll over V)   (+inf for the second term if k == 0)
 //   K = {i in V : nll_i >= nu},  L = sum_K w nll / sum_K w,  dL/dz = upstream w (p - g) / sum_K w on K, exactly 0 elsewhere
 // The gradient hangs on a global order statistic, so nothing can be written in the pass that forms the sums:
@@ -449,7 +447,7 @@ __global__ __launch_bounds__(256) void k_overlap_bwd(const float* __restrict__ l
 //   k_ohem_hist   keys -> the histogram of one digit of the keys that carry the prefix selected so far (LDS bins, integer atomics)
 //   k_ohem_scan   one workgroup: the bin that holds rank r -> prefix and remaining rank for the next digit; after the last
 //                 digit nu as a device scalar.  Three digits of 11 + 10 + 10 bits from the top of the 31 significant bits.
-//   k_ohem_sums   keys + labels -> per-block partials {sum_K w nll, sum_K w, |K|} on k_loss_fwd's walk, then k_overlap_finalize
+//   k_ohem_sums   keys + labels -> per-block partials {sum_K w nll, sum_K w, |K|} in gather_pixels' order, then k_overlap_finalize
 //   k_ohem_loss   sums -> {loss, 1 / sum_K w}
 //   k_ohem_bwd    logits + labels + keys + nu -> the finished gradient, once
 // Key order: nll >= 0 always (log se >= 0 because the largest class contributes exp(0) = 1; both forms of log_softmax are then
@@ -465,30 +463,25 @@ __global__ __launch_bounds__(256) void k_overlap_bwd(const float* __restrict__ l
 constexpr int OHEM_DIGITS = 3, OHEM_BINS = 2048, OHEM_HIST_UNR = 8;
 __host__ __device__ constexpr int ohem_shift(int d) { return d == 0 ? 20 : (d == 1 ? 10 : 0); }
 __host__ __device__ constexpr int ohem_width(int d) { return d == 0 ? 11 : 10; }
+// the kept decision of the sums and the backward pass: the STORED key against the bits of nu (the label guards the weight lookup)
+__device__ __forceinline__ bool ohem_kept(int key, int nu_bits, long long y, int C) {
+    return key >= 0 && key >= nu_bits && y >= 0 && y < C;
+}
 
 template <typename LabelT, int CT>
 __global__ __launch_bounds__(256) void k_ohem_keys(const float* __restrict__ logits, const LabelT* __restrict__ labels, int Crt,
                                                    int64_t HW, int64_t npix, int ignore_index, int* __restrict__ keys,
                                                    int* __restrict__ counts) {
-    constexpr int UNR = 4, CMAX = CT > 0 ? CT : OVL_CMAX;
+    constexpr int UNR = LOSS_UNR, CMAX = CT > 0 ? CT : OVL_CMAX;
     const int C = CT > 0 ? CT : Crt;
-    __shared__ int red[4];
+    __shared__ int red[1][4];
     int cnt = 0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i0 < npix; i0 += UNR * stride) {
         float z[UNR][CMAX];
         long long y[UNR];
         bool in[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const int64_t i = i0 + u * stride;
-            in[u] = i < npix;
-            const int64_t ii = in[u] ? i : 0;
-            const int64_t b = ii / HW, p = ii - b * HW;
-            y[u] = in[u] ? (long long)labels[ii] : (long long)ignore_index;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) z[u][c] = (in[u] && c < C) ? logits[b * C * HW + c * HW + p] : 0.f;
-        }
+        gather_pixels(logits, labels, C, HW, npix, i0, stride, (long long)ignore_index, every_pixel(), z, y, no_offsets(), in);
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             if (!in[u]) continue;
@@ -499,22 +492,20 @@ __global__ __launch_bounds__(256) void k_ohem_keys(const float* __restrict__ log
             cnt += valid ? 1 : 0;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    int s[1] = {cnt};
+    block_reduce(s, red);
+    if (threadIdx.x == 0) counts[blockIdx.x] = block_total(red[0]);
 }
 
 // |V| = the sum of the blocks' counts.  One workgroup: 4112 atomics on one address from k_ohem_keys itself took longer (35 us
 // in the kernel trace) than the pass.
 __global__ __launch_bounds__(256) void k_ohem_count(const int* __restrict__ counts, int blocks, unsigned long long* __restrict__ nvalid) {
-    __shared__ unsigned long long red[4];
+    __shared__ unsigned long long red[1][4];
     unsigned long long n = 0;
     for (int i = threadIdx.x; i < blocks; i += 256) n += (unsigned long long)counts[i];
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) nvalid[0] = (red[0] + red[1]) + (red[2] + red[3]);
+    unsigned long long s[1] = {n};
+    block_reduce(s, red);
+    if (threadIdx.x == 0) nvalid[0] = block_total(red[0]);
 }
 
 // Few, long-lived workgroups (two per compute unit, 8 keys in flight per thread): every workgroup flushes its non-empty bins with
@@ -609,13 +600,13 @@ __global__ __launch_bounds__(256) void k_ohem_scan(const unsigned long long* __r
     }
 }
 
-// k_loss_fwd's walk, per-thread order and block reduction over the kept pixels; the count rides along as a float (exact: a block
-// sees fewer than 2^24 pixels, the launcher checks it)
+// gather_pixels' per-thread pixel order (keys instead of logits) and block_reduce over the kept pixels; the count rides along
+// as a float (exact: a block sees fewer than 2^24 pixels, the launcher checks it)
 template <typename LabelT>
 __global__ __launch_bounds__(256) void k_ohem_sums(const int* __restrict__ keys, const LabelT* __restrict__ labels, int C,
                                                    int64_t npix, const float* __restrict__ cw, const int* __restrict__ nu_bits,
                                                    float* __restrict__ partials, int nblocks) {
-    constexpr int UNR = 4;
+    constexpr int UNR = LOSS_UNR;
     __shared__ float red[3][4];
     const int nb = nu_bits[0];
     float s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -632,30 +623,18 @@ __global__ __launch_bounds__(256) void k_ohem_sums(const int* __restrict__ keys,
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            if (k[u] >= 0 && k[u] >= nb && y[u] >= 0 && y[u] < C) {
+            if (ohem_kept(k[u], nb, y[u], C)) {
                 const float w = cw ? cw[y[u]] : 1.f;
-                s1 += w * __int_as_float(k[u]);
+                s1 = fmaf(w, __int_as_float(k[u]), s1);     // loss_terms' fused add: thresh = 1 gives iswm_loss_fwd's bits
                 s2 += w;
                 s3 += 1.f;
             }
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_down(s1, o);
-        s2 += __shfl_down(s2, o);
-        s3 += __shfl_down(s3, o);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][wave] = s1;
-        red[1][wave] = s2;
-        red[2][wave] = s3;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int v = threadIdx.x;
-        partials[(int64_t)v * nblocks + blockIdx.x] = (red[v][0] + red[v][1]) + (red[v][2] + red[v][3]);
-    }
+    float s[3] = {s1, s2, s3};
+    block_reduce(s, red);
+    const int v = threadIdx.x;
+    if (v < 3) partials[(int64_t)v * nblocks + blockIdx.x] = block_total(red[v]);
 }
 
 // out = {loss, 1 / sum_K w}; both 0 when nothing is kept (or the kept pixels' weights sum to 0)
@@ -671,7 +650,7 @@ __global__ __launch_bounds__(256) void k_ohem_bwd(const float* __restrict__ logi
                                                   const int* __restrict__ keys, const int* __restrict__ nu_bits,
                                                   const float* __restrict__ lossinv, const float* __restrict__ upstream,
                                                   float* __restrict__ grad) {
-    constexpr int UNR = 4, CMAX = CT > 0 ? CT : OVL_CMAX;
+    constexpr int UNR = LOSS_UNR, CMAX = CT > 0 ? CT : OVL_CMAX;
     const int C = CT > 0 ? CT : Crt;
     const int nb = nu_bits[0];
     const float f = upstream[0] * lossinv[1];
@@ -680,30 +659,15 @@ __global__ __launch_bounds__(256) void k_ohem_bwd(const float* __restrict__ logi
         float z[UNR][CMAX];
         long long y[UNR];
         int64_t off[UNR];
-        bool kept[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const int64_t i = i0 + u * stride;
-            const bool in = i < npix;
-            const int64_t ii = in ? i : 0;
-            const int64_t b = ii / HW, p = ii - b * HW;
-            off[u] = in ? b * C * HW + p : -1;
-            const int k = in ? keys[ii] : -1;
-            y[u] = in ? (long long)labels[ii] : -1;
-            kept[u] = k >= 0 && k >= nb && y[u] >= 0 && y[u] < C;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) z[u][c] = (kept[u] && c < C) ? logits[b * C * HW + c * HW + p] : 0.f;   // dropped: not read
-        }
+        bool in[UNR];
+        bool kept[UNR] = {};
+        const auto keep = [&](int u, int64_t i, long long yy) { return kept[u] = ohem_kept(keys[i], nb, yy, C); };
+        gather_pixels(logits, labels, C, HW, npix, i0, stride, -1, keep, z, y, off, in);      // dropped: logits not read
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             if (off[u] < 0) continue;
-            float m = z[u][0];
-#pragma unroll
-            for (int c = 1; c < CMAX; ++c) m = c < C ? fmaxf(m, z[u][c]) : m;
-            float se = 0.f;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) se += c < C ? expf(z[u][c] - m) : 0.f;
-            const float lg = logf(se);
+            float m, lg;
+            softmax_stats(z[u], C, m, lg);
             const float wf = kept[u] ? (cw ? cw[y[u]] : 1.f) * f : 0.f;
 #pragma unroll
             for (int c = 0; c < CMAX; ++c)
@@ -719,6 +683,30 @@ __global__ __launch_bounds__(256) void k_ohem_bwd(const float* __restrict__ logi
 
 using namespace iswm;
 
+// the kernel instantiation of a call: f(label type, CT) with CT = 2 (the binary masks: class count at compile time) or 0 (C at run time)
+template <typename F>
+static void by_label_and_classes(int label_bytes, int C, F&& f) {
+    if (label_bytes == 1) {
+        if (C == 2) f(uint8_t(), std::integral_constant<int, 2>());
+        else f(uint8_t(), std::integral_constant<int, 0>());
+    } else {
+        if (C == 2) f(int64_t(), std::integral_constant<int, 2>());
+        else f(int64_t(), std::integral_constant<int, 0>());
+    }
+}
+
+// the refusals the per-pixel entry points share, in this order; `takes` names the criterion whose kernels hold the classes in
+// registers (null: any C > 0 passes, the weighted CE streams the class axis beyond 8)
+static int refuse_pixel_args(const char* fn, bool pointers, bool shape, int C, const char* takes, int label_bytes) {
+    ISWM_REQUIRE(pointers, "%s: null pointer", fn);
+    ISWM_REQUIRE(shape, "%s: bad shape", fn);
+    ISWM_REQUIRE(!takes || (C >= 1 && C <= OVL_CMAX), "%s: %d classes (%s 1 to %d)", fn, C, takes, OVL_CMAX);
+    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "%s: labels must be uint8 or int64", fn);
+    return 0;
+}
+static const char* const OVERLAP_TAKES = "the overlap losses take";
+static const char* const OHEM_TAKES = "hard-pixel mining takes";
+
 extern "C" int iswm_loss_blocks(int64_t npix) {
     int64_t b = (npix + 1023) / 1024;      // 4 pixels per thread and iteration
     if (b > 8192) b = 8192;
@@ -729,23 +717,17 @@ extern "C" int iswm_loss_blocks(int64_t npix) {
 extern "C" int iswm_loss_fwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
                              const float* class_weight, int ignore_index, float alpha, float gamma, int mode,
                              float* grad_unnorm, float* partials, iswm_stream_t stream) {
-    ISWM_REQUIRE(logits && labels && grad_unnorm && partials, "loss_fwd: null pointer");
-    ISWM_REQUIRE(B > 0 && C > 0 && HW > 0 && mode >= 0 && mode <= 2, "loss_fwd: bad shape or mode");
-    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "loss_fwd: labels must be uint8 or int64");
+    if (refuse_pixel_args("loss_fwd", logits && labels && grad_unnorm && partials,
+                          B > 0 && C > 0 && HW > 0, C, nullptr, label_bytes)) return 1;
+    ISWM_REQUIRE(mode >= 0 && mode <= 2, "loss_fwd: bad mode");
     const int64_t npix = (int64_t)B * HW;
     const int blocks = iswm_loss_blocks(npix);
     hipStream_t s = (hipStream_t)stream;
-#define LLAUNCH(T, CT)                                                                                             \
-    hipLaunchKernelGGL((k_loss_fwd<T, CT>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C, HW, npix,  \
-                       class_weight, ignore_index, alpha, gamma, mode, grad_unnorm, partials, blocks)
-    if (label_bytes == 1) {
-        if (C == 2) LLAUNCH(uint8_t, 2);
-        else LLAUNCH(uint8_t, 0);
-    } else {
-        if (C == 2) LLAUNCH(int64_t, 2);
-        else LLAUNCH(int64_t, 0);
-    }
-#undef LLAUNCH
+    by_label_and_classes(label_bytes, C, [&](auto label, auto ct) {
+        using T = decltype(label);
+        hipLaunchKernelGGL((k_loss_fwd<T, decltype(ct)::value>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C,
+                           HW, npix, class_weight, ignore_index, alpha, gamma, mode, grad_unnorm, partials, blocks);
+    });
     return check_launch("loss_fwd");
 }
 
@@ -776,24 +758,16 @@ extern "C" int iswm_argmax_nchw(const float* logits, int B, int C, int64_t HW, i
 extern "C" int iswm_overlap_loss_fwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
                                      const float* class_weight, int ignore_index, float* partials, double* sums,
                                      iswm_stream_t stream) {
-    ISWM_REQUIRE(logits && labels && partials && sums, "overlap_loss_fwd: null pointer");
-    ISWM_REQUIRE(B > 0 && HW > 0, "overlap_loss_fwd: bad shape");
-    ISWM_REQUIRE(C >= 1 && C <= OVL_CMAX, "overlap_loss_fwd: %d classes (the overlap losses take 1 to %d)", C, OVL_CMAX);
-    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "overlap_loss_fwd: labels must be uint8 or int64");
+    if (refuse_pixel_args("overlap_loss_fwd", logits && labels && partials && sums,
+                          B > 0 && HW > 0, C, OVERLAP_TAKES, label_bytes)) return 1;
     const int64_t npix = (int64_t)B * HW;
     const int blocks = iswm_loss_blocks(npix);
     hipStream_t s = (hipStream_t)stream;
-#define OLAUNCH(T, CT)                                                                                                \
-    hipLaunchKernelGGL((k_overlap_sums<T, CT>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C, HW, npix, \
-                       class_weight, ignore_index, partials, blocks)
-    if (label_bytes == 1) {
-        if (C == 2) OLAUNCH(uint8_t, 2);
-        else OLAUNCH(uint8_t, 0);
-    } else {
-        if (C == 2) OLAUNCH(int64_t, 2);
-        else OLAUNCH(int64_t, 0);
-    }
-#undef OLAUNCH
+    by_label_and_classes(label_bytes, C, [&](auto label, auto ct) {
+        using T = decltype(label);
+        hipLaunchKernelGGL((k_overlap_sums<T, decltype(ct)::value>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C,
+                           HW, npix, class_weight, ignore_index, partials, blocks);
+    });
     hipLaunchKernelGGL(k_overlap_finalize, dim3(2 + 3 * C), dim3(64), 0, s, partials, blocks, sums);
     return check_launch("overlap_loss_fwd");
 }
@@ -819,47 +793,31 @@ extern "C" int iswm_overlap_loss_coeffs(const double* sums, int C, double ce_wei
 extern "C" int iswm_overlap_loss_bwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
                                      const float* class_weight, int ignore_index, const float* coef, const float* upstream,
                                      float* grad, iswm_stream_t stream) {
-    ISWM_REQUIRE(logits && labels && coef && upstream && grad, "overlap_loss_bwd: null pointer");
-    ISWM_REQUIRE(B > 0 && HW > 0, "overlap_loss_bwd: bad shape");
-    ISWM_REQUIRE(C >= 1 && C <= OVL_CMAX, "overlap_loss_bwd: %d classes (the overlap losses take 1 to %d)", C, OVL_CMAX);
-    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "overlap_loss_bwd: labels must be uint8 or int64");
+    if (refuse_pixel_args("overlap_loss_bwd", logits && labels && coef && upstream && grad,
+                          B > 0 && HW > 0, C, OVERLAP_TAKES, label_bytes)) return 1;
     const int64_t npix = (int64_t)B * HW;
     const int blocks = iswm_loss_blocks(npix);
     hipStream_t s = (hipStream_t)stream;
-#define OLAUNCH(T, CT)                                                                                               \
-    hipLaunchKernelGGL((k_overlap_bwd<T, CT>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C, HW, npix, \
-                       class_weight, ignore_index, coef, upstream, grad)
-    if (label_bytes == 1) {
-        if (C == 2) OLAUNCH(uint8_t, 2);
-        else OLAUNCH(uint8_t, 0);
-    } else {
-        if (C == 2) OLAUNCH(int64_t, 2);
-        else OLAUNCH(int64_t, 0);
-    }
-#undef OLAUNCH
+    by_label_and_classes(label_bytes, C, [&](auto label, auto ct) {
+        using T = decltype(label);
+        hipLaunchKernelGGL((k_overlap_bwd<T, decltype(ct)::value>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C,
+                           HW, npix, class_weight, ignore_index, coef, upstream, grad);
+    });
     return check_launch("overlap_loss_bwd");
 }
 
 extern "C" int iswm_ohem_keys(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
                               int ignore_index, int32_t* keys, int32_t* counts, int64_t* nvalid, iswm_stream_t stream) {
-    ISWM_REQUIRE(logits && labels && keys && counts && nvalid, "ohem_keys: null pointer");
-    ISWM_REQUIRE(B > 0 && HW > 0, "ohem_keys: bad shape");
-    ISWM_REQUIRE(C >= 1 && C <= OVL_CMAX, "ohem_keys: %d classes (hard-pixel mining takes 1 to %d)", C, OVL_CMAX);
-    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "ohem_keys: labels must be uint8 or int64");
+    if (refuse_pixel_args("ohem_keys", logits && labels && keys && counts && nvalid,
+                          B > 0 && HW > 0, C, OHEM_TAKES, label_bytes)) return 1;
     const int64_t npix = (int64_t)B * HW;
     const int blocks = iswm_loss_blocks(npix);
     hipStream_t s = (hipStream_t)stream;
-#define KLAUNCH(T, CT)                                                                                             \
-    hipLaunchKernelGGL((k_ohem_keys<T, CT>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C, HW, npix, \
-                       ignore_index, keys, counts)
-    if (label_bytes == 1) {
-        if (C == 2) KLAUNCH(uint8_t, 2);
-        else KLAUNCH(uint8_t, 0);
-    } else {
-        if (C == 2) KLAUNCH(int64_t, 2);
-        else KLAUNCH(int64_t, 0);
-    }
-#undef KLAUNCH
+    by_label_and_classes(label_bytes, C, [&](auto label, auto ct) {
+        using T = decltype(label);
+        hipLaunchKernelGGL((k_ohem_keys<T, decltype(ct)::value>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C,
+                           HW, npix, ignore_index, keys, counts);
+    });
     hipLaunchKernelGGL(k_ohem_count, dim3(1), dim3(256), 0, s, counts, blocks, (unsigned long long*)nvalid);
     return check_launch("ohem_keys");
 }
@@ -892,10 +850,8 @@ extern "C" int iswm_ohem_scan(const int64_t* hist, const int64_t* nvalid, int di
 extern "C" int iswm_ohem_sums(const int32_t* keys, const void* labels, int label_bytes, int64_t npix, int C,
                               const float* class_weight, const float* nu, float* partials, double* sums,
                               iswm_stream_t stream) {
-    ISWM_REQUIRE(keys && labels && nu && partials && sums, "ohem_sums: null pointer");
-    ISWM_REQUIRE(npix > 0 && npix <= ((int64_t)1 << 36), "ohem_sums: bad pixel count");
-    ISWM_REQUIRE(C >= 1 && C <= OVL_CMAX, "ohem_sums: %d classes (hard-pixel mining takes 1 to %d)", C, OVL_CMAX);
-    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "ohem_sums: labels must be uint8 or int64");
+    if (refuse_pixel_args("ohem_sums", keys && labels && nu && partials && sums,
+                          npix > 0 && npix <= ((int64_t)1 << 36), C, OHEM_TAKES, label_bytes)) return 1;
     const int blocks = iswm_loss_blocks(npix);
     hipStream_t s = (hipStream_t)stream;
     if (label_bytes == 1)
@@ -917,23 +873,15 @@ extern "C" int iswm_ohem_loss(const double* sums, float* out, iswm_stream_t stre
 extern "C" int iswm_ohem_bwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
                              const float* class_weight, const int32_t* keys, const float* nu, const float* lossinv,
                              const float* upstream, float* grad, iswm_stream_t stream) {
-    ISWM_REQUIRE(logits && labels && keys && nu && lossinv && upstream && grad, "ohem_bwd: null pointer");
-    ISWM_REQUIRE(B > 0 && HW > 0, "ohem_bwd: bad shape");
-    ISWM_REQUIRE(C >= 1 && C <= OVL_CMAX, "ohem_bwd: %d classes (hard-pixel mining takes 1 to %d)", C, OVL_CMAX);
-    ISWM_REQUIRE(label_bytes == 1 || label_bytes == 8, "ohem_bwd: labels must be uint8 or int64");
+    if (refuse_pixel_args("ohem_bwd", logits && labels && keys && nu && lossinv && upstream && grad,
+                          B > 0 && HW > 0, C, OHEM_TAKES, label_bytes)) return 1;
     const int64_t npix = (int64_t)B * HW;
     const int blocks = iswm_loss_blocks(npix);
     hipStream_t s = (hipStream_t)stream;
-#define BLAUNCH(T, CT)                                                                                            \
-    hipLaunchKernelGGL((k_ohem_bwd<T, CT>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C, HW, npix, \
-                       class_weight, keys, (const int*)nu, lossinv, upstream, grad)
-    if (label_bytes == 1) {
-        if (C == 2) BLAUNCH(uint8_t, 2);
-        else BLAUNCH(uint8_t, 0);
-    } else {
-        if (C == 2) BLAUNCH(int64_t, 2);
-        else BLAUNCH(int64_t, 0);
-    }
-#undef BLAUNCH
+    by_label_and_classes(label_bytes, C, [&](auto label, auto ct) {
+        using T = decltype(label);
+        hipLaunchKernelGGL((k_ohem_bwd<T, decltype(ct)::value>), dim3(blocks), dim3(256), 0, s, logits, (const T*)labels, C,
+                           HW, npix, class_weight, keys, (const int*)nu, lossinv, upstream, grad);
+    });
     return check_launch("ohem_bwd");
 }

@@ -1026,13 +1026,14 @@ def loss_bwd_scale(grad, sums, upstream, mode, npix):
 OVERLAP_CLASSES = {"foreground": 0, "all": 1}
 
 
-def _overlap_args(logits, labels, weight):
+def _pixel_loss_args(logits, labels, weight, noun):
+    """the checks the two-pass criteria share (`noun` names the criterion in the messages) -> logits, labels, B, C, H * W"""
     if not (logits.dim() == 4 and logits.dtype == torch.float32 and logits.is_cuda):
-        raise ValueError("the overlap loss expects fp32 CUDA logits [B,C,H,W] (there is no CPU fallback)")
+        raise ValueError("%s expects fp32 CUDA logits [B,C,H,W] (there is no CPU fallback)" % noun)
     logits = logits.contiguous()
     b, c, h, w = logits.shape
     if c > 8:
-        raise ValueError("the overlap losses take at most 8 classes (got %d)" % c)
+        raise ValueError("%s takes at most 8 classes (got %d)" % (noun, c))
     assert labels.shape == (b, h, w) and labels.dtype in (torch.uint8, torch.int64)
     assert weight is None or (weight.dtype == torch.float32 and weight.numel() == c and weight.is_cuda)
     return logits, labels.contiguous(), b, c, h * w
@@ -1041,7 +1042,7 @@ def _overlap_args(logits, labels, weight):
 def overlap_loss_fwd(logits, labels, weight, ignore_index):
     """One pass over the logits, nothing stored per pixel -> sums (float64 [2 + 3C], on the device) =
     {sum w*nll, sum w, I_c [C], P_c [C], G_c [C]} over the valid pixels (include/iswm_hip.h)."""
-    logits, labels, b, c, hw = _overlap_args(logits, labels, weight)
+    logits, labels, b, c, hw = _pixel_loss_args(logits, labels, weight, "the overlap loss")
     blocks = _lib.load().iswm_loss_blocks(b * hw)
     nv = 2 + 3 * c
     partials = torch.empty((nv, blocks), dtype=torch.float32, device=logits.device)
@@ -1064,25 +1065,13 @@ def overlap_loss_coeffs(sums, C, ce_weight, overlap_weight, alpha, beta, gamma, 
 
 def overlap_loss_bwd(logits, labels, weight, ignore_index, coef, upstream):
     """The second pass: upstream[0] * dL/dlogits, written once (upstream: fp32 device scalar [1])."""
-    logits, labels, b, c, hw = _overlap_args(logits, labels, weight)
+    logits, labels, b, c, hw = _pixel_loss_args(logits, labels, weight, "the overlap loss")
     assert coef.dtype == torch.float32 and coef.numel() == 1 + 2 * c and coef.is_cuda
     assert upstream.dtype == torch.float32 and upstream.numel() == 1 and upstream.is_cuda
     grad = torch.empty_like(logits)
     call("iswm_overlap_loss_bwd", _p(logits), _p(labels), labels.element_size(), b, c, hw, _p(weight), int(ignore_index),
          _p(coef), _p(upstream), _p(grad), _stream())
     return grad
-
-
-def _ohem_args(logits, labels, weight):
-    if not (logits.dim() == 4 and logits.dtype == torch.float32 and logits.is_cuda):
-        raise ValueError("hard-pixel mining expects fp32 CUDA logits [B,C,H,W] (there is no CPU fallback)")
-    logits = logits.contiguous()
-    b, c, h, w = logits.shape
-    if c > 8:
-        raise ValueError("hard-pixel mining takes at most 8 classes (got %d)" % c)
-    assert labels.shape == (b, h, w) and labels.dtype in (torch.uint8, torch.int64)
-    assert weight is None or (weight.dtype == torch.float32 and weight.numel() == c and weight.is_cuda)
-    return logits, labels.contiguous(), b, c, h * w
 
 
 def ohem_nu0(thresh):
@@ -1094,7 +1083,7 @@ def ohem_nu0(thresh):
 
 def ohem_keys(logits, labels, ignore_index):
     """-> (keys int32 [B,H,W]: the bit pattern of the pixel's nll, -1 at an invalid pixel; nvalid int64 [1] = |V|), on the device"""
-    logits, labels, b, c, hw = _ohem_args(logits, labels, None)
+    logits, labels, b, c, hw = _pixel_loss_args(logits, labels, None, "hard-pixel mining")
     keys = torch.empty(labels.shape, dtype=torch.int32, device=logits.device)
     nvalid = torch.empty((1,), dtype=torch.int64, device=logits.device)
     counts = torch.empty((_lib.load().iswm_loss_blocks(b * hw),), dtype=torch.int32, device=logits.device)
@@ -1175,7 +1164,7 @@ def ohem_loss(sums):
 
 def ohem_bwd(logits, labels, weight, keys, nu, lossinv, upstream):
     """upstream[0] * dL/dlogits, written once: w (p - onehot) / sum_K w on the kept pixels, exactly 0 elsewhere"""
-    logits, labels, b, c, hw = _ohem_args(logits, labels, weight)
+    logits, labels, b, c, hw = _pixel_loss_args(logits, labels, weight, "hard-pixel mining")
     assert keys.dtype == torch.int32 and keys.is_cuda and keys.is_contiguous() and keys.shape == labels.shape
     assert nu.dtype == torch.float32 and nu.numel() == 1 and lossinv.dtype == torch.float32 and lossinv.numel() == 2
     assert upstream.dtype == torch.float32 and upstream.numel() == 1 and upstream.is_cuda

@@ -17,6 +17,16 @@ import torch.nn as nn
 from .. import ops
 
 
+def _scalar(upstream):
+    """the upstream gradient as the fp32 device scalar [1] the backward kernels read"""
+    return upstream.reshape(1).contiguous().to(torch.float32)
+
+
+def _weight_for(weight, inputs):
+    """a module's class weights as fp32 on the input's device (None without weights)"""
+    return None if weight is None else weight.to(device=inputs.device, dtype=torch.float32)
+
+
 class _LossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, weight, ignore_index, alpha, gamma, mode, group):
@@ -40,8 +50,7 @@ class _LossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, upstream):
         grad, sums = ctx.saved_tensors
-        up = upstream.reshape(1).contiguous().to(torch.float32)
-        ops.loss_bwd_scale(grad, sums, up, ctx.mode, ctx.npix)
+        ops.loss_bwd_scale(grad, sums, _scalar(upstream), ctx.mode, ctx.npix)
         return grad, None, None, None, None, None, None, None
 
 
@@ -67,7 +76,7 @@ class CrossEntropyLoss(nn.Module):
 
     def forward(self, inputs, targets):
         targets = _check(inputs, targets)
-        w = None if self.weight is None else self.weight.to(inputs.device)
+        w = _weight_for(self.weight, inputs)
         return _LossFn.apply(inputs, targets, w, self.ignore_index, 1.0, 0.0, ops.MODE_WCE, self.group)
 
 
@@ -86,7 +95,7 @@ class FocalLoss(nn.Module):
 
     def forward(self, inputs, targets):
         targets = _check(inputs, targets)
-        w = None if self.weight is None else self.weight.to(device=inputs.device, dtype=torch.float32)
+        w = _weight_for(self.weight, inputs)
         mode = ops.MODE_FOCAL_MEAN if self.size_average else ops.MODE_FOCAL_SUM
         return _LossFn.apply(inputs, targets, w, self.ignore_index, float(self.alpha), float(self.gamma), mode,
                              self.group)
@@ -112,8 +121,7 @@ class _OverlapLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, upstream):
         logits, labels, weight, coef = ctx.saved_tensors
-        up = upstream.reshape(1).contiguous().to(torch.float32)
-        grad = ops.overlap_loss_bwd(logits, labels, weight, ctx.ignore_index, coef, up)
+        grad = ops.overlap_loss_bwd(logits, labels, weight, ctx.ignore_index, coef, _scalar(upstream))
         return grad, None, None, None, None, None
 
 
@@ -141,7 +149,7 @@ class TverskyLoss(nn.Module):
 
     def forward(self, inputs, targets):
         targets = _check(inputs, targets)
-        w = None if self.weight is None else self.weight.to(inputs.device)
+        w = _weight_for(self.weight, inputs)
         return _OverlapLossFn.apply(inputs, targets, w, self.ignore_index, self.params, self.group)
 
 
@@ -177,8 +185,7 @@ class _OhemLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, upstream, _sums, _nu):
         logits, labels, weight, keys, nu, out = ctx.saved_tensors
-        up = upstream.reshape(1).contiguous().to(torch.float32)
-        grad = ops.ohem_bwd(logits, labels, weight, keys, nu, out, up)
+        grad = ops.ohem_bwd(logits, labels, weight, keys, nu, out, _scalar(upstream))
         return grad, None, None, None, None, None, None
 
 
@@ -205,7 +212,7 @@ class OhemCrossEntropyLoss(nn.Module):
 
     def forward(self, inputs, targets):
         targets = _check(inputs, targets)
-        w = None if self.weight is None else self.weight.to(inputs.device)
+        w = _weight_for(self.weight, inputs)
         loss, sums, nu = _OhemLossFn.apply(inputs, targets, w, self.ignore_index, self.thresh, self.min_kept, self.group)
         self.last_kept, self.last_nu = sums[2], nu[0]
         return loss
