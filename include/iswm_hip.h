@@ -448,6 +448,38 @@ int iswm_ohem_loss(const double* sums, float* out, iswm_stream_t stream);
 int iswm_ohem_bwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
                   const float* class_weight, const int32_t* keys, const float* nu, const float* lossinv,
                   const float* upstream, float* grad, iswm_stream_t stream);
+/* ---- Lovasz-Softmax, per image, + weighted CE (lovasz.hip) ------------------------------------
+ * Segment (b, c) = image b, class c of S (classes 0: c >= 1; classes 1: every c), nseg = B * |S| segments of P = HW pixels,
+ * segment index b * |S| + (c - first).  Over the valid pixels of image b: e = |[y == c] - softmax_c| in [0, 1],
+ * sorted descending (ties: g = 1 first, then ascending pixel index); omega_j = the Jaccard increment at position j in
+ * closed form;  L = ce_weight * sum(w nll) / sum(w) + lovasz_weight * (sum over segments with G > 0 of sum_j e_j omega_j) / N.
+ * 1 <= C <= 8, 1 <= P <= 2^24, nseg <= 65535, nseg * P < 2^31; anything else is refused with a message.
+ * keys: keys [nseg, P] = ((bits(e) << 1) | g) + 1, 0 at an invalid pixel; counts [nseg, 2] (int32) = {valid pixels of
+ *   the image, G}; partials [2 * iswm_loss_blocks(B * HW)] is a workspace; sums[0..1] (double) = {sum w nll, sum w},
+ *   iswm_loss_fwd's mode-0 sums bit for bit once rounded to float.
+ * sort: stable descending LSD radix sort of nseg segments of P uint32 keys, iswm_lovasz_digits() digits of 8 bits over
+ *   tiles of iswm_lovasz_tile() keys -> sorted [nseg, P], perm [nseg, P] (the key's index in its segment).
+ *   workspace: iswm_lovasz_workspace(nseg, P) bytes (0 and a message for sizes the sort does not take).
+ * weights: sorted, perm, counts -> m [nseg, P]: m[seg, perm[j]] = omega_j, 0 at invalid pixels and where G = 0;
+ *   out[0..1] (double) = {sum over present segments of L_bc, N}.  Same workspace.
+ * loss: sums[4] = {sum w nll, sum w, sum L_bc, N} (this process's or all-reduced) -> out[3] = {loss, ce_weight / sum w,
+ *   lovasz_weight / N}; a term whose normaliser is 0 is 0 and so is its coefficient.
+ * bwd: logits, labels, m, coef = out + 1 -> upstream[0] * dL/dlogits written once, exactly 0 at invalid pixels.
+ * Every result is bit-reproducible: integer counts and ranks, fixed-order sums, no float atomics. */
+int iswm_lovasz_digits(void);
+int iswm_lovasz_tile(void);
+int64_t iswm_lovasz_workspace(int64_t nseg, int64_t P);
+int iswm_lovasz_keys(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
+                     const float* class_weight, int ignore_index, int classes, uint32_t* keys, int32_t* counts,
+                     float* partials, double* sums, iswm_stream_t stream);
+int iswm_lovasz_sort(const uint32_t* keys, int64_t nseg, int64_t P, void* workspace, int64_t workspace_bytes,
+                     uint32_t* sorted, uint32_t* perm, iswm_stream_t stream);
+int iswm_lovasz_weights(const uint32_t* sorted, const uint32_t* perm, const int32_t* counts, int64_t nseg, int64_t P,
+                        void* workspace, int64_t workspace_bytes, float* m, double* out, iswm_stream_t stream);
+int iswm_lovasz_loss(const double* sums, double ce_weight, double lovasz_weight, float* out, iswm_stream_t stream);
+int iswm_lovasz_bwd(const float* logits, const void* labels, int label_bytes, int B, int C, int64_t HW,
+                    const float* class_weight, int ignore_index, int classes, const float* m, const float* coef,
+                    const float* upstream, float* grad, iswm_stream_t stream);
 /* logits.max(1)[1], train.py:644,659 -- ties resolve to the lowest class index */
 int iswm_argmax_nchw(const float* logits, int B, int C, int64_t HW, int64_t* out, iswm_stream_t stream);
 

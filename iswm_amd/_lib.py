@@ -162,6 +162,14 @@ _SIGS = {
     "iswm_ohem_sums": (c_int, [P, P, c_int, c_int64, c_int, P, P, P, P, P]),
     "iswm_ohem_loss": (c_int, [P, P, P]),
     "iswm_ohem_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, P, P, P, P, P, P]),
+    "iswm_lovasz_digits": (c_int, []),
+    "iswm_lovasz_tile": (c_int, []),
+    "iswm_lovasz_workspace": (c_int64, [c_int64, c_int64]),
+    "iswm_lovasz_keys": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, c_int, P, P, P, P, P]),
+    "iswm_lovasz_sort": (c_int, [P, c_int64, c_int64, P, c_int64, P, P, P]),
+    "iswm_lovasz_weights": (c_int, [P, P, P, c_int64, c_int64, P, c_int64, P, P, P]),
+    "iswm_lovasz_loss": (c_int, [P, c_double, c_double, P, P]),
+    "iswm_lovasz_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, c_int, P, P, P, P, P]),
     "iswm_argmax_nchw": (c_int, [P, c_int, c_int, c_int64, P, P]),
     "iswm_augment_batch": (c_int, [P, P, P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P, P]),
     "iswm_aug_rotate": (c_int, [P, P, P, P, c_int, c_int64, P, c_size_t, P, c_size_t, P]),

@@ -1174,6 +1174,93 @@ def ohem_bwd(logits, labels, weight, keys, nu, lossinv, upstream):
     return grad
 
 
+_LOVASZ_WS = {}
+
+
+def lovasz_segments(b, c, classes):
+    """the number of (image, class) segments of a [b, c, ...] batch: every class but 0 ('foreground') or all"""
+    if classes not in OVERLAP_CLASSES:
+        raise ValueError("classes is 'foreground' or 'all' (got %r)" % (classes,))
+    return b * (c - (0 if classes == "all" else 1))
+
+
+def lovasz_workspace(device, nseg, P):
+    """the sort's ping-pong buffers and tables (uint8 on `device`), cached per (device, nseg, P): one criterion call after
+    another on one stream reuses it"""
+    key = (str(device), int(nseg), int(P))
+    ws = _LOVASZ_WS.get(key)
+    if ws is None:
+        need = _lib.load().iswm_lovasz_workspace(int(nseg), int(P))
+        if need <= 0:
+            raise _lib.IswmError(_lib.load().iswm_last_error().decode())
+        ws = _LOVASZ_WS[key] = torch.empty((need,), dtype=torch.uint8, device=device)
+    return ws
+
+
+def lovasz_keys(logits, labels, weight, ignore_index, classes, sums=None):
+    """-> (keys int32 [nseg, HW]: the bits of ((bits(e) << 1) | g) + 1, 0 at an invalid pixel; counts int32 [nseg, 2] = {valid
+    pixels of the image, G}; sums float64 [4] whose first two entries are {sum w nll, sum w}) on the device.  The keys are
+    uint32 values held in int32 tensors."""
+    logits, labels, b, c, hw = _pixel_loss_args(logits, labels, weight, "the Lovasz loss")
+    nseg = lovasz_segments(b, c, classes)
+    keys = torch.empty((max(nseg, 0), hw), dtype=torch.int32, device=logits.device)
+    counts = torch.empty((max(nseg, 0), 2), dtype=torch.int32, device=logits.device)
+    partials = torch.empty((2, _lib.load().iswm_loss_blocks(b * hw)), dtype=torch.float32, device=logits.device)
+    if sums is None:
+        sums = torch.zeros((4,), dtype=torch.float64, device=logits.device)
+    call("iswm_lovasz_keys", _p(logits), _p(labels), labels.element_size(), b, c, hw, _p(weight), int(ignore_index),
+         OVERLAP_CLASSES[classes], _p(keys), _p(counts), _p(partials), _p(sums), _stream())
+    return keys, counts, sums
+
+
+def lovasz_sort(keys):
+    """keys int32 [nseg, P] (uint32 values) -> (sorted [nseg, P], perm [nseg, P]): every segment in descending order of the
+    unsigned keys, equal keys in input order; perm is the key's index in its segment"""
+    assert keys.dtype == torch.int32 and keys.is_cuda and keys.is_contiguous() and keys.dim() == 2
+    nseg, P = keys.shape
+    ws = lovasz_workspace(keys.device, nseg, P)
+    out = torch.empty((2, nseg, P), dtype=torch.int32, device=keys.device)
+    call("iswm_lovasz_sort", _p(keys), nseg, P, _p(ws), ws.numel(), _p(out[0]), _p(out[1]), _stream())
+    return out[0], out[1]
+
+
+def lovasz_weights(sorted_keys, perm, counts, sums=None):
+    """-> (m fp32 [nseg, P]: m[seg, perm[j]] = omega_j, 0 at invalid pixels and in absent segments; sums float64 [4] whose last
+    two entries are {sum over present segments of L_bc, N})"""
+    assert sorted_keys.dtype == torch.int32 and sorted_keys.is_cuda and sorted_keys.is_contiguous() and sorted_keys.dim() == 2
+    nseg, P = sorted_keys.shape
+    assert perm.dtype == torch.int32 and perm.shape == sorted_keys.shape and perm.is_contiguous() and perm.is_cuda
+    assert counts.dtype == torch.int32 and counts.shape == (nseg, 2) and counts.is_contiguous() and counts.is_cuda
+    ws = lovasz_workspace(sorted_keys.device, nseg, P)
+    m = torch.empty((nseg, P), dtype=torch.float32, device=sorted_keys.device)
+    if sums is None:
+        sums = torch.zeros((4,), dtype=torch.float64, device=sorted_keys.device)
+    assert sums.dtype == torch.float64 and sums.numel() == 4 and sums.is_contiguous() and sums.is_cuda
+    call("iswm_lovasz_weights", _p(sorted_keys), _p(perm), _p(counts), nseg, P, _p(ws), ws.numel(), _p(m), _p(sums[2:]), _stream())
+    return m, sums
+
+
+def lovasz_loss(sums, ce_weight, lovasz_weight):
+    """sums (this process's, or all-reduced) -> fp32 [3] on the device: {loss, ce_weight / sum w, lovasz_weight / N}"""
+    assert sums.dtype == torch.float64 and sums.numel() == 4 and sums.is_cuda and sums.is_contiguous()
+    out = torch.empty((3,), dtype=torch.float32, device=sums.device)
+    call("iswm_lovasz_loss", _p(sums), float(ce_weight), float(lovasz_weight), _p(out), _stream())
+    return out
+
+
+def lovasz_bwd(logits, labels, weight, ignore_index, classes, m, out, upstream):
+    """upstream[0] * dL/dlogits, written once, CE term included (out: lovasz_loss's result); exactly 0 at invalid pixels"""
+    logits, labels, b, c, hw = _pixel_loss_args(logits, labels, weight, "the Lovasz loss")
+    nseg = lovasz_segments(b, c, classes)
+    assert m.dtype == torch.float32 and m.shape == (nseg, hw) and m.is_contiguous() and m.is_cuda
+    assert out.dtype == torch.float32 and out.numel() == 3 and out.is_cuda and out.is_contiguous()
+    assert upstream.dtype == torch.float32 and upstream.numel() == 1 and upstream.is_cuda
+    grad = torch.empty_like(logits)
+    call("iswm_lovasz_bwd", _p(logits), _p(labels), labels.element_size(), b, c, hw, _p(weight), int(ignore_index),
+         OVERLAP_CLASSES[classes], _p(m), _p(out[1:]), _p(upstream), _p(grad), _stream())
+    return grad
+
+
 def argmax_nchw(logits):
     logits = logits.contiguous()
     b, c, h, w = logits.shape

@@ -27,7 +27,9 @@ forced by the reference not being runnable as shipped:
     section 18).  With EMA on, validation, best-model selection and the validation images use the EMA weights, the
     checkpoint gains ``"ema_state"`` (``"model_state"`` stays the live weights) and ``--test_only --use_ema`` scores it;
   * ``--ohem_thresh P`` (off by default) averages the CE over the hard pixels only: those predicted below P and at least
-    ``--ohem_min_kept`` per process, selected on the device.
+    ``--ohem_min_kept`` per process, selected on the device (DESIGN.md section 19);
+  * ``--lovasz_weight W`` (off by default) adds W x the per-image Lovasz-Softmax term to ``--ce_weight`` x the CE, on a
+    segmented radix sort on the device.
 """
 import argparse
 import contextlib
@@ -45,8 +47,8 @@ from torch.utils import data
 from . import network, ops
 from .optim import FusedAdam, FusedAdamW, FusedSGD, ema_model_state
 from .parallel import DistributedDataParallelHIP
-from .utils.loss import (CrossEntropyLoss, DiceLoss, OhemCrossEntropyLoss, TverskyLoss, calculate_class_weights,
-                         calculate_class_weights_resident)
+from .utils.loss import (CrossEntropyLoss, DiceLoss, LovaszSoftmaxLoss, OhemCrossEntropyLoss, TverskyLoss,
+                         calculate_class_weights, calculate_class_weights_resident)
 from .val_results import save_validation_results
 
 
@@ -55,8 +57,14 @@ class _ArgParser(argparse.ArgumentParser):
 
     def parse_known_args(self, args=None, namespace=None):
         opts, rest = super().parse_known_args(args, namespace)
-        if opts.overlap_loss == 'none' and opts.ce_weight == 0:
+        if not (math.isfinite(opts.lovasz_weight) and opts.lovasz_weight >= 0):
+            self.error("--lovasz_weight must be finite and not negative (0 = off)")
+        if opts.overlap_loss == 'none' and opts.lovasz_weight == 0 and opts.ce_weight == 0:
             self.error("--ce_weight 0 with --overlap_loss none leaves no loss term")
+        if opts.lovasz_weight > 0 and opts.overlap_loss != 'none':
+            self.error("--lovasz_weight with --overlap_loss %s: one region term at a time" % opts.overlap_loss)
+        if opts.lovasz_weight > 0 and opts.ohem_thresh > 0:
+            self.error("--lovasz_weight with --ohem_thresh: hard-pixel mining inside the combined criterion is not supported")
         if opts.ce_weight < 0 or opts.overlap_weight < 0:
             self.error("--ce_weight and --overlap_weight must not be negative")
         if not opts.overlap_smooth > 0:
@@ -150,6 +158,9 @@ def get_argparser():
     parser.add_argument("--overlap_smooth", type=float, default=1.0, help="smoothing constant of the overlap term (> 0)")
     parser.add_argument("--overlap_classes", type=str, default='foreground', choices=['foreground', 'all'],
                         help="classes the overlap term averages over: every class but 0, or all")
+    parser.add_argument("--lovasz_weight", type=float, default=0.0, metavar="W",
+                        help="add W x the per-image Lovasz-Softmax term (the Jaccard loss's convex extension, sorted on the "
+                             "device) to --ce_weight x the CE; --overlap_classes selects its classes; 0 = off")
     parser.add_argument("--ohem_thresh", type=float, default=0.0, metavar="P",
                         help="online hard-example mining: average the CE over the pixels whose true-class probability is at "
                              "most P, and over at least the --ohem_min_kept hardest ones; --loss_type still selects the class "
@@ -284,6 +295,9 @@ def setup_criterion(opts, class_weights, group=None):
             return DiceLoss(**common)
         return TverskyLoss(alpha=opts.tversky_alpha, beta=opts.tversky_beta,
                            gamma=opts.tversky_gamma if kind == 'focal_tversky' else 1.0, **common)
+    if getattr(opts, 'lovasz_weight', 0.0) > 0:
+        return LovaszSoftmaxLoss(classes=opts.overlap_classes, ce_weight=opts.ce_weight, lovasz_weight=opts.lovasz_weight,
+                                 weight=weight, ignore_index=255, group=group)
     if getattr(opts, 'ohem_thresh', 0.0) > 0:
         world = dist.get_world_size(group) if group is not None else 1      # --ohem_min_kept is per process, like --batch_size
         return OhemCrossEntropyLoss(thresh=opts.ohem_thresh, min_kept=opts.ohem_min_kept * world, weight=weight,
@@ -592,6 +606,7 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
     ema_weights = optimizer.ema_weights if optimizer.ema_enabled else contextlib.nullcontext
     clipping = bool(getattr(opts, "clip_grad_norm", 0.0))
     mining = isinstance(criterion, OhemCrossEntropyLoss)
+    lovasz = isinstance(criterion, LovaszSoftmaxLoss)
 
     sequence_val = opts.val_metrics == 'sequence'
     if sequence_val:
@@ -636,6 +651,8 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
                 if mining:                                      # the last step's kept pixels of the global batch: one read-back
                     kept = int(criterion.last_kept)
                     norm += ", kept=%d (%.2f%%)" % (kept, 100.0 * kept / (labels.numel() * world))
+                if lovasz:                                      # the last step's (image, class) pairs of the global batch: one read-back
+                    norm += ", present=%d" % int(criterion.last_present)
                 print("Epoch %d, Itrs %d/%d, Loss=%.6f, lr=%.3e, %.1f img/s%s" %
                       (cur_epochs, cur_itrs, opts.total_itrs, avg, optimizer.param_groups[0]['lr'], n_last / dt, norm))
                 interval_loss.zero_()

@@ -218,6 +218,68 @@ class OhemCrossEntropyLoss(nn.Module):
         return loss
 
 
+class _LovaszLossFn(torch.autograd.Function):
+    """ce_weight * weighted CE + lovasz_weight * per-image Lovasz-Softmax (csrc/lovasz.hip): keys, a stable segmented radix
+    sort on the device, the Jaccard weights of every pixel; the backward pass reads the logits again and writes the finished
+    gradient once.  Nothing is read back.  With `group` the four sums {sum w nll, sum w, sum L_bc, N} are all-reduced between
+    the kernel that writes them and the one that reads them: the order statistic is per image, so no sort crosses a rank, and
+    the SUM gradient all-reduce of parallel.py yields the gradient of the global loss."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, ignore_index, classes, ce_weight, lovasz_weight, group):
+        keys, counts, sums = ops.lovasz_keys(logits, labels, weight, ignore_index, classes)
+        sorted_keys, perm = ops.lovasz_sort(keys)
+        m, sums = ops.lovasz_weights(sorted_keys, perm, counts, sums)
+        if group is not None:
+            import torch.distributed as dist
+            dist.all_reduce(sums, group=group)
+        out = ops.lovasz_loss(sums, ce_weight, lovasz_weight)
+        ctx.save_for_backward(logits, labels, weight, m, out)
+        ctx.ignore_index, ctx.classes = ignore_index, classes
+        ctx.mark_non_differentiable(sums)
+        return out[0].clone(), sums
+
+    @staticmethod
+    def backward(ctx, upstream, _sums):
+        logits, labels, weight, m, out = ctx.saved_tensors
+        grad = ops.lovasz_bwd(logits, labels, weight, ctx.ignore_index, ctx.classes, m, out, _scalar(upstream))
+        return grad, None, None, None, None, None, None, None
+
+
+class LovaszSoftmaxLoss(nn.Module):
+    """ce_weight * CrossEntropyLoss(weight, ignore_index) + lovasz_weight * Lovasz-Softmax (Berman et al. 2018), per image:
+    for every image and class of `classes` ('foreground': every class but 0, or 'all') that occurs in the image, the errors
+    |[y == c] - softmax_c| of the image's valid pixels, sorted descending, weighted by the increments of the Jaccard loss;
+    averaged over those (image, class) pairs -- of all ranks together under `group`.  Absent classes are not counted; with
+    none present the term is 0.  At most 8 classes.
+
+    `last_present` is a 0-dim device view of the number of (image, class) pairs of the last call; reading it synchronises."""
+
+    def __init__(self, classes='foreground', ce_weight=0.0, lovasz_weight=1.0, weight=None, ignore_index=255, group=None):
+        super().__init__()
+        if classes not in ops.OVERLAP_CLASSES:
+            raise ValueError("classes is 'foreground' or 'all' (got %r)" % (classes,))
+        if not (0 <= ce_weight < math.inf and 0 <= lovasz_weight < math.inf):
+            raise ValueError("ce_weight and lovasz_weight must be finite and not negative")
+        if ce_weight == 0 and lovasz_weight == 0:
+            raise ValueError("ce_weight 0 with lovasz_weight 0 leaves no loss term")
+        self.register_buffer('weight', None if weight is None else weight.detach().float().clone())
+        self.classes, self.ce_weight, self.lovasz_weight = classes, float(ce_weight), float(lovasz_weight)
+        self.ignore_index = ignore_index
+        self.group = group
+        self.last_present = None
+
+    def forward(self, inputs, targets):
+        targets = _check(inputs, targets)
+        if self.classes == 'foreground' and inputs.shape[1] < 2:
+            raise ValueError("no foreground class among %d (empty class set)" % inputs.shape[1])
+        w = _weight_for(self.weight, inputs)
+        loss, sums = _LovaszLossFn.apply(inputs, targets, w, self.ignore_index, self.classes, self.ce_weight,
+                                         self.lovasz_weight, self.group)
+        self.last_present = sums[3]
+        return loss
+
+
 def create_loss(loss_type="focal", temporal_loss="none", temporal_weight=0.5, **kwargs):
     """reference utils/loss.py:37-39"""
     return FocalLoss(**kwargs)
