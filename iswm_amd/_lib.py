@@ -1,4 +1,18 @@
-"""ctypes binding of libiswm_hip.so (the C ABI declared in include/iswm_hip.h).
+"""ctypes binding of libiswm_hip.so, derived from include/iswm_hip.h at import.
+
+The header is the only declaration of the C ABI.  It is parsed once here -- `re` and `ctypes`, nothing generated, neither
+the library nor torch loaded -- into
+    CONSTANTS   every `#define ISWM_* <integer>` and `enum { NAME = <integer>, ... };`
+    STRUCTS     a ctypes.Structure per `typedef struct [tag] { ... } name;` (scalars, `T name[N]`, `int H, W;`, pointers)
+    _SIGS       (restype, argtypes) per prototype, in header order
+so an entry point needs its header line and its definition to be callable from Python.  The header keeps to that subset
+of C; a declaration outside it (an unknown type, a function pointer, a bit-field, a prototype that does not split)
+raises ValueError at import with the declaration in the message -- the parser never guesses.
+
+Types: the scalars of `_SCALARS`; `char*` -> c_char_p; a pointer to one of the header's records -> POINTER(record);
+every other pointer (`T**`, `T* const*`, `T name[]` included) -> c_void_p.  Host arrays (mean3 / std3, the ASPP ksize /
+dil lists, arrays of device pointers, `int*` outputs) are therefore c_void_p like device pointers: they take the ctypes
+arrays and byref() results the callers pass, and a bare integer passed there is no longer an ArgumentError.
 
 The product path has NO fallback: if the shared library is missing or a symbol
 cannot be resolved, importing the ops raises -- nothing silently routes through
@@ -6,28 +20,111 @@ torch ops or the CPU oracle.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
+import re
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libiswm_hip.so")
+HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip.h")
+
+# (`long long` is 8 bytes on every ABI the library is built for; tests/test_abi_cpu.py holds that)
+_SCALARS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "size_t": c_size_t, "float": c_float,
+            "double": c_double, "uint64_t": c_uint64}
+_POINTEES = {"void", "char", "unsigned char", "signed char", "uint8_t", "int32_t", "uint32_t"}    # pointed to, never by value
 
 
-class ConvDesc(Structure):
-    """iswm_conv_desc"""
-    _fields_ = [(n, c_int) for n in ("N", "H", "W", "Cin", "Ho", "Wo", "Cout", "KH", "KW", "stride", "pad",
-                                     "dil", "ldx", "ldy")]
+def parse_header(text):
+    """(CONSTANTS, STRUCTS, _SIGS) of a header written in the subset of C the module docstring names"""
+    constants, structs, sigs, scalars, known = {}, {}, {}, dict(_SCALARS), {}
+
+    def bad(why, decl):
+        return ValueError("iswm_hip.h: %s: %r" % (why, " ".join(decl.split())))
+
+    def integer(v, decl):
+        try:
+            return int(v, 0)
+        except ValueError:
+            raise bad("%r is not an integer" % v.strip(), decl)
+
+    def declarator(d, decl):
+        """(type text, name, array) of `T name`, `T name[]` (array "") or `T name[N]`; array None otherwise"""
+        m = re.fullmatch(r"([\w\s*]*[\s*])(\w+)\s*(?:\[\s*(\d*)\s*\])?", d.strip())
+        if not m:
+            raise bad("cannot read %r" % d.strip(), decl)
+        return m.groups()
+
+    def ctype(t, decl, array=None):
+        if (t, array) not in known:
+            known[t, array] = resolve(t, decl, array)
+        return known[t, array]
+
+    def resolve(t, decl, array):
+        m = re.fullmatch(r"(?:const\s+)?(\w+(?:\s+\w+)*?)(?:\s+const)?((?:\s*\*(?:\s*const)?)*)", t.strip())
+        if not m:
+            raise bad("cannot read the type %r" % t.strip(), decl)
+        base, stars = " ".join(m.group(1).split()), m.group(2).count("*")
+        if base not in scalars and base not in structs and base not in _POINTEES:
+            raise bad("unknown type %r" % base, decl)
+        if stars == 0 and base not in scalars:
+            raise bad("%r is only taken by pointer" % base, decl)
+        one = (scalars[base] if stars == 0 else c_char_p if (stars, base) == (1, "char") else
+               POINTER(structs[base]) if stars == 1 and base in structs else c_void_p)
+        if array == "":
+            raise bad("an array member needs a length", decl)
+        return one if array is None else one * int(array)
+
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    for line in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\S[^\n]*)", text, re.M):    # (the include guard has no value)
+        constants[line[0]] = integer(line[1], "#define %s %s" % line)
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    m = re.fullmatch(r'\s*extern\s+"C"\s*\{(.*)\}\s*', text, re.S)
+    body, one = m.group(1) if m else text, r"((?:[^;{}]|\{[^{}]*\})*);"          # up to the next `;` outside braces
+    if re.sub(one, "", body).strip():
+        raise bad("no `;` behind", re.sub(one, "", body))
+    for decl in (d.strip() for d in re.findall(one, body)):
+        m = re.fullmatch(r"enum\s*\{(.*)\}", decl, re.S)
+        if m:
+            for item in m.group(1).split(","):
+                name, eq, value = item.partition("=")
+                if not eq or not re.fullmatch(r"\s*\w+\s*", name):
+                    raise bad("an enumerator needs `NAME = <integer>`", decl)
+                constants[name.strip()] = integer(value, decl)
+            continue
+        m = re.fullmatch(r"typedef\s+struct(?:\s+\w+)?\s*\{(.*)\}\s*(\w+)", decl, re.S)
+        if m:
+            *members, rest = m.group(1).split(";")
+            if rest.strip():
+                raise bad("no `;` behind %r" % rest.strip(), decl)
+            fields = []
+            for first, *more in (member.split(",") for member in members):
+                t, name, array = declarator(first, decl)
+                if more and "*" in t:
+                    raise bad("a comma list of pointers", decl)
+                fields += [(name, ctype(t, decl, array))] + [(n, ctype(t, decl, a)) for _, n, a in
+                                                             (declarator(t + d, decl) for d in more)]
+            structs[m.group(2)] = type(m.group(2), (ctypes.Structure,), {"_fields_": fields})
+            continue
+        m = re.fullmatch(r"typedef\s+([\w\s*]*[\s*])(\w+)", decl)
+        if m:
+            scalars[m.group(2)] = ctype(m.group(1), decl)
+            continue
+        m = re.fullmatch(r"([\w\s*]*[\s*])(\w+)\s*\(([^()]*)\)", decl)
+        if not m:
+            raise bad("neither constants, a record nor a prototype `T name(T name, ...)`", decl)
+        args = [] if m.group(3).strip() in ("", "void") else [declarator(a, decl) for a in m.group(3).split(",")]
+        # (an array parameter `T name[]` is the pointer `T* name`)
+        sigs[m.group(2)] = (ctype(m.group(1), decl), [ctype(t if array is None else t + "*", decl) for t, _, array in args])
+    return constants, structs, sigs
 
 
-class QConvDesc(Structure):
-    """iswm_qconv_desc"""
-    _fields_ = [(n, c_int) for n in ("N", "H", "W", "Cin", "Ho", "Wo", "Cout", "KH", "KW", "stride", "pad",
-                                     "dil", "ldx", "ldy", "ldr", "relu", "lo", "out_f32", "cstore")]
+with open(HEADER) as _f:
+    CONSTANTS, STRUCTS, _SIGS = parse_header(_f.read())
+ConvDesc, QConvDesc, PredictView = STRUCTS["iswm_conv_desc"], STRUCTS["iswm_qconv_desc"], STRUCTS["iswm_predict_view"]
 
 
-class ScenePlan(Structure):
+class ScenePlan(STRUCTS["iswm_scene_plan"]):
     """iswm_scene_plan: nty x ntx windows of th x tw every (sy, sx) pixels over an H x W scene, the last window of an
     axis pulled back inside it; ramp = the blending ramp.  Windows are numbered k = ty * ntx + tx."""
-    _fields_ = [(n, c_int) for n in ("H", "W", "th", "tw", "sy", "sx", "nty", "ntx", "ramp")]
 
     @property
     def ntiles(self):
@@ -42,191 +139,6 @@ class ScenePlan(Structure):
     def astuple(self):
         return tuple(getattr(self, n) for n, _ in self._fields_)
 
-
-class PredictView(Structure):
-    """iswm_predict_view: one view's low-resolution logits [N][Hi][Wi][ldx] and whether the view was mirrored"""
-    _fields_ = [("yl", c_void_p), ("Hi", c_int), ("Wi", c_int), ("flip", c_int)]
-
-
-P = c_void_p
-_SIGS = {
-    # name: (restype, [argtypes])
-    "iswm_last_error": (c_char_p, []),
-    "iswm_version": (c_int, []),
-    "iswm_set_conv_math": (c_int, [c_int]),
-    "iswm_get_conv_math": (c_int, []),
-    "iswm_conv2d_kernel_name": (c_int, [POINTER(ConvDesc), c_int, c_char_p, c_int]),
-    "iswm_conv2d_stat_tile_rows": (c_int, [POINTER(ConvDesc)]),
-    "iswm_conv2d_stat_tiles": (c_int, [POINTER(ConvDesc)]),
-    "iswm_conv2d_fwd": (c_int, [POINTER(ConvDesc), P, P, P, P, P, P]),
-    "iswm_conv2d_dgrad": (c_int, [POINTER(ConvDesc), P, P, P, c_int, P]),
-    "iswm_transpose_weights": (c_int, [POINTER(ConvDesc), P, P, P]),
-    "iswm_conv2d_dgrad_wants_wt": (c_int, [POINTER(ConvDesc)]),
-    "iswm_conv2d_dgrad_wt": (c_int, [POINTER(ConvDesc), P, P, P, c_int, P]),
-    "iswm_conv2d_packed_weight_bytes": (c_size_t, [POINTER(ConvDesc), c_int]),
-    "iswm_conv2d_pack_weights": (c_int, [POINTER(ConvDesc), c_int, P, P, P]),
-    "iswm_packed_weight_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "iswm_pack_job_blocks": (c_int, [c_int, c_int, c_int, c_int]),
-    "iswm_pack_weights_batch": (c_int, [P, c_int, c_int, P]),
-    "iswm_conv2d_fwd_packed_stat_layout": (c_int, [POINTER(ConvDesc), POINTER(c_int), POINTER(c_int)]),
-    "iswm_conv2d_fwd_packed": (c_int, [POINTER(ConvDesc), P, P, P, P, P, P]),
-    "iswm_conv2d_dgrad_packed": (c_int, [POINTER(ConvDesc), P, P, P, c_int, P]),
-    "iswm_split_planes": (c_int, [P, c_int64, c_int, c_int, P, c_int, c_int64, P]),
-    "iswm_join_planes": (c_int, [P, c_int, c_int64, c_int64, c_int, P, c_int, P]),
-    "iswm_bn_apply_pl": (c_int, [P, c_int64, c_int, c_int, P, P, P, P, c_int, c_int64, c_int, P, c_int, c_int64, P]),
-    "iswm_bn_backward_pl": (c_int, [P, c_int, P, c_int, c_int64, P, c_int, c_int64, c_int, P, P, P, P, P, c_int, c_int, P, P, P,
-                                    c_int, c_int64, P, c_int, P, c_size_t, P]),
-    "iswm_maxpool3x3s2_fwd_pl": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int64, P, c_int, c_int, P]),
-    "iswm_gap_fwd_pl": (c_int, [P, c_int64, c_int, c_int, c_int, c_int, P, P]),
-    "iswm_bcast_fwd_pl": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int64, P]),
-    "iswm_bilinear_fwd_pl": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int64, c_int, c_int, c_int, P]),
-    "iswm_conv2d_pl2_weight_bytes": (c_size_t, [POINTER(ConvDesc), c_int]),
-    "iswm_conv2d_pl2_pack_weights": (c_int, [POINTER(ConvDesc), c_int, P, P, P]),
-    "iswm_conv2d_pl2_tile_rows": (c_int, [POINTER(ConvDesc), c_int]),
-    "iswm_conv2d_fwd_pl2": (c_int, [POINTER(ConvDesc), P, c_int64, P, P, P, P, P]),
-    "iswm_conv2d_dgrad_pl2": (c_int, [POINTER(ConvDesc), P, c_int64, P, P, c_int, P]),
-    "iswm_conv2d_dgrad_pl2_stat_tiles": (c_int, [POINTER(ConvDesc)]),
-    "iswm_conv2d_dgrad_pl2_bn": (c_int, [POINTER(ConvDesc), P, c_int64, P, P, c_int, P, c_int, P, P, P, P, c_int, P, c_int, P,
-                                         c_int, P]),
-    "iswm_bn_backward_stats_pl": (c_int, [P, c_int, P, c_int, c_int64, P, c_int, c_int64, c_int, P, P, P, P, P, c_int, c_int, P, P,
-                                          P, c_int, c_int64, P, c_int, P, c_int, P, c_size_t, P]),
-    "iswm_aspp_plan_bytes": (c_size_t, [POINTER(ConvDesc), c_int, POINTER(c_int), POINTER(c_int), c_int]),
-    "iswm_aspp_plan": (c_int, [POINTER(ConvDesc), c_int, POINTER(c_int), POINTER(c_int), c_int, P, c_int]),
-    "iswm_aspp_fwd": (c_int, [POINTER(ConvDesc), c_int, POINTER(c_int), POINTER(c_int), P, P, c_int64, POINTER(c_void_p),
-                              POINTER(c_void_p), POINTER(c_void_p), P]),
-    "iswm_aspp_bwd": (c_int, [POINTER(ConvDesc), c_int, POINTER(c_int), POINTER(c_int), P, P, c_int64, c_int, POINTER(c_void_p), P,
-                              c_int, P, c_int64, POINTER(c_void_p), P, c_size_t, P]),
-    "iswm_conv2d_wgrad_planes_ok": (c_int, [POINTER(ConvDesc)]),
-    "iswm_conv2d_wgrad_planes_workspace": (c_size_t, [POINTER(ConvDesc)]),
-    "iswm_conv2d_wgrad_planes": (c_int, [POINTER(ConvDesc), P, c_int64, P, c_int64, P, P, c_size_t, P]),
-    "iswm_conv2d_wgrad_workspace": (c_size_t, [POINTER(ConvDesc)]),
-    "iswm_dwconv2d_fwd": (c_int, [POINTER(ConvDesc), P, P, c_int, P, P, P]),
-    "iswm_dwconv2d_dgrad": (c_int, [POINTER(ConvDesc), P, P, c_int, P, c_int, P]),
-    "iswm_dwconv2d_wgrad_workspace": (c_size_t, [POINTER(ConvDesc)]),
-    "iswm_dwconv2d_wgrad": (c_int, [POINTER(ConvDesc), P, P, c_int, P, P, c_size_t, P]),
-    "iswm_dwconv3x3_stat_tile_rows": (c_int, [POINTER(ConvDesc)]),
-    "iswm_dwconv3x3_stat_tiles": (c_int, [POINTER(ConvDesc)]),
-    "iswm_dwconv3x3_fwd_stats": (c_int, [POINTER(ConvDesc), P, P, c_int, P, P, P]),
-    "iswm_dwconv3x3_bwd_workspace": (c_size_t, [POINTER(ConvDesc)]),
-    "iswm_dwconv3x3_bwd": (c_int, [POINTER(ConvDesc), P, P, P, c_int, P, c_int, c_int, P, P, c_size_t, P]),
-    "iswm_conv2d_wgrad": (c_int, [POINTER(ConvDesc), P, P, P, P, c_size_t, P]),
-    "iswm_colstat_tiles": (c_int, [c_int64]),
-    "iswm_colstat_tile_rows": (c_int64, [c_int64]),
-    "iswm_colstat": (c_int, [P, c_int64, c_int, c_int, P, P]),
-    "iswm_bn_finalize": (c_int, [P, c_int, c_int, c_int64, c_int64, P, P, P, P, c_float, c_float, P, P, P, P, P]),
-    "iswm_colstat_res": (c_int, [P, c_int64, c_int, c_int, P, P]),
-    "iswm_bn_finalize_res": (c_int, [P, c_int, c_int, c_int64, c_int64, P, P, P, P, c_float, c_float, P, P, P, P, P]),
-    "iswm_bn_eval_coeffs": (c_int, [c_int, P, P, P, P, c_float, P, P, P, P, P]),
-    "iswm_bn_apply": (c_int, [P, c_int64, c_int, c_int, P, P, P, P, c_int, c_int, P, c_int, P]),
-    "iswm_bn_bwd_workspace": (c_size_t, [c_int64, c_int]),
-    "iswm_bn_backward": (c_int, [P, c_int, P, c_int, P, c_int, c_int64, c_int, P, P, P, P, P, c_int, c_int, P, P, P, c_int,
-                                 P, c_int, P, c_size_t, P]),
-    "iswm_colsum_finalize": (c_int, [P, c_int, c_int, P, P, P]),
-    "iswm_maxpool3x3s2_fwd": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P]),
-    "iswm_maxpool3x3s2_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
-    "iswm_gap_fwd": (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
-    "iswm_gap_bwd": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P]),
-    "iswm_bcast_fwd": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
-    "iswm_bcast_bwd": (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
-    "iswm_bilinear_fwd": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P]),
-    "iswm_bilinear_bwd": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P]),
-    "iswm_bilinear_nhwc_to_nchw_fwd": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
-    "iswm_bilinear_nhwc_to_nchw_bwd": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
-    "iswm_nchw_to_nhwc": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
-    "iswm_nhwc_to_nchw": (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
-    "iswm_copy_channels": (c_int, [P, c_int, P, c_int, c_int64, c_int, P]),
-    "iswm_add_inplace": (c_int, [P, P, c_int64, P]),
-    "iswm_scale_inplace": (c_int, [P, c_int64, P, c_float, P]),
-    "iswm_bn_apply_classify": (c_int, [P, c_int64, c_int, c_int, P, P, P, P, P, P, c_int, P]),
-    "iswm_bn_classify_bwd_workspace": (c_size_t, [c_int64, c_int]),
-    "iswm_bn_backward_classify": (c_int, [P, c_int, P, P, c_int, c_int64, c_int, P, P, P, P, P, c_int, P, P, P, P, c_int, c_int64,
-                                          P, c_size_t, P]),
-    "iswm_pad_weights": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P]),
-    "iswm_unpad_weights": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
-    "iswm_fill_zero": (c_int, [P, c_size_t, P]),
-    "iswm_zero_cols": (c_int, [P, c_int64, c_int64, c_int, c_int, c_int64, c_int, P]),
-    "iswm_dropout_fwd": (c_int, [P, P, P, c_int64, c_float, c_uint64, c_uint64, P]),
-    "iswm_dropout_bwd": (c_int, [P, P, P, c_int64, c_float, P]),
-    "iswm_loss_blocks": (c_int, [c_int64]),
-    "iswm_loss_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, c_float, c_float, c_int, P, P, P]),
-    "iswm_loss_finalize": (c_int, [P, c_int, c_int, c_int64, P, P, P]),
-    "iswm_loss_bwd_scale": (c_int, [P, c_int64, P, P, c_int, c_int64, P]),
-    "iswm_overlap_loss_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, P, P, P]),
-    "iswm_overlap_loss_coeffs": (c_int, [P, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_int, P, P, P]),
-    "iswm_overlap_loss_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, P, P, P, P]),
-    "iswm_ohem_digits": (c_int, []),
-    "iswm_ohem_bins": (c_int, []),
-    "iswm_ohem_keys": (c_int, [P, P, c_int, c_int, c_int, c_int64, c_int, P, P, P, P]),
-    "iswm_ohem_hist": (c_int, [P, c_int64, P, c_int, P, P]),
-    "iswm_ohem_scan": (c_int, [P, P, c_int, c_int64, c_float, P, P, P]),
-    "iswm_ohem_sums": (c_int, [P, P, c_int, c_int64, c_int, P, P, P, P, P]),
-    "iswm_ohem_loss": (c_int, [P, P, P]),
-    "iswm_ohem_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, P, P, P, P, P, P]),
-    "iswm_lovasz_digits": (c_int, []),
-    "iswm_lovasz_tile": (c_int, []),
-    "iswm_lovasz_workspace": (c_int64, [c_int64, c_int64]),
-    "iswm_lovasz_keys": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, c_int, P, P, P, P, P]),
-    "iswm_lovasz_sort": (c_int, [P, c_int64, c_int64, P, c_int64, P, P, P]),
-    "iswm_lovasz_weights": (c_int, [P, P, P, c_int64, c_int64, P, c_int64, P, P, P]),
-    "iswm_lovasz_loss": (c_int, [P, c_double, c_double, P, P]),
-    "iswm_lovasz_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, c_int, c_int, P, P, P, P, P]),
-    "iswm_argmax_nchw": (c_int, [P, c_int, c_int, c_int64, P, P]),
-    "iswm_augment_batch": (c_int, [P, P, P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P, P]),
-    "iswm_aug_rotate": (c_int, [P, P, P, P, c_int, c_int64, P, c_size_t, P, c_size_t, P]),
-    "iswm_augment_batch_ex_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "iswm_augment_batch_ex": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_int, P,
-                                      P, P, c_size_t, P]),
-    "iswm_label_prepare_workspace": (c_size_t, [c_int64]),
-    "iswm_label_prepare": (c_int, [P, c_int64, P, P, c_size_t, P]),
-    "iswm_label_count_workspace": (c_size_t, [c_int64]),
-    "iswm_label_count": (c_int, [P, c_int64, c_int, P, P, c_size_t, P]),
-    "iswm_aug_tables_workspace": (c_size_t, [P, c_int]),
-    "iswm_aug_tables": (c_int, [P, c_int, c_int, P, c_size_t, P]),
-    "iswm_gather_normalize": (c_int, [P, P, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P, P]),
-    "iswm_confusion_matrix": (c_int, [P, c_int, P, c_int, c_int64, c_int, P, P]),
-    "iswm_confusion_matrix_logits": (c_int, [P, c_int, P, c_int, c_int, c_int64, c_int, P, P]),
-    "iswm_mask_morph": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
-    "iswm_ccl": (c_int, [P, c_int, c_int, c_int, P, P, P]),
-    "iswm_mask_preprocess_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "iswm_mask_preprocess": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
-    "iswm_mask_fronts": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
-    "iswm_front_error": (c_int, [P, P, c_int, c_int, c_double, P, P]),
-    "iswm_mask_pair_scores": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P, P]),
-    "iswm_region_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "iswm_region_score": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
-    "iswm_predict_normalize": (c_int, [P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P]),
-    "iswm_predict_maps_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "iswm_predict_maps": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P, P,
-                                  P, P, P, P, c_size_t, P]),
-    "iswm_scene_plan_make": (c_int, [c_int, c_int, c_int, c_int, POINTER(ScenePlan)]),
-    "iswm_scene_tiles_normalize": (c_int, [P, POINTER(ScenePlan), c_int, c_int, POINTER(c_float), POINTER(c_float), P, P]),
-    "iswm_scene_maps_workspace": (c_size_t, [c_int, c_int]),
-    "iswm_scene_maps": (c_int, [P, POINTER(ScenePlan), c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P, P, P, P,
-                                P, P, c_size_t, P]),
-    "iswm_predict_view_normalize": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float),
-                                            P, P]),
-    "iswm_predict_views_maps_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "iswm_predict_views_maps": (c_int, [POINTER(PredictView), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                                        c_int, c_int, P, P, P, P, P, P, c_size_t, P]),
-    "iswm_val_panels": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float),
-                                POINTER(c_float), P, P, P, P, P, P, P, P, P, P]),
-    "iswm_qconv_weight_bytes": (c_size_t, [POINTER(QConvDesc)]),
-    "iswm_qconv_fwd": (c_int, [POINTER(QConvDesc), P, P, P, P, P, c_double, c_double, P, P]),
-    "iswm_absmax_workspace": (c_size_t, [c_int64, c_int]),
-    "iswm_absmax": (c_int, [P, c_int64, c_int64, c_int, c_int, P, c_size_t, P, P]),
-    "iswm_quantize_i8": (c_int, [P, c_int64, c_int64, c_int, c_int, c_double, c_int, P, c_int, P]),
-    "iswm_qgap": (c_int, [P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, P]),
-    "iswm_qbcast": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P]),
-    "iswm_qbilinear": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_double, P, c_int, P]),
-    "iswm_sgd_step": (c_int, [P, P, P, c_int64, P, c_float, c_float, c_int, P]),
-    "iswm_adam_step": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, c_int, P]),
-    "iswm_grad_sqnorm_slots": (c_int, []),
-    "iswm_grad_sqnorm": (c_int, [P, c_int64, P, c_int, P]),
-    "iswm_clip_finalize": (c_int, [P, c_float, P, P]),
-    "iswm_sgd_step_ex": (c_int, [P, P, P, c_int64, P, c_float, c_float, c_int, P, P, P]),
-    "iswm_adam_step_ex": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, c_int, P, P, P]),
-    "iswm_swap_f32": (c_int, [P, P, c_int64, P]),
-}
 
 EXPORTS = tuple(_SIGS)
 _lib = None

@@ -20,18 +20,7 @@ namespace iswm {
 
 constexpr int AUG_PRECISION_BITS = 22;   // Pillow: 32 - 8 - 2
 
-struct AugSample {           // mirrors iswm_aug_sample
-    long long img_off;       // byte offset of the uint8 HWC (3 channel) source image
-    long long lbl_off;       // byte offset of the uint8 HW source label
-    int src_h, src_w;
-    int rs_h, rs_w;          // size after ExtRandomScale
-    int pad;                 // border added on every side by pad_if_needed (0 if none)
-    int crop_i, crop_j;      // crop origin in the padded image
-    int flip;
-    int tab_off;             // offset (ints) of this sample's tables in `tables`
-    int ksize_h, ksize_v;    // taps per output column / row
-    int reserved;
-};
+using AugSample = iswm_aug_sample;
 
 __device__ __forceinline__ int clip8(int v) {
     v >>= AUG_PRECISION_BITS;
@@ -108,16 +97,7 @@ __global__ __launch_bounds__(256) void k_augment(const unsigned char* __restrict
 }
 
 // ---- rotation, vertical flip, colour jitter ----------------------------------------------------
-struct AugExtra {            // mirrors iswm_aug_extra
-    int rot_mode;
-    int a[6];
-    int n_ops;
-    long long rot_img_off, rot_lbl_off;
-    int ops[4];
-    float factor[4];
-    int hue_shift;
-    int reserved[3];
-};
+using AugExtra = iswm_aug_extra;
 
 constexpr int AUG_SUM_BLOCKS = 64;       // partial grey sums per sample (k_augment_gray_sum's grid.x)
 
@@ -349,7 +329,7 @@ extern "C" int iswm_aug_rotate(const unsigned char* images, const unsigned char*
     ISWM_REQUIRE(images && labels && samples && extras && rot_images && rot_labels, "aug_rotate: null pointer");
     ISWM_REQUIRE(B > 0 && B <= 65535 && max_hw > 0, "aug_rotate: need 0 < B <= 65535 and max_hw > 0");
     ISWM_REQUIRE(rot_images_bytes > 0 && rot_labels_bytes > 0, "aug_rotate: empty scratch arena");
-    static_assert(sizeof(AugExtra) == 96 && sizeof(AugExtra) == sizeof(iswm_aug_extra), "iswm_aug_extra layout");
+    static_assert(sizeof(AugExtra) == 96, "iswm_aug_extra layout");
     hipLaunchKernelGGL(k_aug_rotate, dim3(stream_grid(max_hw, 256), B), dim3(256), 0, (hipStream_t)stream, images, labels,
                        (const AugSample*)samples, (const AugExtra*)extras, rot_images, (long long)rot_images_bytes,
                        rot_labels, (long long)rot_labels_bytes);

@@ -418,8 +418,7 @@ extern "C" int iswm_pack_job_blocks(int Cout, int taps, int Cin, int kind) {
     return pack_job_blocks_x6(Cout, taps, Cin, kind == 1);
 }
 
-extern "C" int iswm_pack_weights_batch(const iswm_pack_job* jobs_dev, int njobs, int total_blocks,
-                                       iswm_stream_t stream) {
+extern "C" int iswm_pack_weights_batch(const void* jobs_dev, int njobs, int total_blocks, iswm_stream_t stream) {
     ISWM_REQUIRE(jobs_dev && njobs > 0 && total_blocks > 0, "pack_weights_batch: bad argument");
     static_assert(sizeof(iswm_pack_job) == 40, "iswm_pack_job layout");
     launch_pack_weights_batch(jobs_dev, njobs, total_blocks, math_planes(conv_math()), (hipStream_t)stream);

@@ -435,12 +435,7 @@ __global__ __launch_bounds__(256) void k_pack_weights_x6(const float* __restrict
 
 // All conv weights of a model in ONE launch (a training step otherwise issues ~220 tiny pack kernels, each mostly
 // launch latency): jobs[] is sorted by first_block; a workgroup finds its job by binary search.
-struct PackJob {             // mirrors iswm_pack_job
-    const float* w;
-    void* packed;
-    int Cout, T, Cin, kind;
-    int first_block, reserved;
-};
+using PackJob = iswm_pack_job;
 
 template <int NP>
 __global__ __launch_bounds__(256) void k_pack_weights_batch(const PackJob* __restrict__ jobs, int njobs) {
@@ -456,17 +451,17 @@ __global__ __launch_bounds__(256) void k_pack_weights_batch(const PackJob* __res
     if (j.kind >= 2) {          // kinds 2 / 3: the 16x16x32 fragment order of the planes kernels (conv_mfma_pl2.hip)
         const bool dg = j.kind == 3;
         const int NC = dg ? j.Cin : j.Cout, GC = dg ? j.Cout : j.Cin;
-        const int cbs = ((NC + 127) / 128) * 8, K32 = j.T * GC / 32;
+        const int cbs = ((NC + 127) / 128) * 8, K32 = j.taps * GC / 32;
         if (idx >= cbs * K32 * 64) return;
-        if (dg) pack_weights_pl2_body<true, NP>(j.w, (uint4*)j.packed, j.Cout, j.T, j.Cin, K32, idx);
-        else pack_weights_pl2_body<false, NP>(j.w, (uint4*)j.packed, j.Cout, j.T, j.Cin, K32, idx);
+        if (dg) pack_weights_pl2_body<true, NP>(j.w, (uint4*)j.packed, j.Cout, j.taps, j.Cin, K32, idx);
+        else pack_weights_pl2_body<false, NP>(j.w, (uint4*)j.packed, j.Cout, j.taps, j.Cin, K32, idx);
         return;
     }
     const int NC = j.kind ? j.Cin : j.Cout, GC = j.kind ? j.Cout : j.Cin;
-    const int cbs = ((NC + 63) / 64) * 2, K16 = j.T * GC / 16;
+    const int cbs = ((NC + 63) / 64) * 2, K16 = j.taps * GC / 16;
     if (idx >= cbs * K16 * 64) return;
-    if (j.kind) pack_weights_body<true, NP>(j.w, (uint4*)j.packed, j.Cout, j.T, j.Cin, K16, idx);
-    else pack_weights_body<false, NP>(j.w, (uint4*)j.packed, j.Cout, j.T, j.Cin, K16, idx);
+    if (j.kind) pack_weights_body<true, NP>(j.w, (uint4*)j.packed, j.Cout, j.taps, j.Cin, K16, idx);
+    else pack_weights_body<false, NP>(j.w, (uint4*)j.packed, j.Cout, j.taps, j.Cin, K16, idx);
 }
 
 void launch_pack_weights_batch(const void* jobs_dev, int njobs, int total_blocks, int planes, hipStream_t s) {

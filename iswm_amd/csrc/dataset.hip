@@ -20,15 +20,7 @@ namespace iswm {
 constexpr int DS_BLOCK = 256;
 constexpr int AUG_TAB_PRECISION_BITS = 22;   // Pillow: 32 - 8 - 2
 
-struct AugSampleT {          // mirrors iswm_aug_sample (augment.hip AugSample)
-    long long img_off, lbl_off;
-    int src_h, src_w;
-    int rs_h, rs_w;
-    int pad, crop_i, crop_j, flip;
-    int tab_off;
-    int ksize_h, ksize_v;
-    int reserved;
-};
+using AugSampleT = iswm_aug_sample;
 
 // 0x80 in every byte of x that is non-zero (no carry crosses a byte: 0x7f + 0x7f = 0xfe)
 __device__ __forceinline__ unsigned nonzero_bytes(unsigned x) {

@@ -563,7 +563,6 @@ class WeightPacker(object):
         self.key, self.jobs, self.njobs, self.blocks, self.entries = None, None, 0, 0, []
 
     def _build(self, dev):
-        import ctypes
         from .. import _lib
         lib = _lib.load()
         jobs, entries, first = [], [], 0
@@ -596,14 +595,8 @@ class WeightPacker(object):
                 m._iswm_wpk = e
                 entries.append((m, e))
                 keep.append(bufs)
-
-        class _Job(ctypes.Structure):
-            _fields_ = [("w", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("Cout", ctypes.c_int), ("taps", ctypes.c_int),
-                        ("Cin", ctypes.c_int), ("kind", ctypes.c_int), ("first_block", ctypes.c_int),
-                        ("reserved", ctypes.c_int)]
-        arr = (_Job * max(1, len(jobs)))()
-        for i, j in enumerate(jobs):
-            arr[i] = _Job(*j)
+        job = _lib.STRUCTS["iswm_pack_job"]
+        arr = (job * max(1, len(jobs)))(*(job(*j) for j in jobs))
         self.jobs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev) if jobs else None
         self.njobs, self.blocks, self.entries = len(jobs), first, entries
 

@@ -27,9 +27,9 @@ BN_EPS = 1e-5
 class Act(enum.IntEnum):
     """activation fused behind a BatchNorm.  The values are the C ABI codes (include/iswm_hip.h, ISWM_ACT_*): int(act) is what
     the iswm_bn_apply* / iswm_bn_backward* entry points take."""
-    NONE = 0
-    RELU = 1
-    RELU6 = 6
+    NONE = _lib.CONSTANTS["ISWM_ACT_NONE"]
+    RELU = _lib.CONSTANTS["ISWM_ACT_RELU"]
+    RELU6 = _lib.CONSTANTS["ISWM_ACT_RELU6"]
 
     @classmethod
     def of(cls, v):
@@ -486,10 +486,11 @@ def conv2d_fwd(x, w, g, bias=None, out=None, want_stats=False):
     return out, partials, tiles
 
 
-# what iswm_conv2d_dgrad_pl2_bn applies to dx before it takes the sums (include/iswm_hip.h, ISWM_GATE_*)
-GATE_NONE = 0          # the producer stage has no activation
-GATE_RECOMPUTED = 2    # ReLU, no residual: the pattern recomputed from the producer's y and scale / shift
-GATE_RESIDUAL = 3      # ReLU behind a residual add: the pattern read from the saved output's hi plane, dx stored masked
+# what iswm_conv2d_dgrad_pl2_bn applies to dx before it takes the sums (include/iswm_hip.h, ISWM_GATE_*):
+#   NONE        the producer stage has no activation
+#   RECOMPUTED  ReLU, no residual: the pattern recomputed from the producer's y and scale / shift
+#   RESIDUAL    ReLU behind a residual add: the pattern read from the saved output's hi plane, dx stored masked
+GATE_NONE, GATE_RECOMPUTED, GATE_RESIDUAL = (_lib.CONSTANTS["ISWM_GATE_" + n] for n in ("NONE", "RECOMPUTED", "RESIDUAL"))
 
 
 class BnStats(object):
@@ -1634,7 +1635,7 @@ def scene_maps(yl_tiles, num_classes, fg, plan, thr, min_prob, max_prob, want_pr
     return PredictMaps((pred, conf, band, prob, stats, packed))
 
 
-PREDICT_MAX_VIEWS = 16             # ISWM_PREDICT_MAX_VIEWS
+PREDICT_MAX_VIEWS = _lib.CONSTANTS["ISWM_PREDICT_MAX_VIEWS"]
 TTA_MAX_SCALES = 8
 TTA_SCALE_RANGE = (0.25, 4.0)
 

@@ -26,7 +26,6 @@ import numbers
 import random
 
 import numpy as np
-import torch
 
 from .. import _lib
 from .._lib import call
@@ -156,31 +155,12 @@ def _nearest_table(in_size, out_size):
     return np.clip(idx, 0, in_size - 1).astype(np.int32)       # (indices outside the source cannot occur for a resize)
 
 
-class _AugSample(ctypes.Structure):
-    _fields_ = [("img_off", ctypes.c_longlong), ("lbl_off", ctypes.c_longlong),
-                ("src_h", ctypes.c_int), ("src_w", ctypes.c_int), ("rs_h", ctypes.c_int), ("rs_w", ctypes.c_int),
-                ("pad", ctypes.c_int), ("crop_i", ctypes.c_int), ("crop_j", ctypes.c_int), ("flip", ctypes.c_int),
-                ("tab_off", ctypes.c_int), ("ksize_h", ctypes.c_int), ("ksize_v", ctypes.c_int),
-                ("reserved", ctypes.c_int)]
+# the header's records, and the same bytes as numpy records for filling a pinned buffer without a Python object per field
+_AUG_SAMPLE = _lib.STRUCTS["iswm_aug_sample"]
+_AUG_DTYPE, _AUG_EXTRA_DTYPE = np.dtype(_AUG_SAMPLE), np.dtype(_lib.STRUCTS["iswm_aug_extra"])
 
-
-# the same 64 bytes as a numpy record, for filling a pinned buffer without a Python object per field
-_AUG_DTYPE = np.dtype([(n, "<i8" if t is ctypes.c_longlong else "<i4") for n, t in _AugSample._fields_])
-
-
-class _AugExtra(ctypes.Structure):
-    """iswm_aug_extra"""
-    _fields_ = [("rot_mode", ctypes.c_int), ("a", ctypes.c_int * 6), ("n_ops", ctypes.c_int),
-                ("rot_img_off", ctypes.c_longlong), ("rot_lbl_off", ctypes.c_longlong), ("ops", ctypes.c_int * 4),
-                ("factor", ctypes.c_float * 4), ("hue_shift", ctypes.c_int), ("reserved", ctypes.c_int * 3)]
-
-
-_AUG_EXTRA_DTYPE = np.dtype([("rot_mode", "<i4"), ("a", "<i4", (6,)), ("n_ops", "<i4"), ("rot_img_off", "<i8"),
-                             ("rot_lbl_off", "<i8"), ("ops", "<i4", (4,)), ("factor", "<f4", (4,)), ("hue_shift", "<i4"),
-                             ("reserved", "<i4", (3,))])
-assert _AUG_EXTRA_DTYPE.itemsize == ctypes.sizeof(_AugExtra) == 96
-
-OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION, OP_HUE = 0, 1, 2, 3      # ISWM_AUG_OP_*
+OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION, OP_HUE = (_lib.CONSTANTS["ISWM_AUG_OP_" + n] for n in
+                                                     ("BRIGHTNESS", "CONTRAST", "SATURATION", "HUE"))
 ROT_MAX_SIDE = 8192     # keeps Pillow's 32-bit fixed-point walk (Geometry.c affine_fixed) clear of overflow
 
 
@@ -371,10 +351,11 @@ class ExtCompose(object):
         draw with explicit (rs_h, rs_w, pad, crop_i, crop_j, flip) tuples (tests)."""
         if len(images) != len(labels) or not images:
             raise ValueError("need equally many images and labels (got %d, %d)" % (len(images), len(labels)))
+        import torch
         dev = images[0].device
         th, tw = self.crop.size
         B = len(images)
-        samples = (_AugSample * B)()
+        samples = (_AUG_SAMPLE * B)()
         extras = np.zeros(B, dtype=_AUG_EXTRA_DTYPE) if self.extended else None
         rot_img, rot_lbl, any_contrast = 0, 0, False
         tabs, tab_off, img_off, lbl_off = [], 0, 0, 0
@@ -431,6 +412,7 @@ class ExtCompose(object):
                          any_contrast, mean, std, out, out_lbl, stream):
         """iswm_aug_rotate into scratch arenas of rot_img / rot_lbl bytes (skipped when no sample rotates), then
         iswm_augment_batch_ex; every buffer comes from torch's caching allocator on the current stream"""
+        import torch
         th, tw = self.crop.size
         dev = out.device
         rimg = rlbl = None
@@ -457,6 +439,7 @@ class ExtCompose(object):
         B = len(indices)
         if B < 1:
             raise ValueError("need at least one tile index")
+        import torch
         th, tw = self.crop.size
         rec = np.zeros(B, dtype=_AUG_DTYPE)
         extras = np.zeros(B, dtype=_AUG_EXTRA_DTYPE) if self.extended else None

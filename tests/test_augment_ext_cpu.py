@@ -284,9 +284,10 @@ def test_extra_record_layout_and_exports():
 
     from iswm_amd import _lib
     from iswm_amd.utils import ext_transforms as et
-    assert ctypes.sizeof(et._AugExtra) == et._AUG_EXTRA_DTYPE.itemsize == 96
-    for name, _ in et._AugExtra._fields_:
-        assert getattr(et._AugExtra, name).offset == et._AUG_EXTRA_DTYPE.fields[name][1], name
+    extra = _lib.STRUCTS["iswm_aug_extra"]
+    assert ctypes.sizeof(extra) == et._AUG_EXTRA_DTYPE.itemsize == 96
+    for name, _ in extra._fields_:
+        assert getattr(extra, name).offset == et._AUG_EXTRA_DTYPE.fields[name][1], name
     header = open(os.path.join(ROOT, "include", "iswm_hip.h")).read()
     declared = set(re.findall(r"\b(iswm_[a-z0-9_]+)\s*\(", header))
     for n in ("iswm_aug_rotate", "iswm_augment_batch_ex_workspace", "iswm_augment_batch_ex"):

@@ -9,8 +9,10 @@ labels renumbered in order of appearance, the per-file g_zero_row_* / g_dump_* s
     same opcodes  the same opcode sequence, operands (register numbers, immediates) differ
     differs       anything else
 followed by the instruction counts and the resource fields of the code-object metadata, parent/new.  A resource field that
-is larger in the new tree is marked with `!`.  This is the table of profiles/pl2_refactor_isa.txt, conv_route_refactor_isa.txt,
-scene_predict_isa.txt and wgrad_refactor_isa.txt.  It compares two trees and nothing else."""
+is larger in the new tree is marked with `!`.  A kernel left unmatched by mangled symbol (a parameter type was renamed) is paired
+by its demangled name without the parameter list when that name is unique in both trees, compared with the mangled names inside
+its instruction lines masked, and reported with `(renamed)` appended.  This is the table of profiles/pl2_refactor_isa.txt,
+conv_route_refactor_isa.txt, scene_predict_isa.txt and wgrad_refactor_isa.txt.  It compares two trees and nothing else."""
 import os
 import re
 import subprocess
@@ -25,6 +27,7 @@ FIELDS = (("vgpr", ".vgpr_count"), ("agpr", ".agpr_count"), ("sgpr", ".sgpr_coun
           ("lds", ".group_segment_fixed_size"), ("vspill", ".vgpr_spill_count"), ("sspill", ".sgpr_spill_count"))
 MASKED = re.compile(r"\b\w*g_(?:zero_row|dump)_\w*")
 LABEL = re.compile(r"\.LBB\d+_\d+")
+MANGLED = re.compile(r"\b_Z\w+")
 
 
 def assembly(tree, name, out):
@@ -80,6 +83,16 @@ def insns(lines):
     return [ln for ln in lines if not ln.endswith(":") and not ln.startswith(".")]
 
 
+def renamed(a, b, names):
+    """{parent symbol: new symbol} of the kernels left unmatched by symbol whose demangled name is unique on both sides"""
+    pairs = {}
+    for sym in a:
+        same = [[t for t in side if names[t] == names[sym]] for side in (a, b)]
+        if sym not in b and len(same[0]) == 1 and len(same[1]) == 1 and same[1][0] not in a:
+            pairs[sym] = same[1][0]
+    return pairs
+
+
 def compare(name, tmp, parent, new):
     a = kernels(assembly(parent, name, os.path.join(tmp, "a_" + name + ".s")))
     b = kernels(assembly(new, name, os.path.join(tmp, "b_" + name + ".s")))
@@ -98,12 +111,15 @@ def main(argv):
         for name, a, b in ex.map(lambda f: compare(f, tmp, parent, new), files):
             short = re.sub(r"^conv_|\.hip$", "", name)
             names = demangle(sorted(set(a) | set(b)))
-            for sym in sorted(names, key=names.get):
-                if sym not in a or sym not in b:
+            pairs = renamed(a, b, names)
+            for sym in sorted(set(names) - set(pairs.values()), key=names.get):
+                if sym not in a or pairs.get(sym, sym) not in b:
                     print("%-10s %-48s %s" % (short, names[sym], "only in parent" if sym in a else "only in new"))
                     changed += 1
                     continue
-                (la, ma), (lb, mb) = a[sym], b[sym]
+                (la, ma), (lb, mb) = a[sym], b[pairs.get(sym, sym)]
+                if sym in pairs:
+                    la, lb = ([MANGLED.sub("Z_SYM", ln) for ln in side] for side in (la, lb))
                 ia, ib = insns(la), insns(lb)
                 if la == lb:
                     verdict = "identical"
@@ -114,7 +130,8 @@ def main(argv):
                 changed += verdict != "identical"
                 res = " ".join("%s %d/%d%s" % (k, ma[k], mb[k], "!" if mb[k] > ma[k] else "") for k, _ in FIELDS)
                 worse += any(mb[k] > ma[k] for k, _ in FIELDS)
-                print("%-10s %-48s %-13s insns %d/%d  %s" % (short, names[sym], verdict, len(ia), len(ib), res))
+                print("%-10s %-48s %-13s insns %d/%d  %s%s" % (short, names[sym], verdict, len(ia), len(ib), res,
+                                                               "  (renamed)" if sym in pairs else ""))
     print("ALL IDENTICAL" if not changed else "%d kernel(s) not identical, %d with a larger resource field" % (changed, worse))
 
 
