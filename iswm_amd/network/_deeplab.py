@@ -64,12 +64,11 @@ class ASPPPooling(_hip.HipSequential):
         if out is None:
             out = ops.new_act(n, h, w, v.shape[3], x.device)
         ops.bcast_fwd(v, out)                                              # bilinear from 1x1 == broadcast
-        self._saved = (ctx, (n, h, w, c)) if save else None
+        _hip.keep(self, save, (ctx, (n, h, w, c)))
         return out
 
     def bwd(self, dy, sink, need_dx=True, dx=None, accumulate=False):
-        ctx, shape = self._saved
-        self._saved = None
+        ctx, shape = _hip.take(self, sink)
         dv = ops.bcast_bwd(dy)
         dpooled, _ = _hip.cba_bwd(ctx, dv, sink)
         if dx is None:
@@ -114,7 +113,7 @@ class ASPP(_hip.HipModule):
                 conv.fwd(x, save, out=cat[..., i * oc:(i + 1) * oc])
         if _hip.CALIB_RECORDER is not None:
             _hip.CALIB_RECORDER.record(self, cat)
-        self._saved = (tuple(x.shape), oc, fused) if save else None
+        _hip.keep(self, save, (tuple(x.shape), oc, fused))
         return self.project.fwd(cat, save)
 
     # ---- the parallel conv branches (convs[0..3]: 1x1 and the three atrous 3x3) as ONE launch each way (ops.aspp_fwd / aspp_dgrad:
@@ -175,8 +174,7 @@ class ASPP(_hip.HipModule):
         return ctxs
 
     def bwd(self, dy, sink):
-        xshape, oc, fused = self._saved
-        self._saved = None
+        xshape, oc, fused = _hip.take(self, sink)
         dcat = self.project.bwd(dy, sink)
         dx, first = None, 0
         if fused is not None:
@@ -251,12 +249,11 @@ class DeepLabHeadV3Plus(_hip.HipModule):
         ops.bilinear_fwd(a, hl, wl, out=cat[..., c_low:c_cat])
         if _hip.CALIB_RECORDER is not None:
             _hip.CALIB_RECORDER.record(self, cat, c_cat)
-        self._saved = (tuple(a.shape), c_low, c_cat) if save else None
+        _hip.keep(self, save, (tuple(a.shape), c_low, c_cat))
         return self.classifier.fwd(cat, save)
 
     def bwd(self, dy, sink):
-        (n, ha, wa, ca), c_low, c_cat = self._saved
-        self._saved = None
+        (n, ha, wa, ca), c_low, c_cat = _hip.take(self, sink)
         dcat = self.classifier.bwd(dy, sink)
         da = ops.bilinear_bwd(dcat[..., c_low:c_cat], ha, wa)
         dhi = self.aspp.bwd(da, sink)
@@ -274,15 +271,17 @@ class DeepLabHeadV3Plus(_hip.HipModule):
 class _HeadBridge(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, low, out, *params):
-        ctx.head, ctx.shapes = head, (low.shape[1], out.shape[1])
-        y = head.fwd({'low_level': ops.nchw_to_nhwc(low), 'out': ops.nchw_to_nhwc(out)}, True)
+        ctx.head, ctx.shapes, ctx.serial = head, (low.shape[1], out.shape[1]), _hip.new_serial()
+        y = head.fwd({'low_level': ops.nchw_to_nhwc(low), 'out': ops.nchw_to_nhwc(out)}, ctx.serial)
         return ops.nhwc_to_nchw(y, head.num_classes)
 
     @staticmethod
+    @_hip.once
     def backward(ctx, dy):
         head = ctx.head
+        _hip.claim(head, ctx.serial)
         cp = _hip.pad4(head.num_classes)
-        d = head.bwd(ops.nchw_to_nhwc(dy.contiguous(), cp), _hip.GradSink())
+        d = head.bwd(ops.nchw_to_nhwc(dy.contiguous(), cp), _hip.GradSink(serial=ctx.serial))
         dlow = ops.nhwc_to_nchw(d['low_level'], ctx.shapes[0]) if 'low_level' in d else None
         dout = ops.nhwc_to_nchw(d['out'], ctx.shapes[1])
         return (None, dlow, dout) + (None,) * (len(ctx.needs_input_grad) - 3)
@@ -323,13 +322,15 @@ def run_v3_head(head, feature):
 class _V3Bridge(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, x, *params):
-        ctx.head, ctx.cin = head, x.shape[1]
-        return ops.nhwc_to_nchw(head.fwd({'out': ops.nchw_to_nhwc(x)}, True), head.num_classes)
+        ctx.head, ctx.cin, ctx.serial = head, x.shape[1], _hip.new_serial()
+        return ops.nhwc_to_nchw(head.fwd({'out': ops.nchw_to_nhwc(x)}, ctx.serial), head.num_classes)
 
     @staticmethod
+    @_hip.once
     def backward(ctx, dy):
         head = ctx.head
-        d = head.bwd(ops.nchw_to_nhwc(dy.contiguous(), _hip.pad4(head.num_classes)), _hip.GradSink())
+        _hip.claim(head, ctx.serial)
+        d = head.bwd(ops.nchw_to_nhwc(dy.contiguous(), _hip.pad4(head.num_classes)), _hip.GradSink(serial=ctx.serial))
         return (None, ops.nhwc_to_nchw(d['out'], ctx.cin)) + (None,) * (len(ctx.needs_input_grad) - 2)
 
 

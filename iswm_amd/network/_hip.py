@@ -14,6 +14,8 @@ and the whole model is ONE node in torch's autograd graph (``_Bridge``), so
 torch op ever touches an activation.  All compute is libiswm_hip.so kernels.
 """
 import dataclasses
+import functools
+import itertools
 from typing import Optional
 
 import torch
@@ -63,10 +65,11 @@ class GradSink:
     """Where parameter gradients go.  ``target(p)`` returns a tensor shaped/strided
     like ``p`` for a kernel to overwrite; ``done(p)`` folds it into ``p.grad``
     (a no-op on the usual zero_grad(set_to_none=True) path) and fires the
-    data-parallel ready hook."""
+    data-parallel ready hook.  A bridge also puts its call's serial on it, which ``take`` checks."""
 
-    def __init__(self, on_ready=None):
+    def __init__(self, on_ready=None, serial=None):
         self.on_ready = on_ready
+        self.serial = serial             # of the forward call this backward belongs to (take); None: fwd / bwd driven by hand
         self._pending = {}
 
     def target(self, p):
@@ -84,6 +87,114 @@ class GradSink:
             ops.add_inplace(dense_flat(p.grad), dense_flat(tmp))
         if self.on_ready is not None:
             self.on_ready(p)
+
+
+# ---------------------------------------------------------------------------------------
+# What a forward saves for its backward lives on the modules (one slot each), not per call as under autograd.  So a
+# backward must find the state ITS forward saved, or refuse: every bridge draws a serial per call and hands it down as
+# `save` (a positive int: still truthy) and, on the GradSink, to the backward; `keep` stamps what it stores with it and
+# enters the module in the call's list, `take` checks the stamp, and `claim` checks every module of the call before a
+# bridge's backward launches anything.  Nothing here is thread-local: the autograd engine runs backward on a thread of
+# its own.
+# ---------------------------------------------------------------------------------------
+_SERIALS = itertools.count(1)
+
+REPLACED = ("a later forward of this module (or of a module containing / contained in it) replaced the state saved for "
+            "this backward; run forward and backward of each batch in turn, gradients accumulate")
+CONSUMED = ("the state saved for this backward was already consumed (a second backward through the same call, "
+            "`retain_graph`, is not supported)")
+
+
+class Serial(int):
+    """the number of one forward call through a bridge, with the modules that kept state for it (`mods`, in the order
+    their fwd finished).  The modules are stamped with the plain int, so they hold no reference back to the call."""
+
+    def __new__(cls, value):
+        self = int.__new__(cls, value)
+        self.mods = []
+        return self
+
+
+def new_serial():
+    """the Serial of a new forward call: a number no other call has (next() of itertools.count is atomic)"""
+    return Serial(next(_SERIALS))
+
+
+def _refuse(mod, why, root=None):
+    name = type(mod).__name__
+    if root is not None and root is not mod:
+        name = "%s (at its %s)" % (type(root).__name__, name)
+    return RuntimeError("%s: %s" % (name, why))
+
+
+def keep(mod, save, payload):
+    """the end of a module's fwd: store `payload` for the backward of call `save` (a bridge's Serial; True when fwd / bwd
+    are driven by hand: no stamp to check).  A falsy `save` stores nothing and clears what an earlier call left -- and
+    stamps the module all the same, so that the backward of that earlier call sees a forward came in between."""
+    if not save:
+        mod._saved, mod._stamp = None, next(_SERIALS)
+    elif save is True:
+        mod._saved, mod._stamp = payload, None
+    else:
+        mod._saved, mod._stamp = payload, int(save)
+        save.mods.append(mod)
+
+
+def peek(mod, sink):
+    """what take(mod, sink) would return, left in place; None when the module holds nothing for this call"""
+    serial = getattr(sink, "serial", None)
+    if serial is not None and getattr(mod, "_stamp", None) != serial:
+        return None
+    return getattr(mod, "_saved", None)
+
+
+def take(mod, sink):
+    """the start of a module's bwd: the payload keep() stored for this call, cleared from the module.  RuntimeError when
+    another forward's state stands there (REPLACED) or none (CONSUMED) -- never a wrong gradient."""
+    payload, stamp = getattr(mod, "_saved", None), getattr(mod, "_stamp", None)
+    mod._saved = None
+    serial = getattr(sink, "serial", None)
+    if serial is not None and stamp != serial:
+        raise _refuse(mod, REPLACED)
+    if payload is None:
+        raise _refuse(mod, CONSUMED)
+    return payload
+
+
+def claim(root, serial):
+    """A bridge's backward calls this first, before it launches a kernel or touches a .grad: every module that kept state
+    for the forward call `serial` (the bridge's Serial) still holds it.  If another forward went through one of them since
+    -- whole or in part, saving or not -- the state under `root` is dropped (the module is usable again) and REPLACED
+    raised; if the call's state is gone already, CONSUMED."""
+    for m in reversed(serial.mods):                     # `root` first: it kept last
+        if m._stamp != serial:
+            drop(root)
+            raise _refuse(m, REPLACED, root)
+        if m._saved is None:
+            raise _refuse(m, CONSUMED, root)
+
+
+def drop(root):
+    """forget whatever the modules under `root` hold for a backward; a backward that still counts on it gets REPLACED"""
+    for m in root.modules():
+        if getattr(m, "_stamp", None) is not None or getattr(m, "_saved", None) is not None:
+            m._saved, m._stamp = None, next(_SERIALS)
+
+
+def once(backward):
+    """torch's once_differentiable for a hand-written backward, and strict: under create_graph=True (the engine then runs
+    backward with grad mode on) torch's decorator lets a gradient that is no function of anything through unless the
+    upstream gradient itself requires grad; here the call is refused, so a gradient penalty cannot silently be zero."""
+    inner = torch.autograd.function.once_differentiable(backward)
+
+    @functools.wraps(backward)
+    def wrapper(ctx, *args):
+        if torch.is_grad_enabled():
+            raise RuntimeError("trying to differentiate twice a function that was marked with @once_differentiable: %s is "
+                               "a hand-written kernel pass and builds no graph (create_graph=True is not supported)" %
+                               backward.__qualname__.split(".")[0])
+        return inner(ctx, *args)
+    return wrapper
 
 
 def _bias_grad(bias, dy, sink):
@@ -117,15 +228,18 @@ class _Bridge(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, cout, x, *params):
         xh = ops.nchw_to_nhwc(x)
-        yh = mod.fwd(xh, True)
+        ctx.serial = new_serial()
+        yh = mod.fwd(xh, ctx.serial)
         ctx.mod, ctx.cin, ctx.need_dx = mod, x.shape[1], x.requires_grad
         return ops.nhwc_to_nchw(yh, cout or yh.shape[3])
 
     @staticmethod
+    @once
     def backward(ctx, dy):
         mod = ctx.mod
+        claim(mod, ctx.serial)
         dyh = ops.nchw_to_nhwc(dy.contiguous())
-        sink = GradSink(getattr(mod, "_iswm_on_ready", None))
+        sink = GradSink(getattr(mod, "_iswm_on_ready", None), ctx.serial)
         dxh = mod.bwd(dyh, sink)
         dx = ops.nhwc_to_nchw(dxh, ctx.cin) if (ctx.need_dx and dxh is not None) else None
         return (None, None, dx) + (None,) * (len(ctx.needs_input_grad) - 3)
@@ -226,12 +340,11 @@ class Conv2d(HipModule, nn.Conv2d):
     def fwd(self, x, save, out=None):
         g = self.geometry(x)
         y, _, _ = ops.conv2d_fwd(x, self.weight_for(0), g, bias=self.bias_p(), out=out)
-        self._saved = (x, g) if save else None
+        keep(self, save, (x, g))
         return y
 
     def bwd(self, dy, sink, need_dx=True, dx=None, accumulate=False):
-        x, g = self._saved
-        self._saved = None
+        x, g = take(self, sink)
         _bias_grad(self.bias, dy, sink)
         self.write_wgrad(x, dy, g, sink)
         if not need_dx:
@@ -265,7 +378,7 @@ class DepthwiseConv2d(HipModule, nn.Conv2d):
     def fwd(self, x, save, out=None):
         g = self.geometry(x)
         y = ops.dwconv2d_fwd(x, self.weight.contiguous(), g, self.bias, out)
-        self._saved = (x, g) if save else None
+        keep(self, save, (x, g))
         return y
 
     def is_dw3x3(self):
@@ -278,13 +391,12 @@ class DepthwiseConv2d(HipModule, nn.Conv2d):
         statistics taken by the convolution's own launch"""
         g = self.geometry(x)
         y, partials, tiles = ops.dwconv3x3_fwd_stats(x, self.weight.contiguous(), g, want_stats)
-        self._saved = (x, g) if save else None
+        keep(self, save, (x, g))
         return y, partials, tiles
 
     def bwd_fused(self, dy, sink, need_dx=True, dx=None, accumulate=False):
         """backward of fwd_stats: data and weight gradient from one pass over dy and x"""
-        x, g = self._saved
-        self._saved = None
+        x, g = take(self, sink)
         need_dw, buf, tgt = self.weight.requires_grad, None, None
         if need_dw:
             buf = sink.target(self.weight)
@@ -299,8 +411,7 @@ class DepthwiseConv2d(HipModule, nn.Conv2d):
         return dx
 
     def bwd(self, dy, sink, need_dx=True, dx=None, accumulate=False):
-        x, g = self._saved
-        self._saved = None
+        x, g = take(self, sink)
         _bias_grad(self.bias, dy, sink)
         if self.weight.requires_grad:
             buf = sink.target(self.weight)
@@ -336,23 +447,22 @@ class Dropout(HipModule, nn.Dropout):
     def __init__(self, *a, **k):
         nn.Dropout.__init__(self, *a, **k)
         self._calls = 0
-        self._mask = None
+        self._saved = None
 
     def fwd(self, x, save):
         if not self.training or self.p == 0.0:
-            self._mask = None
+            keep(self, save, (None,))                   # the identity: no mask
             return x
         self._calls += 1
         y, mask = ops.dropout_fwd(x, self.p, torch.initial_seed() & 0x7FFFFFFFFFFFFFFF, self._calls)
-        self._mask = mask if save else None
+        keep(self, save, (mask,))
         return y
 
     def bwd(self, dy, sink):
-        if self._mask is None:
+        mask, = take(self, sink)
+        if mask is None:
             return dy
-        dx = ops.dropout_bwd(dy.contiguous(), self._mask, self.p)
-        self._mask = None
-        return dx
+        return ops.dropout_bwd(dy.contiguous(), mask, self.p)
 
 
 # ---------------------------------------------------------------------------------------
@@ -731,12 +841,11 @@ class HipSequential(HipModule, nn.Sequential):
             else:
                 x = s.conv.fwd(x, save)
                 ctxs.append(None)
-        self._saved = (st, ctxs) if save else None
+        keep(self, save, (st, ctxs))
         return x
 
     def bwd(self, dy, sink, need_dx=True, dx=None, accumulate=False):
-        st, ctxs = self._saved
-        self._saved = None
+        st, ctxs = take(self, sink)
         for k in range(len(st) - 1, -1, -1):
             s, c = st[k], ctxs[k]
             rest = (need_dx or k > 0, dx if k == 0 else None, accumulate and k == 0)

@@ -83,12 +83,11 @@ class InvertedResidual(_hip.HipModule):
             h, c = _hip.cba_fwd(s.conv, s.bn, s.act, h, save, residual=x if (last and self.use_res_connect) else None,
                                 out_fmt=fmt)
             ctxs.append(c)
-        self._saved = ctxs if save else None
+        _hip.keep(self, save, ctxs)
         return h
 
     def bwd(self, dout, sink):
-        ctxs = self._saved
-        self._saved = None
+        ctxs = _hip.take(self, sink)
         dres = None
         if self.use_res_connect:
             # no activation after the add: the gradient of the identity branch IS the incoming gradient (the last stage is asked

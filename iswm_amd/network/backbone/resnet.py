@@ -56,7 +56,7 @@ class Bottleneck(_hip.HipModule):
             identity, cd = _hip.cba_fwd(self.downsample[0], self.downsample[1], Act.NONE, x, save)
         # conv3 -> bn3 -> (+identity) -> relu in one fused elementwise pass (reference :110-118)
         out, c3 = _hip.cba_fwd(self.conv3, self.bn3, Act.RELU, o2, save, residual=identity)
-        self._saved = (c1, c2, c3, cd) if save else None
+        _hip.keep(self, save, (c1, c2, c3, cd))
         return out
 
     def bwd(self, dout, sink, need_dx=True, up=None, dx0=None):
@@ -65,8 +65,7 @@ class Bottleneck(_hip.HipModule):
         up: the bn3 stage context of the PREVIOUS block when this block's input gradient is consumed by that stage alone
         (identity blocks inside a layer): conv1's accumulating data gradient then applies that stage's ReLU pattern and takes
         its BatchNorm-backward sums (ops.BnStats.mask)"""
-        c1, c2, c3, cd = self._saved
-        self._saved = None
+        c1, c2, c3, cd = _hip.take(self, sink)
         # conv3's / conv2's data gradients are consumed by bn2's / bn1's backward alone: they take its reduction pass along
         d2, dres = _hip.cba_bwd(c3, dout, sink, up=c2)
         d1, _ = _hip.cba_bwd(c2, d2, sink, up=c1)
@@ -100,8 +99,9 @@ class _Layer(_hip.HipModule, nn.Sequential):
         blocks = list(self)
         for i in range(len(blocks) - 1, -1, -1):
             up = None
-            if i > 0 and blocks[i].downsample is None and blocks[i - 1]._saved is not None:
-                up = blocks[i - 1]._saved[2]            # the previous block's conv3 / bn3 / + identity / ReLU stage
+            if i > 0 and blocks[i].downsample is None:
+                prev = _hip.peek(blocks[i - 1], sink)   # (left in place: the previous block's own bwd takes it)
+                up = prev[2] if prev is not None else None      # its conv3 / bn3 / + identity / ReLU stage
             dy = blocks[i].bwd(dy, sink, up=up, dx0=dx0 if i == 0 else None)
         return dy
 
@@ -121,12 +121,11 @@ class MaxPool2d(_hip.HipModule, nn.MaxPool2d):
             _hip.POOL_RECORDER[self] = idx
         if _hip.CALIB_RECORDER is not None:
             _hip.CALIB_RECORDER.record(self, y)
-        self._saved = (idx, tuple(x.shape)) if save else None
+        _hip.keep(self, save, (idx, tuple(x.shape)))
         return y
 
     def bwd(self, dy, sink):
-        idx, shape = self._saved
-        self._saved = None
+        idx, shape = _hip.take(self, sink)
         return ops.maxpool_bwd(dy, idx, shape)
 
 

@@ -18,11 +18,13 @@ class _SegBridge(torch.autograd.Function):
         ctx.model = model
         ctx.need_dx = x.requires_grad
         ctx.cin = x.shape[1]
-        return model._fwd(x, True)
+        ctx.serial = _hip.new_serial()
+        return model._fwd(x, ctx.serial)
 
     @staticmethod
+    @_hip.once
     def backward(ctx, dlogits):
-        dx = ctx.model._bwd(dlogits.contiguous(), ctx.need_dx)
+        dx = ctx.model._bwd(dlogits, ctx.need_dx, ctx.serial)
         return (None, dx) + (None,) * (len(ctx.needs_input_grad) - 2)
 
 
@@ -89,15 +91,22 @@ class _SimpleSegmentationModel(nn.Module):
             raise
         if not save:
             pk.end()                                           # no backward will follow: retire the packed weights
-        self._saved = (tuple(yl.shape), c) if save else None
+        _hip.keep(self, save, (tuple(yl.shape), c))
         return yl
 
-    def _bwd(self, dlogits, need_dx):
-        (n, hl, wl, cp), cin = self._saved
-        self._saved = None
-        sink = _hip.GradSink(self._iswm_on_ready)
+    def _bwd(self, dlogits, need_dx, serial=None):
+        """serial: of the forward call this backward belongs to (_SegBridge's); refused before any launch when the modules no
+        longer hold that call's state (_hip.claim)"""
+        sink = _hip.GradSink(self._iswm_on_ready, serial)
+        if serial is not None:
+            try:
+                _hip.claim(self, serial)
+            except RuntimeError:
+                self._packer().end()                           # the packed weights of the call that will not finish
+                raise
+        (n, hl, wl, cp), cin = _hip.take(self, sink)
         try:
-            dyl = ops.bilinear_to_nchw_bwd(dlogits, hl, wl, cp)
+            dyl = ops.bilinear_to_nchw_bwd(dlogits.contiguous(), hl, wl, cp)
             dfeats = self.classifier.bwd(dyl, sink)
             if getattr(self, "_debug_keep_dfeats", False):
                 self._debug_dfeats = {k: v.clone() for k, v in dfeats.items()}
@@ -164,10 +173,11 @@ class IntermediateLayerGetter(nn.ModuleDict):
                 x = module.fwd(x, save)
             if name in self.return_layers:
                 out[self.return_layers[name]] = x
-        self._saved = stem_ctx if save else None
+        _hip.keep(self, save, (stem_ctx,))
         return out
 
     def bwd(self, dfeats, sink, need_dx=False):
+        stem_ctx, = _hip.take(self, sink)
         names = [n for n, _ in self.named_children()]
         inv = {v: k for k, v in self.return_layers.items()}
         tap = {inv[k]: g for k, g in dfeats.items() if g is not None}
@@ -180,7 +190,7 @@ class IntermediateLayerGetter(nn.ModuleDict):
             if name in ("relu", "bn1"):
                 continue
             if name == "conv1":
-                dy, _ = _hip.cba_bwd(self._saved, dy, sink, need_dx=need_dx)
+                dy, _ = _hip.cba_bwd(stem_ctx, dy, sink, need_dx=need_dx)
             else:
                 # a tapped feature right below this layer (low_level under layer2): the layer's first block accumulates its data
                 # gradient into the tap's gradient instead of a separate 800-MB add pass
@@ -192,7 +202,6 @@ class IntermediateLayerGetter(nn.ModuleDict):
                     dy = self[name].bwd(dy, sink, need_dx=need_dx)
                 else:
                     dy = self[name].bwd(dy, sink)
-        self._saved = None
         return dy
 
     def forward(self, x):

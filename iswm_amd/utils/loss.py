@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..network._hip import CONSUMED, once
 
 
 def _scalar(upstream):
@@ -28,6 +29,9 @@ def _weight_for(weight, inputs):
 
 
 class _LossFn(torch.autograd.Function):
+    """The one-pass criteria: the forward stores the unnormalised gradient and the backward rescales it IN PLACE, so it is
+    good for one backward; a second one through the same call (retain_graph) is refused, not handed a twice-scaled tensor."""
+
     @staticmethod
     def forward(ctx, logits, labels, weight, ignore_index, alpha, gamma, mode, group):
         loss, sums, grad = ops.loss_fwd(logits, labels, weight, ignore_index, alpha, gamma, mode)
@@ -44,11 +48,15 @@ class _LossFn(torch.autograd.Function):
                 dist.all_reduce(sums, group=group)
                 loss = (sums[0] / npix if mode == ops.MODE_FOCAL_MEAN else sums[0]).reshape(1)
         ctx.save_for_backward(grad, sums)
-        ctx.mode, ctx.npix = mode, npix
+        ctx.mode, ctx.npix, ctx.consumed = mode, npix, False
         return loss.reshape(())
 
     @staticmethod
+    @once
     def backward(ctx, upstream):
+        if ctx.consumed:
+            raise RuntimeError("%s: %s" % (("CrossEntropyLoss" if ctx.mode == ops.MODE_WCE else "FocalLoss"), CONSUMED))
+        ctx.consumed = True
         grad, sums = ctx.saved_tensors
         ops.loss_bwd_scale(grad, sums, _scalar(upstream), ctx.mode, ctx.npix)
         return grad, None, None, None, None, None, None, None
@@ -119,6 +127,7 @@ class _OverlapLossFn(torch.autograd.Function):
         return loss.reshape(())
 
     @staticmethod
+    @once
     def backward(ctx, upstream):
         logits, labels, weight, coef = ctx.saved_tensors
         grad = ops.overlap_loss_bwd(logits, labels, weight, ctx.ignore_index, coef, _scalar(upstream))
@@ -183,6 +192,7 @@ class _OhemLossFn(torch.autograd.Function):
         return out[0].clone(), sums, nu
 
     @staticmethod
+    @once
     def backward(ctx, upstream, _sums, _nu):
         logits, labels, weight, keys, nu, out = ctx.saved_tensors
         grad = ops.ohem_bwd(logits, labels, weight, keys, nu, out, _scalar(upstream))
@@ -240,6 +250,7 @@ class _LovaszLossFn(torch.autograd.Function):
         return out[0].clone(), sums
 
     @staticmethod
+    @once
     def backward(ctx, upstream, _sums):
         logits, labels, weight, m, out = ctx.saved_tensors
         grad = ops.lovasz_bwd(logits, labels, weight, ctx.ignore_index, ctx.classes, m, out, _scalar(upstream))
