@@ -1,6 +1,7 @@
 // Declarations shared by all convolution kernels and their launchers: the argument structs (ConvArgs, BnFuse, PatchArgs),
 // the row -> pixel maps, the weight packing of the planes kernels, the tile choices and launch entry points of every family
-// -- conv_mfma.hip (fp32 kernels), conv_mfma_u.hip (tap-uniform fast path), conv_mfma_x6*.hip (round-1 bf16x6),
+// -- conv_mfma.hip (fp32 kernels), conv_mfma_u.hip (tap-uniform fast path), conv_mfma_x6*.hip (round-1 bf16x6; the row map, tap
+// gather, chunk multiply and epilogue these three share are in conv_tile32.h),
 // conv_mfma_pl2*.hip (planes kernels; their device-side pieces are in conv_pl2_stage.h), conv_stem.hip, conv_wgrad_pl.hip
 // (planes weight gradient; conv_wgrad_frag.h holds the fragment read and multiply it shares with the stem's weight gradient)
 // -- and the weight-gradient plan.  conv_api.hip is the host-only file over them: the C entry

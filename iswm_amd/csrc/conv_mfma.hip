@@ -25,7 +25,7 @@
 //   * wgrad flattens (tap, cin) into the GEMM N axis and splits the pixel (K) axis across
 //     workgroups into slabs that a second kernel sums in a fixed order (bit-reproducible).
 // The C entry points that choose between these kernels and the other families are in conv_api.hip.
-#include "conv_common.h"
+#include "conv_tile32.h"
 
 namespace iswm {
 
@@ -48,23 +48,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_fwd(const ConvArgs a) {
     const int m0 = mt * BM, n0 = nt * BN;
     const int q = t & 7, r0 = t >> 3;
 
-    const int HoWo = a.Ho * a.Wo;
     int ihb[4], iwb[4], pb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int m = m0 + r0 + 32 * j;
-        if (m < a.M) {
-            int n = m / HoWo, rem = m - n * HoWo;
-            int oh = rem / a.Wo, ow = rem - oh * a.Wo;
-            ihb[j] = oh * a.stride - a.pad;
-            iwb[j] = ow * a.stride - a.pad;
-            pb[j] = n * a.H * a.W;
-        } else {
-            ihb[j] = -(1 << 28);
-            iwb[j] = 0;
-            pb[j] = 0;
-        }
-    }
+    row_bases<false>(a, m0 + r0, false, ihb, iwb, pb);
     const int Cin4 = a.Cin >> 2, K4 = a.Ktot >> 2;
     const float* wrow[BROWS];
     bool wok[BROWS];
@@ -103,12 +88,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_fwd(const ConvArgs a) {
     };
 
     f32x16 acc[2][NB];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    tile_clear(acc);
 
     const int nK = (a.Ktot + 31) >> 5;
     gload(0);
@@ -120,84 +100,13 @@ __global__ __launch_bounds__(256, 2) void k_conv_fwd(const ConvArgs a) {
         if (more) gload(kc + 1);
         const float* Ab = &As[(cur * BM + wm * 64 + li) * KC_PITCH + lh * 4];
         const float* Bb = &Bs[(cur * BN + wn * (BN / 2) + li) * KC_PITCH + lh * 4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float af[2][4], bf[NB][4];
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-                *reinterpret_cast<float4*>(af[mb]) =
-                    *reinterpret_cast<const float4*>(Ab + mb * 32 * KC_PITCH + g * 8);
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-                *reinterpret_cast<float4*>(bf[nb]) =
-                    *reinterpret_cast<const float4*>(Bb + nb * 32 * KC_PITCH + g * 8);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[mb][nb] = mfma32(af[mb][j], bf[nb][j], acc[mb][nb]);
-        }
+        mma_chunk_kc(Ab, Bb, acc);
         if (more) lstore(cur ^ 1);
         __syncthreads();
     }
 
-    // ---- epilogue: C/D map of the 32x32 tile: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int col = n0 + wn * (BN / 2) + nb * 32 + li;
-        const bool cok = col < a.Cout;
-        const float bv = (a.bias != nullptr && cok) ? a.bias[col] : 0.f;
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int row = m0 + wm * 64 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (cok && row < a.M) a.y[(size_t)row * a.ldy + col] = acc[mb][nb][r] + bv;
-            }
-        }
-    }
-    if (a.stats != nullptr) {
-        // Per-tile BatchNorm statistics, numerically centred: column sum S_t first, then the sum of
-        // squared deviations from the TILE mean (M2_t).  iswm_bn_finalize merges tiles with the
-        // pairwise (Chan) update in double, so the batch variance never suffers the E[x^2]-mean^2
-        // cancellation -- this is what keeps 100 stacked train-mode BN layers within 1e-3 of the CPU.
-        float* red = smem;  // [4][BN]: sum(wm=0), sum(wm=1), M2(wm=0), M2(wm=1)
-        const int cnt = min(BM, a.M - m0);
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            float s = 0.f;   // rows past M were staged as zeros, so they add nothing
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s += acc[mb][nb][r];
-            s += __shfl_xor(s, 32);
-            if (lh == 0) red[wm * BN + wn * (BN / 2) + nb * 32 + li] = s;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const int c = wn * (BN / 2) + nb * 32 + li;
-            const float mean = (red[c] + red[BN + c]) / (float)cnt;
-            float q = 0.f;
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    int row = m0 + wm * 64 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    float dv = acc[mb][nb][r] - mean;
-                    q += row < a.M ? dv * dv : 0.f;
-                }
-            q += __shfl_xor(q, 32);
-            if (lh == 0) red[(2 + wm) * BN + c] = q;
-        }
-        __syncthreads();
-        if (t < BN && n0 + t < a.Cout) {
-            a.stats[(size_t)mt * a.Cout + n0 + t] = red[t] + red[BN + t];
-            a.stats[(size_t)(a.MT + mt) * a.Cout + n0 + t] = red[2 * BN + t] + red[3 * BN + t];
-        }
-    }
+    tile_store<BM, BN, false>(a, acc, m0, n0);
+    if (a.stats != nullptr) tile_stats<BM, BN>(a, acc, smem, mt, n0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -224,23 +133,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_dgrad(const ConvArgs a) {
     const int bq = t % BQ, bk0 = t / BQ;
 
     // rows are INPUT pixels here: a.H/a.W input dims, a.Ho/a.Wo the dims of dy
-    const int HW = a.H * a.W;
     int thb[4], twb[4], pb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int m = m0 + r0 + 32 * j;
-        if (m < a.M) {
-            int n = m / HW, rem = m - n * HW;
-            int ih = rem / a.W, iw = rem - ih * a.W;
-            thb[j] = ih + a.pad;
-            twb[j] = iw + a.pad;
-            pb[j] = n * a.Ho * a.Wo;
-        } else {
-            thb[j] = -(1 << 28);
-            twb[j] = 0;
-            pb[j] = 0;
-        }
-    }
+    row_bases<true>(a, m0 + r0, false, thb, twb, pb);
     const int Co4 = a.Cout >> 2, K4 = a.Ktot >> 2;
     const int taps = a.KH * a.KW;
     const bool nok = n0 + bq * 4 < a.Cin;
@@ -285,12 +179,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_dgrad(const ConvArgs a) {
     };
 
     f32x16 acc[2][NB];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    tile_clear(acc);
 
     const int nK = (a.Ktot + 31) >> 5;
     gload(0);
@@ -302,51 +191,17 @@ __global__ __launch_bounds__(256, 2) void k_conv_dgrad(const ConvArgs a) {
         if (more) gload(kc + 1);
         const float* Ab = &As[(cur * BM + wm * 64 + li) * KC_PITCH + lh * 4];
         const float* Bb = &Bs[(cur * 32 + lh * 4) * BN + wn * (BN / 2) + li];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float af[2][4], bf[NB][4];
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-                *reinterpret_cast<float4*>(af[mb]) =
-                    *reinterpret_cast<const float4*>(Ab + mb * 32 * KC_PITCH + g * 8);
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) bf[nb][j] = Bb[(g * 8 + j) * BN + nb * 32];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[mb][nb] = mfma32(af[mb][j], bf[nb][j], acc[mb][nb]);
-        }
+        mma_chunk_rc<BN>(Ab, Bb, acc);
         if (more) lstore(cur ^ 1);
         __syncthreads();
     }
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int col = n0 + wn * (BN / 2) + nb * 32 + li;
-        const bool cok = col < a.Cin;
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int row = m0 + wm * 64 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (cok && row < a.M) {
-                    float* o = &a.y[(size_t)row * a.ldy + col];
-                    *o = a.accumulate ? *o + acc[mb][nb][r] : acc[mb][nb][r];
-                }
-            }
-    }
+    tile_store<BM, BN, true>(a, acc, m0, n0);
 }
 
 // ------------------------------------------------------------------------------------------
 // wgrad:  dw[co, j] = sum_p dy[p, co] * xG[p, j],  j = (kh, kw, ci) flattened, p = (n, oh, ow)
 // Both operands row-contiguous; the pixel axis is split across blockIdx.y into slabs.
 // ------------------------------------------------------------------------------------------
-static __device__ __attribute__((aligned(16))) float g_zero_row_w[64];   // target of out-of-bounds rows
-
 // MODE 0: any geometry.  MODE 1: stride 1 and Ho == H, Wo == W ("same" convs: every 3x3 of the net
 // except the two strided ones) -- the gathered pixel of output pixel p is p + dh*W + dw, so addresses
 // advance by a constant and only the bounds test needs (oh, ow).  MODE 2: 1x1 stride 1 -- no bounds.
@@ -456,7 +311,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(const ConvArgs a) {
     float4 ra[APASS], rb[BPASS];
     // All loads are unconditional: rows past the end of the split / outside the image read the zero row
     // (B side), and the A side then only needs a valid address (0 x finite = 0), so it clamps its pixel.
-    const float* abase = aok ? a.y + m0 + aq * 4 : g_zero_row_w;
+    const float* abase = aok ? a.y + m0 + aq * 4 : g_zero_row;
     const int a_ld = aok ? a.ldy : 0;
     const int shift = dh * a.W + dw;     // MODE 1/2: input pixel = output pixel + shift
     auto gload = [&](int kc) {
@@ -481,7 +336,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(const ConvArgs a) {
                 ok = ok && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
                 src = a.x + (size_t)((bn_[j] * a.H + ih) * a.W + iw) * a.ldx + c4 * 4;
             }
-            rb[j] = ldg4(ok ? src : g_zero_row_w);
+            rb[j] = ldg4(ok ? src : g_zero_row);
         }
     };
     auto lstore = [&](int buf) {

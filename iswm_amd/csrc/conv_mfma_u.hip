@@ -15,11 +15,9 @@
 // MFMA scheme, LDS layouts and epilogues are those of conv_mfma.hip.
 #include <stdlib.h>
 
-#include "conv_common.h"
+#include "conv_tile32.h"
 
 namespace iswm {
-
-__device__ __attribute__((aligned(16))) float g_zero_row[64];   // zero-initialised: target of padded rows
 
 template <int BM, int BN>
 struct TileCfg {
@@ -48,23 +46,8 @@ __global__ __launch_bounds__(256, (TileCfg<BM, BN>::OCC)) void k_conv_fwd_u(cons
     const int m0 = mt * BM, n0 = nt * BN;
     const int q = t & 7, r0 = t >> 3;
 
-    const int HoWo = a.Ho * a.Wo;
-    int ihb[AR], iwb[AR], pb[AR];
-#pragma unroll
-    for (int j = 0; j < AR; ++j) {
-        int m = m0 + r0 + 32 * j;
-        if (m < a.M) {
-            int n = m / HoWo, rem = m - n * HoWo;
-            int oh = rem / a.Wo, ow = rem - oh * a.Wo;
-            ihb[j] = oh * a.stride - a.pad;
-            iwb[j] = ow * a.stride - a.pad;
-            pb[j] = n * a.H * a.W;
-        } else {
-            ihb[j] = -(1 << 28);
-            iwb[j] = 0;
-            pb[j] = 0;
-        }
-    }
+    TapGather<false, AR> ga;
+    ga.init(a, m0 + r0, false);
     const float* wbase[BR];
     bool wok[BR];
 #pragma unroll
@@ -73,50 +56,19 @@ __global__ __launch_bounds__(256, (TileCfg<BM, BN>::OCC)) void k_conv_fwd_u(cons
         wok[j] = n < a.Cout;
         wbase[j] = a.w + (size_t)(wok[j] ? n : 0) * a.Ktot + q * 4;
     }
-    const int taps = a.KH * a.KW;
-    const int nCC = a.Cin >> 5;
-
-    const float* aptr[AR];
-    int astep[AR];
     const float* bptr[BR];
     int bstep[BR];
-    // derive this thread's gather pointers for one tap; returns whether ANY row of the tile is in bounds
-    auto setup_tap = [&](int tap) -> bool {
-        const int kh = tap / a.KW, kw = tap - kh * a.KW;
-        const int dh = kh * a.dil, dw = kw * a.dil;
-        int any = 0;
-#pragma unroll
-        for (int j = 0; j < AR; ++j) {
-            int ih = ihb[j] + dh, iw = iwb[j] + dw;
-            bool ok = (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
-            aptr[j] = ok ? a.x + (size_t)(pb[j] + ih * a.W + iw) * a.ldx + q * 4 : g_zero_row + q * 4;
-            astep[j] = ok ? 32 : 0;
-            any |= ok;
-        }
+    auto setup_b = [&](int tap) {
 #pragma unroll
         for (int j = 0; j < BR; ++j) {
             bptr[j] = wok[j] ? wbase[j] + (size_t)tap * a.Cin : g_zero_row + q * 4;
             bstep[j] = wok[j] ? 32 : 0;
         }
-        return __syncthreads_or(any) != 0;
-    };
-    int tap = -1, cc = nCC - 1;
-    auto next = [&]() -> bool {   // advance to the next (tap, channel chunk) that has work; block-uniform
-        if (++cc < nCC) return true;
-        cc = 0;
-        do {
-            if (++tap >= taps) return false;
-        } while (!setup_tap(tap));
-        return true;
     };
 
     float4 ra[AR], rb[BR];
     auto gload = [&]() {
-#pragma unroll
-        for (int j = 0; j < AR; ++j) {
-            ra[j] = ldg4(aptr[j]);
-            aptr[j] += astep[j];
-        }
+        ga.load(ra);
 #pragma unroll
         for (int j = 0; j < BR; ++j) {
             rb[j] = ldg4(bptr[j]);
@@ -133,14 +85,9 @@ __global__ __launch_bounds__(256, (TileCfg<BM, BN>::OCC)) void k_conv_fwd_u(cons
     };
 
     f32x16 acc[MB][NB];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    tile_clear(acc);
 
-    bool more = next();
+    bool more = ga.next(a, q, setup_b);
     if (more) {
         gload();
         lstore(0);
@@ -148,87 +95,19 @@ __global__ __launch_bounds__(256, (TileCfg<BM, BN>::OCC)) void k_conv_fwd_u(cons
     __syncthreads();
     int cur = 0;
     while (more) {
-        const bool more2 = next();
+        const bool more2 = ga.next(a, q, setup_b);
         if (more2) gload();
         const float* Ab = &As[(cur * BM + wm * (BM / 2) + li) * KC_PITCH + lh * 4];
         const float* Bb = &Bs[(cur * BN + wn * (BN / 2) + li) * KC_PITCH + lh * 4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float af[MB][4], bf[NB][4];
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb)
-                *reinterpret_cast<float4*>(af[mb]) =
-                    *reinterpret_cast<const float4*>(Ab + mb * 32 * KC_PITCH + g * 8);
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-                *reinterpret_cast<float4*>(bf[nb]) =
-                    *reinterpret_cast<const float4*>(Bb + nb * 32 * KC_PITCH + g * 8);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[mb][nb] = mfma32(af[mb][j], bf[nb][j], acc[mb][nb]);
-        }
+        mma_chunk_kc(Ab, Bb, acc);
         if (more2) lstore(cur ^ 1);
         __syncthreads();
         cur ^= 1;
         more = more2;
     }
 
-    // ---- epilogue (as conv_mfma.hip): C/D map col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int col = n0 + wn * (BN / 2) + nb * 32 + li;
-        const bool cok = col < a.Cout;
-        const float bv = (a.bias != nullptr && cok) ? a.bias[col] : 0.f;
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int row = m0 + wm * (BM / 2) + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (cok && row < a.M) a.y[(size_t)row * a.ldy + col] = acc[mb][nb][r] + bv;
-            }
-    }
-    if (a.stats != nullptr) {
-        // per-tile BatchNorm statistics {S_t, M2_t about the tile mean}; tiles are BM rows here, so the
-        // host passes tile_rows = BM to iswm_bn_finalize
-        float* red = smem;  // [4][BN]
-        const int cnt = min(BM, a.M - m0);
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            float s = 0.f;
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s += acc[mb][nb][r];
-            s += __shfl_xor(s, 32);
-            if (lh == 0) red[wm * BN + wn * (BN / 2) + nb * 32 + li] = s;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const int c = wn * (BN / 2) + nb * 32 + li;
-            const float mean = (red[c] + red[BN + c]) / (float)cnt;
-            float qv = 0.f;
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    int row = m0 + wm * (BM / 2) + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    float dv = acc[mb][nb][r] - mean;
-                    qv += row < a.M ? dv * dv : 0.f;
-                }
-            qv += __shfl_xor(qv, 32);
-            if (lh == 0) red[(2 + wm) * BN + c] = qv;
-        }
-        __syncthreads();
-        if (t < BN && n0 + t < a.Cout) {
-            a.stats[(size_t)mt * a.Cout + n0 + t] = red[t] + red[BN + t];
-            a.stats[(size_t)(a.MT + mt) * a.Cout + n0 + t] = red[2 * BN + t] + red[3 * BN + t];
-        }
-    }
+    tile_store<BM, BN, false>(a, acc, m0, n0);
+    if (a.stats != nullptr) tile_stats<BM, BN>(a, acc, smem, mt, n0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -251,73 +130,22 @@ __global__ __launch_bounds__(256, (TileCfg<BM, BN>::OCC)) void k_conv_dgrad_u(co
     const int q = t & 7, r0 = t >> 3;
     const int bq = t % BQ, bk0 = t / BQ;
 
-    const int HW = a.H * a.W;
-    int thb[AR], twb[AR], pb[AR];
-#pragma unroll
-    for (int j = 0; j < AR; ++j) {
-        int m = m0 + r0 + 32 * j;
-        if (m < a.M) {
-            int n = m / HW, rem = m - n * HW;
-            int ih = rem / a.W, iw = rem - ih * a.W;
-            thb[j] = ih + a.pad;
-            twb[j] = iw + a.pad;
-            pb[j] = n * a.Ho * a.Wo;
-        } else {
-            thb[j] = -(1 << 28);
-            twb[j] = 0;
-            pb[j] = 0;
-        }
-    }
-    const int taps = a.KH * a.KW;
-    const int nCC = a.Cout >> 5;
+    TapGather<true, AR> ga;
+    ga.init(a, m0 + r0, false);
     const bool nok = n0 + bq * 4 < a.Cin;
-    const size_t bchunk = (size_t)32 * taps * a.Cin;   // weight floats between consecutive cout chunks
+    const size_t bchunk = (size_t)32 * ga.taps * a.Cin;   // weight floats between consecutive cout chunks
 
-    const float* aptr[AR];
-    int astep[AR];
     const float* bptr[BPASS];
-    auto setup_tap = [&](int tap) -> bool {
-        const int kh = tap / a.KW, kw = tap - kh * a.KW;
-        const int dh = kh * a.dil, dw = kw * a.dil;
-        int any = 0;
-#pragma unroll
-        for (int j = 0; j < AR; ++j) {
-            int th = thb[j] - dh, tw = twb[j] - dw;
-            int oh = th, ow = tw;
-            bool ok = th >= 0 && tw >= 0;
-            if (a.stride != 1) {
-                oh = th / a.stride;
-                ow = tw / a.stride;
-                ok = ok && (oh * a.stride == th) && (ow * a.stride == tw);
-            }
-            ok = ok && oh < a.Ho && ow < a.Wo;
-            aptr[j] = ok ? a.x + (size_t)(pb[j] + oh * a.Wo + ow) * a.ldx + q * 4 : g_zero_row + q * 4;
-            astep[j] = ok ? 32 : 0;
-            any |= ok;
-        }
+    auto setup_b = [&](int tap) {
 #pragma unroll
         for (int j = 0; j < BPASS; ++j)
-            bptr[j] = nok ? a.w + ((size_t)(bk0 + BKR * j) * taps + tap) * a.Cin + n0 + bq * 4 : g_zero_row;
-        return __syncthreads_or(any) != 0;
+            bptr[j] = nok ? a.w + ((size_t)(bk0 + BKR * j) * ga.taps + tap) * a.Cin + n0 + bq * 4 : g_zero_row;
     };
     const size_t bstep = nok ? bchunk : 0;
-    int tap = -1, cc = nCC - 1;
-    auto next = [&]() -> bool {
-        if (++cc < nCC) return true;
-        cc = 0;
-        do {
-            if (++tap >= taps) return false;
-        } while (!setup_tap(tap));
-        return true;
-    };
 
     float4 ra[AR], rb[BPASS];
     auto gload = [&]() {
-#pragma unroll
-        for (int j = 0; j < AR; ++j) {
-            ra[j] = ldg4(aptr[j]);
-            aptr[j] += astep[j];
-        }
+        ga.load(ra);
 #pragma unroll
         for (int j = 0; j < BPASS; ++j) {
             rb[j] = ldg4(bptr[j]);
@@ -334,14 +162,9 @@ __global__ __launch_bounds__(256, (TileCfg<BM, BN>::OCC)) void k_conv_dgrad_u(co
     };
 
     f32x16 acc[MB][NB];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    tile_clear(acc);
 
-    bool more = next();
+    bool more = ga.next(a, q, setup_b);
     if (more) {
         gload();
         lstore(0);
@@ -349,49 +172,17 @@ __global__ __launch_bounds__(256, (TileCfg<BM, BN>::OCC)) void k_conv_dgrad_u(co
     __syncthreads();
     int cur = 0;
     while (more) {
-        const bool more2 = next();
+        const bool more2 = ga.next(a, q, setup_b);
         if (more2) gload();
         const float* Ab = &As[(cur * BM + wm * (BM / 2) + li) * KC_PITCH + lh * 4];
         const float* Bb = &Bs[(cur * 32 + lh * 4) * BN + wn * (BN / 2) + li];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float af[MB][4], bf[NB][4];
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb)
-                *reinterpret_cast<float4*>(af[mb]) =
-                    *reinterpret_cast<const float4*>(Ab + mb * 32 * KC_PITCH + g * 8);
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) bf[nb][j] = Bb[(g * 8 + j) * BN + nb * 32];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[mb][nb] = mfma32(af[mb][j], bf[nb][j], acc[mb][nb]);
-        }
+        mma_chunk_rc<BN>(Ab, Bb, acc);
         if (more2) lstore(cur ^ 1);
         __syncthreads();
         cur ^= 1;
         more = more2;
     }
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int col = n0 + wn * (BN / 2) + nb * 32 + li;
-        const bool cok = col < a.Cin;
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int row = m0 + wm * (BM / 2) + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (cok && row < a.M) {
-                    float* o = &a.y[(size_t)row * a.ldy + col];
-                    *o = a.accumulate ? *o + acc[mb][nb][r] : acc[mb][nb][r];
-                }
-            }
-    }
+    tile_store<BM, BN, true>(a, acc, m0, n0);
 }
 
 // Tile choice: a CU works through ceil(tiles / 256) tiles (co-resident workgroups share its SIMDs), so

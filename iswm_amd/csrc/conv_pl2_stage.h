@@ -19,7 +19,7 @@
 
 namespace iswm {
 
-// one definition per including translation unit (the _pl2 suffix: conv_mfma_u.hip owns the name g_zero_row)
+// one definition per including translation unit (the _pl2 suffix: conv_tile32.h owns the name g_zero_row)
 static __device__ __attribute__((aligned(128))) unsigned short g_zero_row_pl2[64];   // 128 B of zeros
 static __device__ float4 g_dump_pl2[64];         // where an epilogue's out-of-range lanes store (never read)
 

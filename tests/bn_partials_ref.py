@@ -689,6 +689,16 @@ FLOOR = {
     "x6_1x1.identity": 9.8e-08,
     "x6_m128.M2": 2.0e-06,
     "x6_m128.S": 6.3e-07,
+    "bf16_m128.M2": 2.0e-06,
+    "bf16_m128.S": 6.0e-07,
+    "f32_u_fwd128.M2": 1.9e-06,
+    "f32_u_fwd128.S": 9.0e-07,
+    "x6w_1x1.M2": 1.0e-06,
+    "x6w_1x1.S": 4.0e-07,
+    "x6w_m128.M2": 1.9e-06,
+    "x6w_m128.S": 5.9e-07,
+    "x6w_wide.M2": 1.9e-06,
+    "x6w_wide.S": 7.6e-07,
     "x6_patch.mean": 4.0e-07,
     "x6_patch.var": 7.0e-07,
     "x6_patch_d2.mean": 2.1e-07,

@@ -21,6 +21,7 @@ from tests.util import rel_err
 # ---- cases ---------------------------------------------------------------------------------------------------------------
 # mode: "pl"   conv math bf16x6, operands pre-split into planes where the network would (gathered channels % 64 == 0)
 #       "x6"   conv math bf16x6, fp32 operands (the planes-off data path: packed-weight kernels, k_conv_wgrad, the stem)
+#       "x6w"  the same with ops._USE_PACKED off: the plain-weight arm of k_conv_x6 (weights split in the kernel)
 #       "f32"  conv math 0: the exact-fp32 MFMA kernels
 #       "bf16" conv math 2 on fp32 operands, "bf16pl" on one-plane operands: ONE bf16 MFMA per product; the restatement runs on
 #              operands rounded to nearest-even bf16
@@ -138,6 +139,12 @@ ROUTES = [
     _r("x6_patch_d2", "x6", (1, 24, 26, 32, 32, 3, 1, 2, 2), "k_conv_x6_patch<false, 3>", "k_conv_x6_patch<true, 3>",
        "k_conv_wgrad<64, 64, 1, true, 3>"),
     _r("x6_m128", "x6", (1, 79, 79, 64, 512, 1, 1, 0, 1), fwd="k_conv_x6<128, 64, false, true, 3>", sub=8),
+    #    the plain-weight arm (ops._USE_PACKED off) in its four tiles: 64 x 64 both directions, 128 x 64 forward and data gradient,
+    #    128 x 128 forward (M >= 131 072 and K >= 1024: 3 x 3 x 128 = 1152, past what a dense case can see -- NO_DENSE)
+    _r("x6w_1x1", "x6w", (5, 7, 11, 64, 128, 1, 1, 0, 1), "k_conv_x6<64, 64, false, false, 3>", "k_conv_x6<64, 64, true, false, 3>"),
+    _r("x6w_m128", "x6w", (1, 79, 79, 64, 512, 1, 1, 0, 1), fwd="k_conv_x6<128, 64, false, false, 3>", sub=8),
+    _r("x6w_dg128", "x6w", (1, 221, 222, 16, 96, 1, 1, 0, 1), dgrad="k_conv_x6<128, 64, true, false, 3>", sub=8),
+    _r("x6w_wide", "x6w", (1, 362, 363, 128, 128, 3, 1, 1, 1), fwd="k_conv_x6<128, 128, false, false, 3>", sub=8),
     _r("stem_even", "x6", (1, 38, 38, 4, 64, 7, 2, 3, 1), fwd="k_stem_fwd<6>", wgrad="k_stem_wgrad"),
     _r("stem_odd", "x6", (1, 37, 41, 4, 64, 7, 2, 3, 1), fwd="k_stem_fwd<6>", wgrad="k_stem_wgrad"),
     # -- conv math 0: the _u kernels (K a multiple of 32) and the general-K kernels in their narrow and wide tiles
@@ -145,13 +152,17 @@ ROUTES = [
        "k_conv_wgrad<64, 64, 2, false, 3>"),
     _r("f32_u_s2", "f32", (1, 13, 13, 96, 160, 3, 2, 1, 1), "k_conv_fwd_u<64, 64>", "k_conv_dgrad_u<64, 64>",
        "k_conv_wgrad<64, 64, 0, false, 3>"),
-    _r("f32_u_m128", "f32", (1, 128, 130, 64, 64, 1, 1, 0, 1), fwd="k_conv_fwd_u<128, 64>", sub=8),
+    _r("f32_u_m128", "f32", (1, 128, 130, 64, 64, 1, 1, 0, 1), fwd="k_conv_fwd_u<128, 64>", dgrad="k_conv_dgrad_u<128, 64>", sub=8),
+    _r("f32_u_fwd128", "f32", (1, 79, 79, 64, 512, 1, 1, 0, 1), fwd="k_conv_fwd_u<128, 128>", sub=8),
+    _r("f32_u_dg128", "f32", (1, 128, 128, 256, 64, 1, 1, 0, 1), dgrad="k_conv_dgrad_u<128, 128>", sub=8),
     _r("f32_narrow", "f32", (1, 13, 13, 48, 48, 3, 1, 1, 1), "k_conv_fwd<64>", "k_conv_dgrad<64>", "k_conv_wgrad<64, 64, 1, false, 3>"),
     _r("f32_wide_fwd", "f32", (1, 128, 129, 48, 128, 1, 1, 0, 1), fwd="k_conv_fwd<128>", sub=8),
     _r("f32_wide_dgrad", "f32", (1, 128, 129, 128, 48, 1, 1, 0, 1), dgrad="k_conv_dgrad<128>", sub=8),
     # -- the one-plane bf16 mode
     _r("bf16_1x1", "bf16", (5, 7, 11, 64, 128, 1, 1, 0, 1), "k_conv_x6<64, 64, false, true, 1>", "k_conv_x6<64, 64, true, true, 1>",
        "k_conv_wgrad<64, 64, 2, true, 1>"),
+    _r("bf16_m128", "bf16", (1, 79, 79, 64, 512, 1, 1, 0, 1), fwd="k_conv_x6<128, 64, false, true, 1>", sub=8),
+    _r("bf16_dg128", "bf16", (1, 221, 222, 16, 96, 1, 1, 0, 1), dgrad="k_conv_x6<128, 64, true, true, 1>", sub=8),
     _r("bf16_patch", "bf16", (1, 10, 12, 64, 64, 3, 1, 1, 1), "k_conv_x6_patch<false, 1>", "k_conv_x6_patch<true, 1>",
        "k_conv_wgrad<64, 64, 1, true, 1>"),
     _r("bf16_pl", "bf16pl", (1, 9, 15, 128, 128, 3, 1, 1, 1), "k_conv_pl2<8, 1, 1, false>", "k_conv_pl2<8, 1, 1, true>",
@@ -171,10 +182,10 @@ BENCH_MOBILENET = collections.OrderedDict(
 # routes whose dense K is too long for the bound to see a lost term (5 x 5 x 64 = 1600; a 3 x 3 on the wide tiles): they run the
 # exact-integer and the stage-isolating kinds only (a dense 5 x 5 has K >= 800 on any bf16x6 kernel, where torch's floor is
 # 8e-7 .. 9.5e-7 and the weakest single-term mutant 2.4 x the bound)
-NO_DENSE = ("pl_5x5", "pl_wide3")
+NO_DENSE = ("pl_5x5", "pl_wide3", "x6w_wide")
 SLICE_ROUTES = ["pl_3x3", "pl_narrow", "pl_s2_1x1", "x6_patch", "x6_1x1", "f32_u", "bf16_pl"]     # bias + channel slices of wider buffers
 
-MATH = {"pl": 1, "x6": 1, "f32": 0, "bf16": 2, "bf16pl": 2}
+MATH = {"pl": 1, "x6": 1, "x6w": 1, "f32": 0, "bf16": 2, "bf16pl": 2}
 QTY = {"fwd": ("y",), "dgrad": ("dx", "dx_acc"), "wgrad": ("dw",)}
 
 
@@ -482,14 +493,17 @@ KIND = {"iswm_conv2d_fwd": 0, "iswm_conv2d_dgrad": 1, "iswm_conv2d_dgrad_wt": 1,
 
 @contextlib.contextmanager
 def conv_math(rt):
-    from iswm_amd import _lib
+    """the route's conv math (and, for mode "x6w", ops._USE_PACKED off) while the block runs"""
+    from iswm_amd import _lib, ops
     lib = _lib.load()
-    old = lib.iswm_get_conv_math()
+    old, packed = lib.iswm_get_conv_math(), ops._USE_PACKED
     lib.iswm_set_conv_math(MATH[rt.mode])
+    ops._USE_PACKED = rt.mode != "x6w"
     try:
         yield lib
     finally:
         lib.iswm_set_conv_math(old)
+        ops._USE_PACKED = packed
 
 
 def planes_operand(rt, c):
@@ -519,16 +533,17 @@ def planned(rt):
     with conv_math(rt) as lib:
         d = desc(rt)
         ref = ctypes.byref(d)
+        packed = lambda kind: rt.mode != "x6w" and lib.iswm_conv2d_packed_weight_bytes(ref, kind)      # as ops._packed_bytes
         if "fwd" in rt.names:
             if planes_operand(rt, cin) and lib.iswm_conv2d_pl2_weight_bytes(ref, 0):
                 e = "iswm_conv2d_fwd_pl2"
             else:
-                e = "iswm_conv2d_fwd_packed" if lib.iswm_conv2d_packed_weight_bytes(ref, 0) else "iswm_conv2d_fwd"
+                e = "iswm_conv2d_fwd_packed" if packed(0) else "iswm_conv2d_fwd"
             out["fwd"] = (e, kernel_name(lib, d, KIND[e]))
         if "dgrad" in rt.names:
             if planes_operand(rt, cout) and lib.iswm_conv2d_pl2_weight_bytes(ref, 1):
                 e = "iswm_conv2d_dgrad_pl2"
-            elif lib.iswm_conv2d_packed_weight_bytes(ref, 1):
+            elif packed(1):
                 e = "iswm_conv2d_dgrad_packed"
             else:
                 e = "iswm_conv2d_dgrad_wt" if lib.iswm_conv2d_dgrad_wants_wt(ref) else "iswm_conv2d_dgrad"
@@ -842,6 +857,21 @@ FLOOR = {
     "f32_u_s2.dx_acc": 3.8e-07,
     "f32_u_s2.dw": 2.5e-07,
     "f32_u_m128.y": 3.6e-07,
+    "f32_u_m128.dx": 3.0e-07,
+    "f32_u_m128.dx_acc": 2.0e-07,
+    "f32_u_fwd128.y": 2.9e-07,
+    "f32_u_dg128.dx": 3.1e-07,
+    "f32_u_dg128.dx_acc": 2.1e-07,
+    "bf16_m128.y": 1.4e-07,
+    "bf16_dg128.dx": 2.0e-07,
+    "bf16_dg128.dx_acc": 1.3e-07,
+    "x6w_1x1.y": 2.1e-07,
+    "x6w_1x1.dx": 4.0e-07,
+    "x6w_1x1.dx_acc": 2.8e-07,
+    "x6w_m128.y": 3.4e-07,
+    "x6w_dg128.dx": 3.6e-07,
+    "x6w_dg128.dx_acc": 2.7e-07,
+    "x6w_wide.y": 4.0e-07,
     "f32_narrow.y": 4.5e-07,
     "f32_narrow.dx": 3.4e-07,
     "f32_narrow.dx_acc": 2.7e-07,

@@ -100,7 +100,12 @@ def test_route_table_reaches_every_listed_kernel():
              "k_conv_dgrad_u<64, 64>", "k_conv_fwd<64>", "k_conv_fwd<128>", "k_conv_dgrad<64>", "k_conv_dgrad<128>",
              "k_conv_x6<64, 64, false, true, 1>", "k_conv_pl2<8, 1, 1, false>", "k_wgrad_pls<1>",
              "k_conv_x6<128, 64, false, true, 3>", "k_conv_x6<128, 64, true, true, 3>", "k_conv_pl2w<9, 3, false>",
-             "k_wgrad_pl<1>", "k_wgrad_plw<1>"]
+             "k_wgrad_pl<1>", "k_wgrad_plw<1>",
+             # every instantiation of the round-1 kernels on csrc/conv_tile32.h that no row above names
+             "k_conv_fwd_u<128, 64>", "k_conv_fwd_u<128, 128>", "k_conv_dgrad_u<128, 64>", "k_conv_dgrad_u<128, 128>",
+             "k_conv_x6<64, 64, true, true, 1>", "k_conv_x6<128, 64, false, true, 1>", "k_conv_x6<128, 64, true, true, 1>",
+             "k_conv_x6<64, 64, false, false, 3>", "k_conv_x6<64, 64, true, false, 3>", "k_conv_x6<128, 64, false, false, 3>",
+             "k_conv_x6<128, 64, true, false, 3>", "k_conv_x6<128, 128, false, false, 3>"]
     assert not [n for n in want if n not in names]
     assert set(("k_conv_pl2w<8, 3, false>", "k_conv_pl2<8, 1, 3, false>")) <= set(
         v for rt in R.ROUTES if rt.id not in R.NO_DENSE for v in rt.names.values())       # a dense case reaches them too

@@ -4,7 +4,7 @@
 
 Each file of both trees is compiled for gfx950 with the flags of iswm_amd/build.py plus `--cuda-device-only -S` (no GPU, nothing
 is launched).  Per kernel symbol the instruction stream is normalised -- comments and alignment directives dropped, basic-block
-labels renumbered in order of appearance, the per-file g_zero_row_* / g_dump_* symbol names masked -- and compared:
+labels renumbered in order of appearance, the per-file g_zero_row* / g_dump_* symbol names masked -- and compared:
     identical     equal line by line, register numbers included
     same opcodes  the same opcode sequence, operands (register numbers, immediates) differ
     differs       anything else
@@ -25,7 +25,7 @@ from iswm_amd.build import FLAGS, _hipcc
 
 FIELDS = (("vgpr", ".vgpr_count"), ("agpr", ".agpr_count"), ("sgpr", ".sgpr_count"), ("scratch", ".private_segment_fixed_size"),
           ("lds", ".group_segment_fixed_size"), ("vspill", ".vgpr_spill_count"), ("sspill", ".sgpr_spill_count"))
-MASKED = re.compile(r"\b\w*g_(?:zero_row|dump)_\w*")
+MASKED = re.compile(r"\b\w*g_(?:zero_row|dump)\w*")
 LABEL = re.compile(r"\.LBB\d+_\d+")
 MANGLED = re.compile(r"\b_Z\w+")
 
