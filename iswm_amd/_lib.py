@@ -1,4 +1,5 @@
-"""ctypes binding of libiswm_hip.so, derived from include/iswm_hip.h at import.
+"""ctypes binding of libiswm_hip.so, derived from include/iswm_hip.h (and its extension header include/iswm_hip_sep.h, whose
+prototypes go to a table of their own, EXT_EXPORTS / _EXT_SIGS, parsed with the main header's types in scope) at import.
 
 The header is the only declaration of the C ABI.  It is parsed once here -- `re` and `ctypes`, nothing generated, neither
 the library nor torch loaded -- into
@@ -19,6 +20,7 @@ cannot be resolved, importing the ops raises -- nothing silently routes through
 torch ops or the CPU oracle.
 """
 import ctypes
+import functools
 import os
 import re
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
@@ -26,6 +28,7 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libiswm_hip.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip.h")
+EXT_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_sep.h")
 
 # (`long long` is 8 bytes on every ABI the library is built for; tests/test_abi_cpu.py holds that)
 _SCALARS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "size_t": c_size_t, "float": c_float,
@@ -33,9 +36,31 @@ _SCALARS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "size_t": c_
 _POINTEES = {"void", "char", "unsigned char", "signed char", "uint8_t", "int32_t", "uint32_t"}    # pointed to, never by value
 
 
-def parse_header(text):
-    """(CONSTANTS, STRUCTS, _SIGS) of a header written in the subset of C the module docstring names"""
-    constants, structs, sigs, scalars, known = {}, {}, {}, dict(_SCALARS), {}
+def parse_header(text, base=None):
+    """(CONSTANTS, STRUCTS, _SIGS) of a header written in the subset of C the module docstring names.  base: the text of the
+    header this one includes; its records and typedefs may be used, and only what `text` itself declares is returned (a name
+    declared in both is a ValueError)."""
+    if base is None:
+        return tuple(dict(t) for t in _parsed(text)[:3])
+    tables = tuple(dict(t) for t in _parsed(base))         # (the record classes are the base's own: one POINTER type each)
+    inherited = [set(t) for t in tables[:3]]
+    redeclared = _scan_header(text, *tables, taken=set().union(*inherited))
+    if redeclared:
+        raise ValueError("iswm_hip.h: an extension header declares %s again" % sorted(redeclared))
+    return tuple({k: v for k, v in t.items() if k not in old} for t, old in zip(tables, inherited))
+
+
+@functools.lru_cache(maxsize=None)
+def _parsed(text):
+    """(constants, structs, sigs, typedef'd scalars, resolved types) of one header text, parsed once"""
+    tables = ({}, {}, {}, dict(_SCALARS), {})
+    _scan_header(text, *tables)
+    return tables
+
+
+def _scan_header(text, constants, structs, sigs, scalars, known, taken=()):
+    """parse_header's pass over one header text, into the tables; returns the names of `taken` it declares again"""
+    declared = []
 
     def bad(why, decl):
         return ValueError("iswm_hip.h: %s: %r" % (why, " ".join(decl.split())))
@@ -76,6 +101,7 @@ def parse_header(text):
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     for line in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\S[^\n]*)", text, re.M):    # (the include guard has no value)
         constants[line[0]] = integer(line[1], "#define %s %s" % line)
+        declared.append(line[0])
     text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
     m = re.fullmatch(r'\s*extern\s+"C"\s*\{(.*)\}\s*', text, re.S)
     body, one = m.group(1) if m else text, r"((?:[^;{}]|\{[^{}]*\})*);"          # up to the next `;` outside braces
@@ -89,6 +115,7 @@ def parse_header(text):
                 if not eq or not re.fullmatch(r"\s*\w+\s*", name):
                     raise bad("an enumerator needs `NAME = <integer>`", decl)
                 constants[name.strip()] = integer(value, decl)
+                declared.append(name.strip())
             continue
         m = re.fullmatch(r"typedef\s+struct(?:\s+\w+)?\s*\{(.*)\}\s*(\w+)", decl, re.S)
         if m:
@@ -103,6 +130,7 @@ def parse_header(text):
                 fields += [(name, ctype(t, decl, array))] + [(n, ctype(t, decl, a)) for _, n, a in
                                                              (declarator(t + d, decl) for d in more)]
             structs[m.group(2)] = type(m.group(2), (ctypes.Structure,), {"_fields_": fields})
+            declared.append(m.group(2))
             continue
         m = re.fullmatch(r"typedef\s+([\w\s*]*[\s*])(\w+)", decl)
         if m:
@@ -114,11 +142,18 @@ def parse_header(text):
         args = [] if m.group(3).strip() in ("", "void") else [declarator(a, decl) for a in m.group(3).split(",")]
         # (an array parameter `T name[]` is the pointer `T* name`)
         sigs[m.group(2)] = (ctype(m.group(1), decl), [ctype(t if array is None else t + "*", decl) for t, _, array in args])
-    return constants, structs, sigs
+        declared.append(m.group(2))
+    return {n for n in declared if n in taken}
 
 
 with open(HEADER) as _f:
-    CONSTANTS, STRUCTS, _SIGS = parse_header(_f.read())
+    _TEXT = _f.read()
+CONSTANTS, STRUCTS, _SIGS = parse_header(_TEXT)
+# the extension header: prototypes added without touching the tables above (it declares no record and no constant)
+with open(EXT_HEADER) as _f:
+    _EXT_CONSTANTS, _EXT_STRUCTS, _EXT_SIGS = parse_header(_f.read(), base=_TEXT)
+if _EXT_CONSTANTS or _EXT_STRUCTS:
+    raise ValueError("iswm_hip_sep.h declares prototypes only, not %s" % sorted(set(_EXT_CONSTANTS) | set(_EXT_STRUCTS)))
 ConvDesc, QConvDesc, PredictView = STRUCTS["iswm_conv_desc"], STRUCTS["iswm_qconv_desc"], STRUCTS["iswm_predict_view"]
 
 
@@ -141,6 +176,7 @@ class ScenePlan(STRUCTS["iswm_scene_plan"]):
 
 
 EXPORTS = tuple(_SIGS)
+EXT_EXPORTS = tuple(_EXT_SIGS)
 _lib = None
 
 
@@ -161,7 +197,7 @@ def load():
     # two runtimes and the library's launches on torch's streams fail ("no ROCm-capable device is detected").
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in list(_SIGS.items()) + list(_EXT_SIGS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

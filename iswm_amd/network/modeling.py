@@ -9,14 +9,17 @@ Differences, all deliberate:
   * ``deeplabv3plus_resnet101`` / ``deeplabv3_resnet50/101`` are exposed (the reference
     reaches ResNet-101 only through the private ``_segm_resnet``);
   * ``deeplabv3plus_mobilenet`` / ``deeplabv3_mobilenet``: the reference has no MobileNet; the backbone
-    and its state_dict keys follow the public MobileNetV2 / DeepLabV3Plus-Pytorch definition.
+    and its state_dict keys follow the public MobileNetV2 / DeepLabV3Plus-Pytorch definition;
+  * ``deeplabv3plus_xception`` / ``deeplabv3_xception``: the reference ships the Xception backbone
+    (network/backbone/xception.py) but no constructor selects it; ``_segm_xception`` follows the public
+    DeepLabV3Plus-Pytorch definition the reference was forked from (return_layers conv4 / block1).
 """
 import torch
 from torch import nn
 
 from . import _hip
 from ._deeplab import DeepLabHead, DeepLabHeadV3Plus, DeepLabV3
-from .backbone import mobilenetv2, resnet
+from .backbone import mobilenetv2, resnet, xception
 from .utils import IntermediateLayerGetter
 
 
@@ -87,6 +90,30 @@ def _segm_mobilenet(name, backbone_name, num_classes, output_stride, pretrained_
     return DeepLabV3(backbone, classifier)
 
 
+def _segm_xception(name, backbone_name, num_classes, output_stride, pretrained_backbone):
+    if output_stride == 8:
+        replace_stride_with_dilation = [False, False, True, True]
+        aspp_dilate = [12, 24, 36]
+    else:
+        replace_stride_with_dilation = [False, False, False, True]
+        aspp_dilate = [6, 12, 18]
+    backbone = xception.xception(pretrained=pretrained_backbone, replace_stride_with_dilation=replace_stride_with_dilation)
+    inplanes = 2048
+    low_level_planes = 128
+
+    # conv4 is the last child taken, so bn4 is never applied and is not part of the model
+    if name == 'deeplabv3plus':
+        return_layers = {'conv4': 'out', 'block1': 'low_level'}
+        classifier = DeepLabHeadV3Plus(inplanes, low_level_planes, num_classes, aspp_dilate)
+    elif name == 'deeplabv3':
+        return_layers = {'conv4': 'out'}
+        classifier = DeepLabHead(inplanes, num_classes, aspp_dilate)
+    else:
+        raise NotImplementedError(name)
+    backbone = IntermediateLayerGetter(backbone, return_layers=return_layers)
+    return DeepLabV3(backbone, classifier)
+
+
 def _load_model(arch_type, backbone, num_classes, output_stride, pretrained_backbone, temporal=False,
                 model_type='parallel', opts=None, in_channels=3):
     if backbone.startswith('resnet'):
@@ -131,3 +158,15 @@ def deeplabv3plus_mobilenet(num_classes=21, output_stride=8, pretrained_backbone
 def deeplabv3_mobilenet(num_classes=21, output_stride=8, pretrained_backbone=False):
     return _load_model('deeplabv3', 'mobilenetv2', num_classes, output_stride=output_stride,
                        pretrained_backbone=pretrained_backbone)
+
+
+def deeplabv3plus_xception(num_classes=21, output_stride=8, pretrained_backbone=False):
+    """DeepLabV3+ with the dilated Xception backbone.  _load_model refuses 'xception' as the reference's does, so the two
+    Xception constructors build through _segm_xception directly."""
+    return _segm_xception('deeplabv3plus', 'xception', num_classes, output_stride=output_stride,
+                          pretrained_backbone=pretrained_backbone)
+
+
+def deeplabv3_xception(num_classes=21, output_stride=8, pretrained_backbone=False):
+    return _segm_xception('deeplabv3', 'xception', num_classes, output_stride=output_stride,
+                          pretrained_backbone=pretrained_backbone)

@@ -6,6 +6,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip
+from .backbone import xception
 from .. import ops
 from .._hip_compat import DeQuantStub, QuantStub
 
@@ -158,8 +159,15 @@ class IntermediateLayerGetter(nn.ModuleDict):
         super(IntermediateLayerGetter, self).__init__(layers)
         self.return_layers = orig_return_layers
         self._saved = None
+        # an Xception's children (two stem stages, blocks, conv3 / bn3 / relu3 as one unit, the bare conv4) are walked by
+        # backbone/xception.py
+        self._xception = isinstance(model, xception.Xception)
 
     def fwd(self, x, save):
+        if self._xception:
+            out, ctxs = xception.walk_fwd(self, x, save)
+            _hip.keep(self, save, (ctxs,))
+            return OrderedDict(out)
         out = OrderedDict()
         stem_ctx = None
         for name, module in self.named_children():
@@ -178,6 +186,8 @@ class IntermediateLayerGetter(nn.ModuleDict):
 
     def bwd(self, dfeats, sink, need_dx=False):
         stem_ctx, = _hip.take(self, sink)
+        if self._xception:
+            return xception.walk_bwd(self, stem_ctx, dfeats, sink, need_dx)
         names = [n for n, _ in self.named_children()]
         inv = {v: k for k, v in self.return_layers.items()}
         tap = {inv[k]: g for k, g in dfeats.items() if g is not None}

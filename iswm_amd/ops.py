@@ -738,6 +738,46 @@ def dwconv3x3_bwd(x, dy, w, g, cw, dx=None, accumulate=False, dw=None, need_dx=T
     return dx, dw
 
 
+def dwconv3x3_pre_fwd(x, w, g, relu_in, out=None, planes=False):
+    """y = dwconv3x3(relu?(x), w) with 1 <= g.pad <= g.dil and no statistics (csrc/dwconv3.hip, include/iswm_hip_sep.h): the
+    depthwise half of a separable unit whose consumer is a 1x1 convolution.  `out`: an fp32 NHWC tensor or Planes whose pitch
+    may exceed g.cin (a channel slice [..., :g.cin] of the consumer's padded input buffer); every column between g.cin and
+    that pitch is written as zeros.  Without `out` the result is dense, Planes if `planes`."""
+    x = as_f32(x)
+    if out is None:
+        out = new_planes(g.n, g.ho, g.wo, g.cin, x.device) if planes else new_act(g.n, g.ho, g.wo, g.cin, x.device)
+    pt, n, h, wd, c, ldy, ps = xgeom(out)
+    if (n, h, wd, c) != (g.n, g.ho, g.wo, g.cin):
+        raise ValueError("dwconv3x3_pre_fwd: out is %s, expected %s" % ((n, h, wd, c), (g.n, g.ho, g.wo, g.cin)))
+    d = g.desc(geom(x)[4], ldy)
+    call("iswm_dwconv3x3_pre_fwd", ctypes.byref(d), _p(x), _p(w), w.shape[0], int(bool(relu_in)), _p(pt), ps, ldy, _stream())
+    return out
+
+
+def dwconv3x3_pre_bwd(x, dy, w, g, cw, relu_in, dx=None, accumulate=False, dw=None, need_dx=True, need_dw=True):
+    """backward of dwconv3x3_pre_fwd in one pass over dy and x, the saved input BEFORE the ReLU: dw [Cw,1,3,3] from relu?(x),
+    and dx (=|+=) (x > 0) * dgrad(dy, w) -- the mask only with relu_in.  Returns (dx|None, dw|None)."""
+    x, dy = as_f32(x), as_f32(dy)
+    if need_dx and dx is None:
+        assert not accumulate
+        dx = new_act(*x.shape, dy.device)
+    if not need_dx:
+        dx = None
+    d = g.desc(geom(x)[4], geom(dy)[4])
+    lddx = geom(dx)[4] if dx is not None else 0
+    ws, need = None, 0
+    if need_dw:
+        if dw is None:
+            dw = torch.empty((cw, 1, 3, 3), dtype=torch.float32, device=x.device)
+        need = _lib.load().iswm_dwconv3x3_pre_bwd_workspace(ctypes.byref(d))
+        ws = torch.empty((need // 4,), dtype=torch.float32, device=x.device)
+    else:
+        dw = None
+    call("iswm_dwconv3x3_pre_bwd", ctypes.byref(d), _p(x), _p(dy), _p(w), cw, int(bool(relu_in)), _p(dx), lddx,
+         int(bool(accumulate)), _p(dw), _p(ws), need, _stream())
+    return dx, dw
+
+
 def rows(t):
     n, h, w, c, ld = geom(t)
     return n * h * w, c, ld
