@@ -1115,6 +1115,53 @@ def overlap_loss_bwd(logits, labels, weight, ignore_index, coef, upstream):
     return grad
 
 
+def _distill_args(student, teacher, labels, weight, temperature):
+    """the checks of the distillation calls -> student, teacher, labels, B, C, H * W, float32(1 / temperature)"""
+    student, labels, b, c, hw = _pixel_loss_args(student, labels, weight, "the distillation loss")
+    if not (torch.is_tensor(teacher) and teacher.dtype == torch.float32 and teacher.is_cuda and teacher.device == student.device):
+        raise ValueError("the distillation loss expects fp32 CUDA teacher logits on the student's device")
+    if teacher.shape != student.shape:
+        raise ValueError("teacher logits %s do not have the student's shape %s" % (tuple(teacher.shape), tuple(student.shape)))
+    if not (0.0 < temperature < math.inf):
+        raise ValueError("temperature must be positive and finite (got %r)" % (temperature,))
+    inv_tau = float(torch.tensor(1.0 / float(temperature), dtype=torch.float32))
+    if not (0.0 < inv_tau < math.inf):
+        raise ValueError("1 / temperature is not a positive finite fp32 value (temperature %r)" % (temperature,))
+    return student, teacher.contiguous(), labels, b, c, hw, inv_tau
+
+
+def distill_loss_fwd(student, teacher, labels, weight, ignore_index, temperature):
+    """One pass over both logit tensors, nothing stored per pixel -> sums (float64 [5], on the device) =
+    {sum w*nll, sum w, sum KL, N, A} over the valid pixels (include/iswm_hip_kd.h)."""
+    student, teacher, labels, b, c, hw, inv_tau = _distill_args(student, teacher, labels, weight, temperature)
+    partials = torch.empty((_lib.load().iswm_distill_loss_partials(b * hw),), dtype=torch.float32, device=student.device)
+    sums = torch.empty((5,), dtype=torch.float64, device=student.device)
+    call("iswm_distill_loss_fwd", _p(student), _p(teacher), _p(labels), labels.element_size(), b, c, hw, _p(weight),
+         int(ignore_index), inv_tau, _p(partials), _p(sums), _stream())
+    return sums
+
+
+def distill_loss_coeffs(sums, ce_weight, distill_weight, temperature):
+    """sums (this process's, or all-reduced over the ranks) -> (out fp32 [3] = {loss, CE term, KD term}, coef fp32 [2]) on
+    the device."""
+    assert sums.dtype == torch.float64 and sums.is_cuda and sums.is_contiguous() and sums.numel() == 5
+    buf = torch.empty((5,), dtype=torch.float32, device=sums.device)
+    call("iswm_distill_loss_coeffs", _p(sums), float(ce_weight), float(distill_weight), float(temperature), _p(buf),
+         _p(buf[3:]), _stream())
+    return buf[:3], buf[3:]
+
+
+def distill_loss_bwd(student, teacher, labels, weight, ignore_index, temperature, coef, upstream):
+    """The second pass: upstream[0] * dL/dstudent, written once (upstream: fp32 device scalar [1])."""
+    student, teacher, labels, b, c, hw, inv_tau = _distill_args(student, teacher, labels, weight, temperature)
+    assert coef.dtype == torch.float32 and coef.numel() == 2 and coef.is_cuda
+    assert upstream.dtype == torch.float32 and upstream.numel() == 1 and upstream.is_cuda
+    grad = torch.empty_like(student)
+    call("iswm_distill_loss_bwd", _p(student), _p(teacher), _p(labels), labels.element_size(), b, c, hw, _p(weight),
+         int(ignore_index), inv_tau, _p(coef), _p(upstream), _p(grad), _stream())
+    return grad
+
+
 def ohem_nu0(thresh):
     """float32(-ln thresh): a pixel whose true-class probability is at most thresh has nll >= this (thresh 1 -> +0)"""
     if not 0.0 < thresh <= 1.0:

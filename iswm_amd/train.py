@@ -29,7 +29,11 @@ forced by the reference not being runnable as shipped:
   * ``--ohem_thresh P`` (off by default) averages the CE over the hard pixels only: those predicted below P and at least
     ``--ohem_min_kept`` per process, selected on the device (DESIGN.md section 19);
   * ``--lovasz_weight W`` (off by default) adds W x the per-image Lovasz-Softmax term to ``--ce_weight`` x the CE, on a
-    segmented radix sort on the device.
+    segmented radix sort on the device (DESIGN.md section 20);
+  * ``--distill_ckpt PATH --distill_model NAME`` (off by default) trains against a frozen teacher: the checkpoint is loaded
+    strictly into NAME, runs in eval mode without gradients on every augmented batch, and the criterion becomes
+    ``--ce_weight`` x the CE plus ``--distill_weight`` x T^2 x KL(teacher || student) at ``--distill_temperature`` T (DESIGN.md
+    section 22).  The teacher never enters the optimizer, the gradient all-reduce or the checkpoint.
 """
 import argparse
 import contextlib
@@ -47,7 +51,7 @@ from torch.utils import data
 from . import network, ops
 from .optim import FusedAdam, FusedAdamW, FusedSGD, ema_model_state
 from .parallel import DistributedDataParallelHIP
-from .utils.loss import (CrossEntropyLoss, DiceLoss, LovaszSoftmaxLoss, OhemCrossEntropyLoss, TverskyLoss,
+from .utils.loss import (CrossEntropyLoss, DiceLoss, DistillationLoss, LovaszSoftmaxLoss, OhemCrossEntropyLoss, TverskyLoss,
                          calculate_class_weights, calculate_class_weights_resident)
 from .val_results import save_validation_results
 
@@ -59,7 +63,7 @@ class _ArgParser(argparse.ArgumentParser):
         opts, rest = super().parse_known_args(args, namespace)
         if not (math.isfinite(opts.lovasz_weight) and opts.lovasz_weight >= 0):
             self.error("--lovasz_weight must be finite and not negative (0 = off)")
-        if opts.overlap_loss == 'none' and opts.lovasz_weight == 0 and opts.ce_weight == 0:
+        if opts.overlap_loss == 'none' and opts.lovasz_weight == 0 and opts.ce_weight == 0 and opts.distill_ckpt is None:
             self.error("--ce_weight 0 with --overlap_loss none leaves no loss term")
         if opts.lovasz_weight > 0 and opts.overlap_loss != 'none':
             self.error("--lovasz_weight with --overlap_loss %s: one region term at a time" % opts.overlap_loss)
@@ -84,7 +88,35 @@ class _ArgParser(argparse.ArgumentParser):
                        "supported" % opts.overlap_loss)
         if opts.use_ema and not (opts.test_only and opts.ckpt):
             self.error("--use_ema evaluates the EMA weights of a checkpoint: it needs --test_only and --ckpt")
+        self._check_distill(opts)
         return opts, rest
+
+    def _check_distill(self, opts):
+        """the --distill_* options: given only with --distill_ckpt, and with no criterion or mode that has no teacher; the
+        options left out then take their defaults"""
+        given = [flag for flag, value in (("--distill_model", opts.distill_model),
+                                          ("--distill_output_stride", opts.distill_output_stride),
+                                          ("--distill_use_ema", opts.distill_use_ema or None),
+                                          ("--distill_weight", opts.distill_weight),
+                                          ("--distill_temperature", opts.distill_temperature)) if value is not None]
+        if opts.distill_ckpt is None:
+            if given:
+                self.error("%s without --distill_ckpt: there is no teacher" % ", ".join(given))
+        else:
+            if opts.distill_model is None:
+                self.error("--distill_ckpt needs --distill_model: the architecture the checkpoint is loaded into")
+            for flag, on in (("--overlap_loss %s" % opts.overlap_loss, opts.overlap_loss != 'none'),
+                             ("--lovasz_weight", opts.lovasz_weight > 0), ("--ohem_thresh", opts.ohem_thresh > 0),
+                             ("--test_only", opts.test_only)):
+                if on:
+                    self.error("--distill_ckpt with %s: distillation goes with the plain CE term of a training run only" % flag)
+        for name, default in (("distill_output_stride", 16), ("distill_weight", 1.0), ("distill_temperature", 1.0)):
+            if getattr(opts, name) is None:
+                setattr(opts, name, default)
+        if not (math.isfinite(opts.distill_weight) and opts.distill_weight > 0):
+            self.error("--distill_weight must be positive and finite")
+        if not (math.isfinite(opts.distill_temperature) and opts.distill_temperature > 0):
+            self.error("--distill_temperature must be positive and finite")
 
 
 def get_argparser():
@@ -178,6 +210,20 @@ def get_argparser():
                         help="use DECAY from the first update instead of min(DECAY, (1 + t) / (10 + t))")
     parser.add_argument("--use_ema", action='store_true', default=False,
                         help="with --test_only --ckpt: evaluate the checkpoint's EMA weights")
+    parser.add_argument("--distill_ckpt", type=str, default=None, metavar="PATH",
+                        help="train against a frozen teacher: a checkpoint of this trainer, loaded strictly into "
+                             "--distill_model; the criterion is --ce_weight x CE + --distill_weight x T^2 x KL(teacher || "
+                             "student) at --distill_temperature T; --loss_type still selects the CE term's class weights")
+    parser.add_argument("--distill_model", type=str, default=None, choices=available_models,
+                        help="the teacher's architecture")
+    parser.add_argument("--distill_output_stride", type=int, default=None, choices=[8, 16],
+                        help="the teacher's output stride (default 16)")
+    parser.add_argument("--distill_use_ema", action='store_true', default=False,
+                        help="load the teacher checkpoint's EMA weights")
+    parser.add_argument("--distill_weight", type=float, default=None, metavar="W",
+                        help="factor of the distillation term (default 1.0)")
+    parser.add_argument("--distill_temperature", type=float, default=None, metavar="T",
+                        help="temperature both logit tensors are divided by (default 1.0)")
     return parser
 
 
@@ -266,6 +312,41 @@ def setup_model(opts):
                 pretrained_backbone=opts.pretrained_backbone)
 
 
+def read_teacher_checkpoint(opts):
+    """the contents of --distill_ckpt (None without the option), read before anything else is set up: a missing file is a
+    FileNotFoundError, an INT8 checkpoint is refused (it holds quantized convolutions, not a state dict to train against)"""
+    path = getattr(opts, "distill_ckpt", None)
+    if path is None:
+        return None
+    if not os.path.isfile(path):
+        raise FileNotFoundError("--distill_ckpt: no checkpoint at %r" % (path,))
+    name = os.path.basename(path)
+    if name.startswith('best_') and name.endswith('.pth') and os.path.isdir(opts.checkpoints_dir) and \
+            os.path.samefile(os.path.dirname(os.path.abspath(path)), opts.checkpoints_dir):
+        raise ValueError("--distill_ckpt %s lies in --checkpoints_dir, where the run replaces every best_*.pth: it would "
+                         "delete its own teacher; pick another --checkpoints_dir" % path)
+    from . import quant
+    q, ck = quant.read_checkpoint(path)
+    if q is not None:
+        raise ValueError("--distill_ckpt %s is an INT8 checkpoint: a teacher is an FP32 checkpoint of this trainer (an INT8 "
+                         "teacher is not supported)" % path)
+    return ck
+
+
+def setup_teacher(opts, device, ck=None):
+    """the frozen teacher of --distill_ckpt: --distill_model built as setup_model builds the student, the checkpoint (its EMA
+    weights with --distill_use_ema) loaded strictly, eval mode, no parameter requires grad.  It is no part of the optimizer,
+    the data-parallel wrapper or the checkpoint.  `ck`: the file's contents when the caller has read it already."""
+    from .predict import load_model
+    if ck is None:
+        ck = read_teacher_checkpoint(opts)
+    ctor = network.modeling.__dict__[opts.distill_model]
+    teacher = ctor(num_classes=opts.num_classes, output_stride=opts.distill_output_stride, pretrained_backbone=False)
+    load_model(teacher, opts.distill_ckpt, ck=ck, use_ema=opts.distill_use_ema)
+    teacher.to(device).eval().requires_grad_(False)
+    return teacher
+
+
 def setup_optimizer(model, opts):
     """train.py:421-444 -- note: no lr argument, torch defaults apply"""
     params = model.parameters()
@@ -287,6 +368,9 @@ def setup_criterion(opts, class_weights, group=None):
     """train.py:454-459; with --overlap_loss the same CE (times --ce_weight) plus a Dice / Tversky / focal-Tversky term; with
     --ohem_thresh the same CE over the hard pixels only"""
     weight = None if opts.loss_type == 'ce_loss' else class_weights
+    if getattr(opts, 'distill_ckpt', None) is not None:
+        return DistillationLoss(temperature=opts.distill_temperature, ce_weight=opts.ce_weight,
+                                distill_weight=opts.distill_weight, weight=weight, ignore_index=255, group=group)
     kind = getattr(opts, 'overlap_loss', 'none')
     if kind != 'none':
         common = dict(smooth=opts.overlap_smooth, classes=opts.overlap_classes, ce_weight=opts.ce_weight,
@@ -433,6 +517,7 @@ def save_best_model(model, optimizer, scheduler, opts, val_score, weighted_score
 def main(argv=None):
     opts = get_argparser().parse_args(argv)
     opts.num_classes = 2                                   # train.py:853
+    opts._teacher_ck = read_teacher_checkpoint(opts)       # refused here, before the data set is touched
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", opts.gpu_id.split(',')[0]))
@@ -607,6 +692,14 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
     clipping = bool(getattr(opts, "clip_grad_norm", 0.0))
     mining = isinstance(criterion, OhemCrossEntropyLoss)
     lovasz = isinstance(criterion, LovaszSoftmaxLoss)
+    teacher = None
+    if getattr(opts, 'distill_ckpt', None) is not None:
+        teacher = setup_teacher(opts, device, getattr(opts, '_teacher_ck', None))
+        opts._teacher_ck = None
+        if rank == 0:
+            print("Teacher %s (output stride %d%s): T=%g, CE x %g + KD x %g" %
+                  (opts.distill_model, opts.distill_output_stride, ", EMA weights" if opts.distill_use_ema else "",
+                   opts.distill_temperature, opts.ce_weight, opts.distill_weight))
 
     sequence_val = opts.val_metrics == 'sequence'
     if sequence_val:
@@ -634,8 +727,14 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
         cur_epochs += 1
         for images, labels in epoch(cur_epochs):
             cur_itrs += 1
-            logits = net(images)
-            loss = criterion(logits, labels)
+            if teacher is not None:
+                with torch.no_grad():                           # eval mode, nothing saved for a backward
+                    teacher_logits = teacher(images)
+                logits = net(images)
+                loss = criterion(logits, labels, teacher_logits)
+            else:
+                logits = net(images)
+                loss = criterion(logits, labels)
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()
@@ -653,6 +752,9 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
                     norm += ", kept=%d (%.2f%%)" % (kept, 100.0 * kept / (labels.numel() * world))
                 if lovasz:                                      # the last step's (image, class) pairs of the global batch: one read-back
                     norm += ", present=%d" % int(criterion.last_present)
+                if teacher is not None:                         # the last step's KD term and agreement of the global batch: one read-back
+                    kd, agree, nvalid = torch.stack([criterion.last_terms[1].double(), *criterion.last_agreement]).tolist()
+                    norm += ", kd=%.6f, agree=%.2f%%" % (kd, 100.0 * agree / nvalid if nvalid else 0.0)
                 print("Epoch %d, Itrs %d/%d, Loss=%.6f, lr=%.3e, %.1f img/s%s" %
                       (cur_epochs, cur_itrs, opts.total_itrs, avg, optimizer.param_groups[0]['lr'], n_last / dt, norm))
                 interval_loss.zero_()

@@ -291,7 +291,79 @@ class LovaszSoftmaxLoss(nn.Module):
         return loss
 
 
-def create_loss(loss_type="focal", temporal_loss="none", temporal_weight=0.5, **kwargs):
+class _DistillLossFn(torch.autograd.Function):
+    """ce_weight * weighted CE + distill_weight * tau^2 * KL(teacher || student) at temperature tau on the two-pass kernels
+    (csrc/distill.hip): the forward pass stores nothing per pixel, the backward pass reads both logit tensors again and writes
+    the finished gradient once.  Nothing is read back.  With `group` the five sums {sum w nll, sum w, sum KL, N, A} are
+    all-reduced before the coefficients are formed, so both normalisers are the global batch's and the SUM gradient all-reduce
+    of parallel.py yields the gradient of the global loss.  The teacher gets no gradient.  Good for one backward: a second one
+    through the same call (retain_graph) is refused."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, teacher, weight, ignore_index, temperature, ce_weight, distill_weight, group):
+        sums = ops.distill_loss_fwd(logits, teacher, labels, weight, ignore_index, temperature)
+        if group is not None:
+            import torch.distributed as dist
+            dist.all_reduce(sums, group=group)
+        out, coef = ops.distill_loss_coeffs(sums, ce_weight, distill_weight, temperature)
+        ctx.save_for_backward(logits, labels, teacher, weight, coef)
+        ctx.ignore_index, ctx.temperature, ctx.consumed = ignore_index, temperature, False
+        ctx.mark_non_differentiable(sums, out)
+        return out[0].clone(), sums, out
+
+    @staticmethod
+    @once
+    def backward(ctx, upstream, _sums, _out):
+        if ctx.consumed:
+            raise RuntimeError("DistillationLoss: %s" % CONSUMED)
+        ctx.consumed = True
+        logits, labels, teacher, weight, coef = ctx.saved_tensors
+        grad = ops.distill_loss_bwd(logits, teacher, labels, weight, ctx.ignore_index, ctx.temperature, coef, _scalar(upstream))
+        return grad, None, None, None, None, None, None, None, None
+
+
+class DistillationLoss(nn.Module):
+    """ce_weight * CrossEntropyLoss(weight, ignore_index) + distill_weight * temperature^2 * mean over the valid pixels of
+    KL(softmax(teacher / temperature) || softmax(student / temperature)) (Hinton et al. 2015), called as
+    ``criterion(logits, labels, teacher_logits)``.  The pixels are the ones the CE counts; the teacher's logits are a constant
+    (a tensor that requires grad is refused).  Under `group` both means run over all ranks' pixels.  At most 8 classes.
+
+    `last_terms` is a device view of {CE term, KD term} of the last call and `last_agreement` a pair of 0-dim device views
+    (A, N): the valid pixels on which student and teacher predict the same class, and the valid pixels (of all ranks under
+    `group`); reading either synchronises."""
+
+    def __init__(self, temperature=1.0, ce_weight=1.0, distill_weight=1.0, weight=None, ignore_index=255, group=None):
+        super().__init__()
+        if not (0 < temperature < math.inf):
+            raise ValueError("temperature must be positive and finite (got %r)" % (temperature,))
+        if not (0 <= ce_weight < math.inf and 0 <= distill_weight < math.inf):
+            raise ValueError("ce_weight and distill_weight must be finite and not negative")
+        if ce_weight == 0 and distill_weight == 0:
+            raise ValueError("ce_weight 0 with distill_weight 0 leaves no loss term")
+        self.register_buffer('weight', None if weight is None else weight.detach().float().clone())
+        self.temperature, self.ce_weight, self.distill_weight = float(temperature), float(ce_weight), float(distill_weight)
+        self.ignore_index = ignore_index
+        self.group = group
+        self.last_terms = self.last_agreement = None
+
+    def forward(self, inputs, targets, teacher_logits):
+        if not torch.is_tensor(teacher_logits):
+            raise TypeError("DistillationLoss is called as criterion(logits, labels, teacher_logits)")
+        if teacher_logits.requires_grad:
+            raise ValueError("the teacher's logits are a constant of the distillation loss: pass them detached (run the "
+                             "teacher under torch.no_grad())")
+        if teacher_logits.shape != inputs.shape:
+            raise ValueError("teacher logits %s do not have the student's shape %s" %
+                             (tuple(teacher_logits.shape), tuple(inputs.shape)))
+        targets = _check(inputs, targets)
+        w = _weight_for(self.weight, inputs)
+        loss, sums, out = _DistillLossFn.apply(inputs, targets, teacher_logits, w, self.ignore_index, self.temperature,
+                                               self.ce_weight, self.distill_weight, self.group)
+        self.last_terms, self.last_agreement = out[1:], (sums[4], sums[3])
+        return loss
+
+
+def create_loss(loss_type="focal",temporal_loss="none", temporal_weight=0.5, **kwargs):
     """reference utils/loss.py:37-39"""
     return FocalLoss(**kwargs)
 
