@@ -1,6 +1,6 @@
-"""ctypes binding of libiswm_hip.so, derived from include/iswm_hip.h (and its extension headers include/iswm_hip_sep.h and
-include/iswm_hip_kd.h, whose prototypes go to tables of their own, EXT_EXPORTS / _EXT_SIGS and KD_EXPORTS / _KD_SIGS, parsed
-with the main header's types in scope) at import.
+"""ctypes binding of libiswm_hip.so, derived from include/iswm_hip.h (and its extension headers include/iswm_hip_sep.h,
+include/iswm_hip_kd.h and include/iswm_hip_bd.h, whose prototypes go to tables of their own, EXT_EXPORTS / _EXT_SIGS,
+KD_EXPORTS / _KD_SIGS and BD_EXPORTS / _BD_SIGS, parsed with the main header's types in scope) at import.
 
 The header is the only declaration of the C ABI.  It is parsed once here -- `re` and `ctypes`, nothing generated, neither
 the library nor torch loaded -- into
@@ -31,6 +31,7 @@ LIB_PATH = os.path.join(HERE, "libiswm_hip.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip.h")
 EXT_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_sep.h")
 KD_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_kd.h")
+BD_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_bd.h")
 
 # (`long long` is 8 bytes on every ABI the library is built for; tests/test_abi_cpu.py holds that)
 _SCALARS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "size_t": c_size_t, "float": c_float,
@@ -163,6 +164,14 @@ if _KD_CONSTANTS or _KD_STRUCTS:
     raise ValueError("iswm_hip_kd.h declares prototypes only, not %s" % sorted(set(_KD_CONSTANTS) | set(_KD_STRUCTS)))
 if set(_KD_SIGS) & set(_EXT_SIGS):
     raise ValueError("iswm_hip_kd.h declares %s again (iswm_hip_sep.h has it)" % sorted(set(_KD_SIGS) & set(_EXT_SIGS)))
+# the distance-map and boundary-loss header, the same way; a name of any earlier header is refused
+with open(BD_HEADER) as _f:
+    _BD_CONSTANTS, _BD_STRUCTS, _BD_SIGS = parse_header(_f.read(), base=_TEXT)
+if _BD_CONSTANTS or _BD_STRUCTS:
+    raise ValueError("iswm_hip_bd.h declares prototypes only, not %s" % sorted(set(_BD_CONSTANTS) | set(_BD_STRUCTS)))
+if set(_BD_SIGS) & (set(_EXT_SIGS) | set(_KD_SIGS)):
+    raise ValueError("iswm_hip_bd.h declares %s again (an earlier extension header has it)" %
+                     sorted(set(_BD_SIGS) & (set(_EXT_SIGS) | set(_KD_SIGS))))
 ConvDesc, QConvDesc, PredictView = STRUCTS["iswm_conv_desc"], STRUCTS["iswm_qconv_desc"], STRUCTS["iswm_predict_view"]
 
 
@@ -187,6 +196,7 @@ class ScenePlan(STRUCTS["iswm_scene_plan"]):
 EXPORTS = tuple(_SIGS)
 EXT_EXPORTS = tuple(_EXT_SIGS)
 KD_EXPORTS = tuple(_KD_SIGS)
+BD_EXPORTS = tuple(_BD_SIGS)
 _lib = None
 
 
@@ -207,7 +217,7 @@ def load():
     # two runtimes and the library's launches on torch's streams fail ("no ROCm-capable device is detected").
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_EXT_SIGS.items()) + list(_KD_SIGS.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_EXT_SIGS.items()) + list(_KD_SIGS.items()) + list(_BD_SIGS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -1162,6 +1162,92 @@ def distill_loss_bwd(student, teacher, labels, weight, ignore_index, temperature
     return grad
 
 
+EDT_MAX_SIDE = 4096
+
+
+def _first_class(classes):
+    """'foreground' -> 1 (the class planes 1 .. C-1), 'all' -> 0"""
+    if classes not in OVERLAP_CLASSES:
+        raise ValueError("classes is 'foreground' or 'all' (got %r)" % (classes,))
+    return 1 - OVERLAP_CLASSES[classes]
+
+
+def signed_edt(labels, num_classes, classes='foreground', ignore_index=255):
+    """The exact signed squared Euclidean distance map of labels [B,H,W] (uint8 or int64, on the GPU) -> int32 [B, |K|, H, W],
+    K = the classes 1 .. C-1 ('foreground') or 0 .. C-1 ('all'): +d^2 to the nearest pixel of the class outside it, -d^2 to the
+    nearest valid pixel of another class inside it, 0 at invalid pixels and over a plane with either set empty
+    (include/iswm_hip_bd.h).  Sides up to 4096.  The workspace comes from torch's allocator; nothing is read back."""
+    first = _first_class(classes)
+    if not (torch.is_tensor(labels) and labels.dim() == 3 and labels.is_cuda and labels.dtype in (torch.uint8, torch.int64)):
+        raise ValueError("the distance map expects uint8 or int64 CUDA labels [B,H,W] (there is no CPU fallback)")
+    b, h, w = labels.shape
+    c = int(num_classes)
+    if c - first < 1:
+        raise ValueError("%d classes with classes=%r leave no class plane" % (c, classes))
+    if h > EDT_MAX_SIDE or w > EDT_MAX_SIDE:
+        raise ValueError("a %d x %d plane: the distance map takes sides up to %d" % (h, w, EDT_MAX_SIDE))
+    if b * h * w == 0:
+        raise ValueError("the distance map of an empty label tensor %s" % (tuple(labels.shape),))
+    nbytes = _lib.load().iswm_signed_edt_workspace(b, c, h, w, first)
+    if nbytes < 0:
+        raise ValueError("the distance map does not take labels %s with %d classes" % (tuple(labels.shape), c))
+    labels = labels.contiguous()
+    work = torch.empty((nbytes // 4,), dtype=torch.int32, device=labels.device)
+    sd2 = torch.empty((b, c - first, h, w), dtype=torch.int32, device=labels.device)
+    call("iswm_signed_edt", _p(labels), labels.element_size(), b, c, h, w, first, int(ignore_index), _p(sd2), _p(work), nbytes,
+         _stream())
+    return sd2
+
+
+def _boundary_args(logits, labels, sd2, weight, classes, clip):
+    """the checks of the boundary-loss calls -> logits, labels, sd2, B, C, H * W, first class"""
+    logits, labels, b, c, hw = _pixel_loss_args(logits, labels, weight, "the boundary loss")
+    first = _first_class(classes)
+    if c - first < 1:
+        raise ValueError("%d classes with classes=%r leave no class plane" % (c, classes))
+    if not (torch.is_tensor(sd2) and sd2.dtype == torch.int32 and sd2.is_cuda and sd2.device == logits.device):
+        raise ValueError("the boundary loss expects an int32 CUDA distance map on the logits' device")
+    want = (b, c - first) + tuple(logits.shape[2:])
+    if tuple(sd2.shape) != want:
+        raise ValueError("the distance map %s does not have the shape %s of these logits and classes=%r" %
+                         (tuple(sd2.shape), want, classes))
+    if not (0.0 <= clip < math.inf):
+        raise ValueError("clip must be finite and not negative, 0 = no clamp (got %r)" % (clip,))
+    return logits, labels, sd2.contiguous(), b, c, hw, first
+
+
+def boundary_loss_fwd(logits, labels, sd2, weight, ignore_index, classes='foreground', clip=0.0):
+    """One pass over the logits, the labels and the distance map of signed_edt, nothing stored per pixel -> sums (float64 [4],
+    on the device) = {sum w*nll, sum w, sum p*phi, N} over the valid pixels (include/iswm_hip_bd.h)."""
+    logits, labels, sd2, b, c, hw, first = _boundary_args(logits, labels, sd2, weight, classes, clip)
+    partials = torch.empty((_lib.load().iswm_boundary_loss_partials(b * hw),), dtype=torch.float32, device=logits.device)
+    sums = torch.empty((4,), dtype=torch.float64, device=logits.device)
+    call("iswm_boundary_loss_fwd", _p(logits), _p(labels), labels.element_size(), b, c, hw, first, _p(sd2), _p(weight),
+         int(ignore_index), float(clip), _p(partials), _p(sums), _stream())
+    return sums
+
+
+def boundary_loss_coeffs(sums, nsel, ce_weight, boundary_weight):
+    """sums (this process's, or all-reduced over the ranks) and nsel = |K| -> (out fp32 [3] = {loss, CE term, boundary term},
+    coef fp32 [2]) on the device.  The two factors are host doubles: changing them between calls costs no synchronisation."""
+    assert sums.dtype == torch.float64 and sums.is_cuda and sums.is_contiguous() and sums.numel() == 4
+    buf = torch.empty((5,), dtype=torch.float32, device=sums.device)
+    call("iswm_boundary_loss_coeffs", _p(sums), int(nsel), float(ce_weight), float(boundary_weight), _p(buf), _p(buf[3:]),
+         _stream())
+    return buf[:3], buf[3:]
+
+
+def boundary_loss_bwd(logits, labels, sd2, weight, ignore_index, coef, upstream, classes='foreground', clip=0.0):
+    """The second pass: upstream[0] * dL/dlogits, written once (upstream: fp32 device scalar [1])."""
+    logits, labels, sd2, b, c, hw, first = _boundary_args(logits, labels, sd2, weight, classes, clip)
+    assert coef.dtype == torch.float32 and coef.numel() == 2 and coef.is_cuda
+    assert upstream.dtype == torch.float32 and upstream.numel() == 1 and upstream.is_cuda
+    grad = torch.empty_like(logits)
+    call("iswm_boundary_loss_bwd", _p(logits), _p(labels), labels.element_size(), b, c, hw, first, _p(sd2), _p(weight),
+         int(ignore_index), float(clip), _p(coef), _p(upstream), _p(grad), _stream())
+    return grad
+
+
 def ohem_nu0(thresh):
     """float32(-ln thresh): a pixel whose true-class probability is at most thresh has nll >= this (thresh 1 -> +0)"""
     if not 0.0 < thresh <= 1.0:

@@ -33,7 +33,11 @@ forced by the reference not being runnable as shipped:
   * ``--distill_ckpt PATH --distill_model NAME`` (off by default) trains against a frozen teacher: the checkpoint is loaded
     strictly into NAME, runs in eval mode without gradients on every augmented batch, and the criterion becomes
     ``--ce_weight`` x the CE plus ``--distill_weight`` x T^2 x KL(teacher || student) at ``--distill_temperature`` T (DESIGN.md
-    section 22).  The teacher never enters the optimizer, the gradient all-reduce or the checkpoint.
+    section 22).  The teacher never enters the optimizer, the gradient all-reduce or the checkpoint;
+  * ``--boundary_weight W`` (off by default) adds W x the boundary loss (Kervadec et al. 2019) to ``--ce_weight`` x the CE: the
+    mean of probability x signed Euclidean distance to the ground-truth contour, on a distance map built on the device from
+    every augmented batch's labels; ``--boundary_clip D`` clamps the distance, ``--boundary_ramp_itrs N`` raises the factor
+    linearly from 0 over the first N iterations.
 """
 import argparse
 import contextlib
@@ -51,8 +55,8 @@ from torch.utils import data
 from . import network, ops
 from .optim import FusedAdam, FusedAdamW, FusedSGD, ema_model_state
 from .parallel import DistributedDataParallelHIP
-from .utils.loss import (CrossEntropyLoss, DiceLoss, DistillationLoss, LovaszSoftmaxLoss, OhemCrossEntropyLoss, TverskyLoss,
-                         calculate_class_weights, calculate_class_weights_resident)
+from .utils.loss import (BoundaryLoss, CrossEntropyLoss, DiceLoss, DistillationLoss, LovaszSoftmaxLoss, OhemCrossEntropyLoss,
+                         TverskyLoss, calculate_class_weights, calculate_class_weights_resident)
 from .val_results import save_validation_results
 
 
@@ -63,7 +67,10 @@ class _ArgParser(argparse.ArgumentParser):
         opts, rest = super().parse_known_args(args, namespace)
         if not (math.isfinite(opts.lovasz_weight) and opts.lovasz_weight >= 0):
             self.error("--lovasz_weight must be finite and not negative (0 = off)")
-        if opts.overlap_loss == 'none' and opts.lovasz_weight == 0 and opts.ce_weight == 0 and opts.distill_ckpt is None:
+        if not (math.isfinite(opts.boundary_weight) and opts.boundary_weight >= 0):
+            self.error("--boundary_weight must be finite and not negative (0 = off)")
+        if opts.overlap_loss == 'none' and opts.lovasz_weight == 0 and opts.ce_weight == 0 and opts.distill_ckpt is None and \
+                opts.boundary_weight == 0:
             self.error("--ce_weight 0 with --overlap_loss none leaves no loss term")
         if opts.lovasz_weight > 0 and opts.overlap_loss != 'none':
             self.error("--lovasz_weight with --overlap_loss %s: one region term at a time" % opts.overlap_loss)
@@ -89,7 +96,27 @@ class _ArgParser(argparse.ArgumentParser):
         if opts.use_ema and not (opts.test_only and opts.ckpt):
             self.error("--use_ema evaluates the EMA weights of a checkpoint: it needs --test_only and --ckpt")
         self._check_distill(opts)
+        self._check_boundary(opts)
         return opts, rest
+
+    def _check_boundary(self, opts):
+        """the --boundary_* options: the term goes with the plain weighted CE of a training run only, and the clamp and the
+        ramp are given only with it"""
+        if not (math.isfinite(opts.boundary_clip) and opts.boundary_clip >= 0):
+            self.error("--boundary_clip must be a finite distance >= 0 (0 = no clamp)")
+        if opts.boundary_ramp_itrs < 0:
+            self.error("--boundary_ramp_itrs must not be negative")
+        if opts.boundary_weight == 0:
+            given = [flag for flag, on in (("--boundary_clip", opts.boundary_clip > 0),
+                                           ("--boundary_ramp_itrs", opts.boundary_ramp_itrs > 0)) if on]
+            if given:
+                self.error("%s without --boundary_weight: there is no boundary term" % ", ".join(given))
+            return
+        for flag, on in (("--overlap_loss %s" % opts.overlap_loss, opts.overlap_loss != 'none'),
+                         ("--lovasz_weight", opts.lovasz_weight > 0), ("--ohem_thresh", opts.ohem_thresh > 0),
+                         ("--distill_ckpt", opts.distill_ckpt is not None), ("--test_only", opts.test_only)):
+            if on:
+                self.error("--boundary_weight with %s: the boundary term goes with the plain CE term of a training run only" % flag)
 
     def _check_distill(self, opts):
         """the --distill_* options: given only with --distill_ckpt, and with no criterion or mode that has no teacher; the
@@ -224,6 +251,14 @@ def get_argparser():
                         help="factor of the distillation term (default 1.0)")
     parser.add_argument("--distill_temperature", type=float, default=None, metavar="T",
                         help="temperature both logit tensors are divided by (default 1.0)")
+    parser.add_argument("--boundary_weight", type=float, default=0.0, metavar="W",
+                        help="add W x the boundary loss (probability x signed Euclidean distance to the ground-truth contour, "
+                             "on a distance map built on the device every step) to --ce_weight x CE; 0 = off")
+    parser.add_argument("--boundary_clip", type=float, default=0.0, metavar="D",
+                        help="clamp the signed distance of the boundary term at D pixels (0 = no clamp)")
+    parser.add_argument("--boundary_ramp_itrs", type=int, default=0, metavar="N",
+                        help="raise the boundary term's factor linearly from 0 to --boundary_weight over the first N "
+                             "iterations (0 = the full factor from the first one)")
     return parser
 
 
@@ -371,6 +406,9 @@ def setup_criterion(opts, class_weights, group=None):
     if getattr(opts, 'distill_ckpt', None) is not None:
         return DistillationLoss(temperature=opts.distill_temperature, ce_weight=opts.ce_weight,
                                 distill_weight=opts.distill_weight, weight=weight, ignore_index=255, group=group)
+    if getattr(opts, 'boundary_weight', 0.0) > 0:
+        return BoundaryLoss(classes='foreground', ce_weight=opts.ce_weight, boundary_weight=opts.boundary_weight,
+                            clip=getattr(opts, 'boundary_clip', 0.0), weight=weight, ignore_index=255, group=group)
     kind = getattr(opts, 'overlap_loss', 'none')
     if kind != 'none':
         common = dict(smooth=opts.overlap_smooth, classes=opts.overlap_classes, ce_weight=opts.ce_weight,
@@ -389,6 +427,13 @@ def setup_criterion(opts, class_weights, group=None):
     if opts.loss_type == 'ce_loss':
         return CrossEntropyLoss(ignore_index=255, reduction='mean', group=group)
     return CrossEntropyLoss(weight=class_weights, ignore_index=255, reduction='mean', group=group)
+
+
+def boundary_factor(opts, itr):
+    """the boundary term's factor at iteration `itr` (counted from 1): --boundary_weight, raised linearly from 0 over the first
+    --boundary_ramp_itrs iterations.  A function of the iteration alone, so a resumed run continues the ramp."""
+    weight, ramp = getattr(opts, 'boundary_weight', 0.0), getattr(opts, 'boundary_ramp_itrs', 0)
+    return weight * min(1.0, itr / ramp) if ramp > 0 else weight
 
 
 def validate(model, loader, device, opts):
@@ -692,6 +737,11 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
     clipping = bool(getattr(opts, "clip_grad_norm", 0.0))
     mining = isinstance(criterion, OhemCrossEntropyLoss)
     lovasz = isinstance(criterion, LovaszSoftmaxLoss)
+    boundary = isinstance(criterion, BoundaryLoss)
+    if boundary and rank == 0:
+        print("Boundary term: CE x %g + BD x %g%s%s" %
+              (opts.ce_weight, opts.boundary_weight, ", distance clamped at %g" % opts.boundary_clip if opts.boundary_clip else "",
+               ", ramped over %d iterations" % opts.boundary_ramp_itrs if opts.boundary_ramp_itrs else ""))
     teacher = None
     if getattr(opts, 'distill_ckpt', None) is not None:
         teacher = setup_teacher(opts, device, getattr(opts, '_teacher_ck', None))
@@ -733,6 +783,8 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
                 logits = net(images)
                 loss = criterion(logits, labels, teacher_logits)
             else:
+                if boundary:                                    # a host number: no synchronisation
+                    criterion.boundary_weight = boundary_factor(opts, cur_itrs)
                 logits = net(images)
                 loss = criterion(logits, labels)
             optimizer.zero_grad()
@@ -755,6 +807,8 @@ def _run(opts, device, rank, world, epoch, batches_per_epoch, val_loader, class_
                 if teacher is not None:                         # the last step's KD term and agreement of the global batch: one read-back
                     kd, agree, nvalid = torch.stack([criterion.last_terms[1].double(), *criterion.last_agreement]).tolist()
                     norm += ", kd=%.6f, agree=%.2f%%" % (kd, 100.0 * agree / nvalid if nvalid else 0.0)
+                if boundary:                                    # the last step's boundary term of the global batch: one read-back
+                    norm += ", bd=%.6f, lbd=%.6g" % (float(criterion.last_terms[1]), criterion.boundary_weight)
                 print("Epoch %d, Itrs %d/%d, Loss=%.6f, lr=%.3e, %.1f img/s%s" %
                       (cur_epochs, cur_itrs, opts.total_itrs, avg, optimizer.param_groups[0]['lr'], n_last / dt, norm))
                 interval_loss.zero_()

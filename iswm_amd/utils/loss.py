@@ -363,6 +363,80 @@ class DistillationLoss(nn.Module):
         return loss
 
 
+class _BoundaryLossFn(torch.autograd.Function):
+    """ce_weight * weighted CE + boundary_weight * mean over the valid pixels and the selected classes of p * phi, phi the
+    signed distance to the ground-truth contour, on the two-pass kernels (csrc/boundary.hip): the forward pass stores nothing
+    per pixel besides the distance map it is given, the backward pass reads logits, labels and map again and writes the
+    finished gradient once.  Nothing is read back.  With `group` the four sums {sum w nll, sum w, sum p phi, N} are
+    all-reduced before the coefficients are formed, so both normalisers are the global batch's and the SUM gradient all-reduce
+    of parallel.py yields the gradient of the global loss.  Good for one backward: a second one through the same call
+    (retain_graph) is refused."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, sd2, weight, ignore_index, classes, clip, ce_weight, boundary_weight, group):
+        sums = ops.boundary_loss_fwd(logits, labels, sd2, weight, ignore_index, classes, clip)
+        if group is not None:
+            import torch.distributed as dist
+            dist.all_reduce(sums, group=group)
+        out, coef = ops.boundary_loss_coeffs(sums, sd2.shape[1], ce_weight, boundary_weight)
+        ctx.save_for_backward(logits, labels, sd2, weight, coef)
+        ctx.ignore_index, ctx.classes, ctx.clip, ctx.consumed = ignore_index, classes, clip, False
+        ctx.mark_non_differentiable(sums, out)
+        return out[0].clone(), sums, out
+
+    @staticmethod
+    @once
+    def backward(ctx, upstream, _sums, _out):
+        if ctx.consumed:
+            raise RuntimeError("BoundaryLoss: %s" % CONSUMED)
+        ctx.consumed = True
+        logits, labels, sd2, weight, coef = ctx.saved_tensors
+        grad = ops.boundary_loss_bwd(logits, labels, sd2, weight, ctx.ignore_index, coef, _scalar(upstream), ctx.classes, ctx.clip)
+        return grad, None, None, None, None, None, None, None, None, None
+
+
+class BoundaryLoss(nn.Module):
+    """ce_weight * CrossEntropyLoss(weight, ignore_index) + boundary_weight * the boundary loss of Kervadec et al. (MIDL 2019):
+    the mean over the valid pixels and the classes of `classes` ('foreground': 1 .. C-1, 'all': 0 .. C-1) of
+    softmax probability x signed Euclidean distance to the class's ground-truth contour (negative inside the mask, clamped to
+    +-clip pixels when clip > 0).  The distance map is built from `targets` in every call, on the device and without a
+    gradient (ops.signed_edt: exact, sides up to 4096).  Under `group` both means run over all ranks' pixels.  At most 8 classes.
+
+    `boundary_weight` may be set between calls (a ramp): it is a host number handed to the coefficient kernel, so changing it
+    costs no synchronisation.  `last_terms` is a device view of {CE term, boundary term} of the last call and `last_valid` a
+    0-dim device view of N (of all ranks under `group`); reading either synchronises."""
+
+    def __init__(self, classes='foreground', ce_weight=1.0, boundary_weight=1.0, clip=0.0, weight=None, ignore_index=255,
+                 group=None):
+        super().__init__()
+        if classes not in ops.OVERLAP_CLASSES:
+            raise ValueError("classes is 'foreground' or 'all' (got %r)" % (classes,))
+        if not (0 <= ce_weight < math.inf and 0 <= boundary_weight < math.inf):
+            raise ValueError("ce_weight and boundary_weight must be finite and not negative")
+        if ce_weight == 0 and boundary_weight == 0:
+            raise ValueError("ce_weight 0 with boundary_weight 0 leaves no loss term")
+        if not (0 <= clip < math.inf):
+            raise ValueError("clip must be finite and not negative, 0 = no clamp (got %r)" % (clip,))
+        self.register_buffer('weight', None if weight is None else weight.detach().float().clone())
+        self.classes, self.ce_weight, self.boundary_weight, self.clip = classes, float(ce_weight), float(boundary_weight), float(clip)
+        self.ignore_index = ignore_index
+        self.group = group
+        self.last_terms = self.last_valid = None
+
+    def forward(self, inputs, targets):
+        targets = _check(inputs, targets)
+        lbd = float(self.boundary_weight)
+        if not (0 <= lbd < math.inf):
+            raise ValueError("boundary_weight must be finite and not negative (got %r)" % (self.boundary_weight,))
+        w = _weight_for(self.weight, inputs)
+        with torch.no_grad():
+            sd2 = ops.signed_edt(targets, inputs.shape[1], self.classes, self.ignore_index)
+        loss, sums, out = _BoundaryLossFn.apply(inputs, targets, sd2, w, self.ignore_index, self.classes, self.clip,
+                                                self.ce_weight, lbd, self.group)
+        self.last_terms, self.last_valid = out[1:], sums[3]
+        return loss
+
+
 def create_loss(loss_type="focal",temporal_loss="none", temporal_weight=0.5, **kwargs):
     """reference utils/loss.py:37-39"""
     return FocalLoss(**kwargs)
