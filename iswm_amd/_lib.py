@@ -1,6 +1,7 @@
 """ctypes binding of libiswm_hip.so, derived from include/iswm_hip.h (and its extension headers include/iswm_hip_sep.h,
-include/iswm_hip_kd.h and include/iswm_hip_bd.h, whose prototypes go to tables of their own, EXT_EXPORTS / _EXT_SIGS,
-KD_EXPORTS / _KD_SIGS and BD_EXPORTS / _BD_SIGS, parsed with the main header's types in scope) at import.
+include/iswm_hip_kd.h, include/iswm_hip_bd.h and include/iswm_hip_bm.h, whose prototypes go to tables of their own,
+EXT_EXPORTS / _EXT_SIGS, KD_EXPORTS / _KD_SIGS, BD_EXPORTS / _BD_SIGS and BM_EXPORTS / _BM_SIGS, parsed with the main header's
+types in scope) at import.
 
 The header is the only declaration of the C ABI.  It is parsed once here -- `re` and `ctypes`, nothing generated, neither
 the library nor torch loaded -- into
@@ -32,6 +33,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip.h")
 EXT_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_sep.h")
 KD_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_kd.h")
 BD_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_bd.h")
+BM_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_bm.h")
 
 # (`long long` is 8 bytes on every ABI the library is built for; tests/test_abi_cpu.py holds that)
 _SCALARS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "size_t": c_size_t, "float": c_float,
@@ -172,6 +174,14 @@ if _BD_CONSTANTS or _BD_STRUCTS:
 if set(_BD_SIGS) & (set(_EXT_SIGS) | set(_KD_SIGS)):
     raise ValueError("iswm_hip_bd.h declares %s again (an earlier extension header has it)" %
                      sorted(set(_BD_SIGS) & (set(_EXT_SIGS) | set(_KD_SIGS))))
+# the boundary-metrics header, the same way; a name of any earlier header is refused
+with open(BM_HEADER) as _f:
+    _BM_CONSTANTS, _BM_STRUCTS, _BM_SIGS = parse_header(_f.read(), base=_TEXT)
+if _BM_CONSTANTS or _BM_STRUCTS:
+    raise ValueError("iswm_hip_bm.h declares prototypes only, not %s" % sorted(set(_BM_CONSTANTS) | set(_BM_STRUCTS)))
+if set(_BM_SIGS) & (set(_EXT_SIGS) | set(_KD_SIGS) | set(_BD_SIGS)):
+    raise ValueError("iswm_hip_bm.h declares %s again (an earlier extension header has it)" %
+                     sorted(set(_BM_SIGS) & (set(_EXT_SIGS) | set(_KD_SIGS) | set(_BD_SIGS))))
 ConvDesc, QConvDesc, PredictView = STRUCTS["iswm_conv_desc"], STRUCTS["iswm_qconv_desc"], STRUCTS["iswm_predict_view"]
 
 
@@ -197,6 +207,7 @@ EXPORTS = tuple(_SIGS)
 EXT_EXPORTS = tuple(_EXT_SIGS)
 KD_EXPORTS = tuple(_KD_SIGS)
 BD_EXPORTS = tuple(_BD_SIGS)
+BM_EXPORTS = tuple(_BM_SIGS)
 _lib = None
 
 
@@ -217,7 +228,8 @@ def load():
     # two runtimes and the library's launches on torch's streams fail ("no ROCm-capable device is detected").
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_EXT_SIGS.items()) + list(_KD_SIGS.items()) + list(_BD_SIGS.items()):
+    for name, (res, args) in (list(_SIGS.items()) + list(_EXT_SIGS.items()) + list(_KD_SIGS.items()) + list(_BD_SIGS.items()) +
+                              list(_BM_SIGS.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -1199,6 +1199,43 @@ def signed_edt(labels, num_classes, classes='foreground', ignore_index=255):
     return sd2
 
 
+def boundary_metrics(pred, labels, num_classes, classes='foreground', ignore_index=255, tolerance=2, percent=95):
+    """The contour statistics of predicted masks pred [B,H,W] against labels [B,H,W] (each uint8 or int64, on the GPU), per image,
+    class of K (1 .. C-1 for 'foreground', 0 .. C-1 for 'all') and direction (0: predicted contour -> label contour, 1: the other
+    way) -> (stats int64 [B, |K|, 2, 4] = n, within tolerance, max d^2, d^2 of the percent-th nearest rank; dsum float64
+    [B, |K|, 2] = the sum of the distances), both on the device (include/iswm_hip_bm.h).  Sides up to 4096.  The workspace comes
+    from torch's allocator; nothing is read back."""
+    first = _first_class(classes)
+    for name, t in (("predictions", pred), ("labels", labels)):
+        if not (torch.is_tensor(t) and t.dim() == 3 and t.is_cuda and t.dtype in (torch.uint8, torch.int64)):
+            raise ValueError("the boundary metrics expect uint8 or int64 CUDA %s [B,H,W] (there is no CPU fallback)" % name)
+    if pred.shape != labels.shape or pred.device != labels.device:
+        raise ValueError("the boundary metrics expect predictions and labels of one shape on one device (got %s on %s and %s on %s)" %
+                         (tuple(pred.shape), pred.device, tuple(labels.shape), labels.device))
+    b, h, w = labels.shape
+    c = int(num_classes)
+    if c - first < 1:
+        raise ValueError("%d classes with classes=%r leave no class plane" % (c, classes))
+    if h > EDT_MAX_SIDE or w > EDT_MAX_SIDE:
+        raise ValueError("a %d x %d plane: the boundary metrics take sides up to %d" % (h, w, EDT_MAX_SIDE))
+    if b * h * w == 0:
+        raise ValueError("the boundary metrics of an empty label tensor %s" % (tuple(labels.shape),))
+    if isinstance(tolerance, bool) or int(tolerance) != tolerance or not 0 <= tolerance <= EDT_MAX_SIDE:
+        raise ValueError("tolerance is a whole number of pixels in [0, %d] (got %r)" % (EDT_MAX_SIDE, tolerance))
+    if isinstance(percent, bool) or int(percent) != percent or not 1 <= percent <= 100:
+        raise ValueError("percent is a whole number in [1, 100] (got %r)" % (percent,))
+    nbytes = _lib.load().iswm_boundary_metrics_workspace(b, c, h, w, first)
+    if nbytes < 0:
+        raise ValueError("the boundary metrics do not take labels %s with %d classes" % (tuple(labels.shape), c))
+    pred, labels = pred.contiguous(), labels.contiguous()
+    work = torch.empty((nbytes // 4,), dtype=torch.int32, device=labels.device)
+    stats = torch.empty((b, c - first, 2, 4), dtype=torch.int64, device=labels.device)
+    dsum = torch.empty((b, c - first, 2), dtype=torch.float64, device=labels.device)
+    call("iswm_boundary_metrics", _p(pred), pred.element_size(), _p(labels), labels.element_size(), b, c, h, w, first,
+         int(ignore_index), int(tolerance), int(percent), _p(stats), _p(dsum), _p(work), nbytes, _stream())
+    return stats, dsum
+
+
 def _boundary_args(logits, labels, sd2, weight, classes, clip):
     """the checks of the boundary-loss calls -> logits, labels, sd2, B, C, H * W, first class"""
     logits, labels, b, c, hw = _pixel_loss_args(logits, labels, weight, "the boundary loss")

@@ -97,7 +97,25 @@ class _ArgParser(argparse.ArgumentParser):
             self.error("--use_ema evaluates the EMA weights of a checkpoint: it needs --test_only and --ckpt")
         self._check_distill(opts)
         self._check_boundary(opts)
+        self._check_boundary_metrics(opts)
         return opts, rest
+
+    def _check_boundary_metrics(self, opts):
+        """--boundary_tolerance and --boundary_percentile: given only with --val_boundary_metrics; left out, they take 2 and 95"""
+        given = [flag for flag, value in (("--boundary_tolerance", opts.boundary_tolerance),
+                                          ("--boundary_percentile", opts.boundary_percentile)) if value is not None]
+        if not opts.val_boundary_metrics:
+            if given:
+                self.error("%s without --val_boundary_metrics: there is no boundary metric" % ", ".join(given))
+            return
+        if opts.boundary_tolerance is None:
+            opts.boundary_tolerance = 2
+        if opts.boundary_percentile is None:
+            opts.boundary_percentile = 95
+        if not 0 <= opts.boundary_tolerance <= ops.EDT_MAX_SIDE:
+            self.error("--boundary_tolerance must lie in [0, %d] pixels" % ops.EDT_MAX_SIDE)
+        if not 1 <= opts.boundary_percentile <= 100:
+            self.error("--boundary_percentile must lie in [1, 100]")
 
     def _check_boundary(self, opts):
         """the --boundary_* options: the term goes with the plain weighted CE of a training run only, and the clamp and the
@@ -259,6 +277,14 @@ def get_argparser():
     parser.add_argument("--boundary_ramp_itrs", type=int, default=0, metavar="N",
                         help="raise the boundary term's factor linearly from 0 to --boundary_weight over the first N "
                              "iterations (0 = the full factor from the first one)")
+    parser.add_argument("--val_boundary_metrics", action='store_true', default=False,
+                        help="validation also reports boundary precision / recall / F1 at --boundary_tolerance, ASSD, HD and "
+                             "HD95 between predicted and labelled contours of the foreground classes (exact distances on the "
+                             "device); model selection does not look at them")
+    parser.add_argument("--boundary_tolerance", type=int, default=None, metavar="PX",
+                        help="with --val_boundary_metrics: a contour pixel counts as matched within PX pixels (default 2)")
+    parser.add_argument("--boundary_percentile", type=int, default=None, metavar="Q",
+                        help="with --val_boundary_metrics: the nearest-rank percentile of the HD95 key, 1 to 100 (default 95)")
     return parser
 
 
@@ -443,12 +469,30 @@ def validate(model, loader, device, opts):
     from .metrics import StreamMetrics
     model.eval()
     metrics = StreamMetrics(opts.num_classes, device=device)
+    boundary = boundary_metrics_of(opts, device)
     with torch.no_grad():
         for images, labels in loader:
             logits = model(images.to(device, dtype=torch.float32))
-            metrics.update_logits(labels.to(device), logits)
+            labels = labels.to(device)
+            metrics.update_logits(labels, logits)
+            if boundary is not None:                            # one more argmax per batch, only with the flag on
+                boundary.update_logits(labels, logits)
     model.train()
-    return {k: float(v) for k, v in metrics.get_results().items()}
+    score = {k: float(v) for k, v in metrics.get_results().items()}
+    if boundary is not None:
+        score.update(boundary.get_results())
+    return score
+
+
+def boundary_metrics_of(opts, device):
+    """the BoundaryMetrics of --val_boundary_metrics (the criterion's ignore_index 255 and foreground classes), or None with the
+    flag off; options objects built without the flag are taken as off"""
+    if not getattr(opts, 'val_boundary_metrics', False):
+        return None
+    from .metrics import BoundaryMetrics
+    tolerance, percent = getattr(opts, 'boundary_tolerance', None), getattr(opts, 'boundary_percentile', None)
+    return BoundaryMetrics(opts.num_classes, classes='foreground', ignore_index=255, tolerance=2 if tolerance is None else tolerance,
+                           percent=95 if percent is None else percent, device=device)
 
 
 METRIC_WEIGHTS = {"MIoU": 0.05, "Foreground IoU": 0.25, "Foreground F1": 0.25, "Front Tracking Error": 0.25,
@@ -468,6 +512,10 @@ def validate_sequence(model, loader, device, opts):
             gts.append(labels.to(device))
     model.train()
     metrics = StreamMetrics(opts.num_classes, sequence_length=opts.sequence_length, device=device)
+    boundary = boundary_metrics_of(opts, device)
+    if boundary is not None:                                    # every frame once, not once per window; one call per batch
+        for p, g in zip(preds, gts):
+            boundary.update(g, p)
     L = opts.sequence_length
     if preds:
         preds, gts = torch.cat(preds), torch.cat(gts)
@@ -477,7 +525,10 @@ def validate_sequence(model, loader, device, opts):
         preds, gts = preds.index_select(0, idx), gts.index_select(0, idx)
         for i in range(preds.shape[0] - L + 1):
             metrics.update(gts[i:i + L], preds[i:i + L], sequence_data=True)
-    return {k: float(v) for k, v in metrics.get_results().items()}
+    score = {k: float(v) for k, v in metrics.get_results().items()}
+    if boundary is not None:
+        score.update(boundary.get_results())
+    return score
 
 
 def initialize_best_score():
