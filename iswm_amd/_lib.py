@@ -1,7 +1,7 @@
 """ctypes binding of libiswm_hip.so, derived from include/iswm_hip.h (and its extension headers include/iswm_hip_sep.h,
-include/iswm_hip_kd.h, include/iswm_hip_bd.h and include/iswm_hip_bm.h, whose prototypes go to tables of their own,
-EXT_EXPORTS / _EXT_SIGS, KD_EXPORTS / _KD_SIGS, BD_EXPORTS / _BD_SIGS and BM_EXPORTS / _BM_SIGS, parsed with the main header's
-types in scope) at import.
+include/iswm_hip_kd.h, include/iswm_hip_bd.h, include/iswm_hip_bm.h and include/iswm_hip_cr.h, whose prototypes go to tables of
+their own, EXT_EXPORTS / _EXT_SIGS, KD_EXPORTS / _KD_SIGS, BD_EXPORTS / _BD_SIGS, BM_EXPORTS / _BM_SIGS and CR_EXPORTS / _CR_SIGS,
+parsed with the main header's types in scope) at import.
 
 The header is the only declaration of the C ABI.  It is parsed once here -- `re` and `ctypes`, nothing generated, neither
 the library nor torch loaded -- into
@@ -34,6 +34,7 @@ EXT_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_sep.h")
 KD_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_kd.h")
 BD_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_bd.h")
 BM_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_bm.h")
+CR_HEADER = os.path.join(os.path.dirname(HERE), "include", "iswm_hip_cr.h")
 
 # (`long long` is 8 bytes on every ABI the library is built for; tests/test_abi_cpu.py holds that)
 _SCALARS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "size_t": c_size_t, "float": c_float,
@@ -182,6 +183,14 @@ if _BM_CONSTANTS or _BM_STRUCTS:
 if set(_BM_SIGS) & (set(_EXT_SIGS) | set(_KD_SIGS) | set(_BD_SIGS)):
     raise ValueError("iswm_hip_bm.h declares %s again (an earlier extension header has it)" %
                      sorted(set(_BM_SIGS) & (set(_EXT_SIGS) | set(_KD_SIGS) | set(_BD_SIGS))))
+# the CRF-refinement header, the same way; a name of any earlier header is refused
+with open(CR_HEADER) as _f:
+    _CR_CONSTANTS, _CR_STRUCTS, _CR_SIGS = parse_header(_f.read(), base=_TEXT)
+if _CR_CONSTANTS or _CR_STRUCTS:
+    raise ValueError("iswm_hip_cr.h declares prototypes only, not %s" % sorted(set(_CR_CONSTANTS) | set(_CR_STRUCTS)))
+if set(_CR_SIGS) & (set(_EXT_SIGS) | set(_KD_SIGS) | set(_BD_SIGS) | set(_BM_SIGS)):
+    raise ValueError("iswm_hip_cr.h declares %s again (an earlier extension header has it)" %
+                     sorted(set(_CR_SIGS) & (set(_EXT_SIGS) | set(_KD_SIGS) | set(_BD_SIGS) | set(_BM_SIGS))))
 ConvDesc, QConvDesc, PredictView = STRUCTS["iswm_conv_desc"], STRUCTS["iswm_qconv_desc"], STRUCTS["iswm_predict_view"]
 
 
@@ -208,6 +217,7 @@ EXT_EXPORTS = tuple(_EXT_SIGS)
 KD_EXPORTS = tuple(_KD_SIGS)
 BD_EXPORTS = tuple(_BD_SIGS)
 BM_EXPORTS = tuple(_BM_SIGS)
+CR_EXPORTS = tuple(_CR_SIGS)
 _lib = None
 
 
@@ -229,7 +239,7 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGS.items()) + list(_EXT_SIGS.items()) + list(_KD_SIGS.items()) + list(_BD_SIGS.items()) +
-                              list(_BM_SIGS.items())):
+                              list(_BM_SIGS.items()) + list(_CR_SIGS.items())):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -43,7 +43,8 @@ def build(force=False, verbose=True):
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("iswm_hip.h", "iswm_hip_sep.h", "iswm_hip_kd.h",
-                                                                                 "iswm_hip_bd.h", "iswm_hip_bm.h")]
+                                                                                 "iswm_hip_bd.h", "iswm_hip_bm.h",
+                                                                                 "iswm_hip_cr.h")]
     jobs = []
     objs = []
     for src in sources():

@@ -19,19 +19,12 @@
 // in float32); conf truncates (numpy astype(uint8)); the band compares conf with integer bounds the host derived
 // from the reference's fp64 expression conf / 255.0 >= min_prob, <= max_prob; no float atomics anywhere.
 #include "bilinear.h"
+#include "predict_tail.h"            // PM_BLOCK, PM_PIX, PredictPartial, the map tail and the workgroup sum
 #include "rowmap.h"
 
 namespace iswm {
 
-constexpr int PM_BLOCK = 256;
-constexpr int PM_PIX = 16;           // consecutive raster pixels per thread: one 16-B store per uint8 map
 constexpr int PM_MAX_GROUPS = 4;     // logits kept in registers for C <= 16; larger C re-samples in a second pass
-
-struct PredictPartial {              // one workgroup's share of one image (32 B)
-    double sum;
-    float mn, mx;
-    long long n_low, n_pred;
-};
 
 __global__ __launch_bounds__(256) void k_predict_normalize(const unsigned char* __restrict__ img, int N, int64_t HW,
                                                            float m0, float m1, float m2, float s0, float s1, float s2,
@@ -122,9 +115,7 @@ __global__ __launch_bounds__(PM_BLOCK) void k_predict_maps(const float* __restri
     const int64_t k_begin = p_begin / PM_PIX, k_end = (p_end + PM_PIX - 1) / PM_PIX;
     const float* base = yl + (size_t)n * Hi * Wi * ldx;
 
-    double sum = 0.0;
-    float mn = INFINITY, mx = -INFINITY;
-    long long n_low = 0, n_pred = 0;
+    ISWM_MAP_STATS_DECL;
     for (int64_t k = k_begin + (int64_t)blockIdx.x * PM_BLOCK + threadIdx.x; k < k_end;
          k += (int64_t)gridDim.x * PM_BLOCK) {
         const int64_t q0 = k * PM_PIX;
@@ -133,8 +124,7 @@ __global__ __launch_bounds__(PM_BLOCK) void k_predict_maps(const float* __restri
         int rem = (int)(q0 + j0 - p_begin);
         int oh = rem / Wo, ow = rem - oh * Wo;
         Lerp lh = src_index(sh, oh, Hi);
-        unsigned int wp[4] = {0u, 0u, 0u, 0u}, wc[4] = {0u, 0u, 0u, 0u}, wb[4] = {0u, 0u, 0u, 0u};
-        float pv[PM_PIX];
+        ISWM_MAP_CHUNK_DECL;
 #pragma unroll
         for (int j = 0; j < PM_PIX; ++j) {
             pv[j] = 0.f;
@@ -145,69 +135,15 @@ __global__ __launch_bounds__(PM_BLOCK) void k_predict_maps(const float* __restri
             const float* pd = base + ((size_t)lh.i1 * Wi + lw.i0) * ldx;
             const float* pe = base + ((size_t)lh.i1 * Wi + lw.i1) * ldx;
             const float p = fg_prob<G>(pa, pb, pd, pe, lh, lw, C, fg);
-            pv[j] = p;
-            const unsigned int vp = p > thr ? 255u : 0u;
-            const unsigned int vc = (unsigned int)(p * 255.0f);
-            const unsigned int vb = ((int)vc >= lo && (int)vc <= hi) ? 255u : 0u;
-            wp[j >> 2] |= vp << (8 * (j & 3));
-            wc[j >> 2] |= vc << (8 * (j & 3));
-            wb[j >> 2] |= vb << (8 * (j & 3));
-            sum += (double)p;
-            mn = fminf(mn, p);
-            mx = fmaxf(mx, p);
-            n_low += p < thr ? 1 : 0;
-            n_pred += vp ? 1 : 0;
+            ISWM_MAP_PIXEL(j, p, thr, lo, hi);
             if (++ow == Wo) {
                 ow = 0;
                 lh = src_index(sh, ++oh, Hi);
             }
         }
-        if (j0 == 0 && j1 == PM_PIX) {
-            *reinterpret_cast<uint4*>(pred + q0) = make_uint4(wp[0], wp[1], wp[2], wp[3]);
-            *reinterpret_cast<uint4*>(conf + q0) = make_uint4(wc[0], wc[1], wc[2], wc[3]);
-            *reinterpret_cast<uint4*>(band + q0) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
-            if (prob) {
-#pragma unroll
-                for (int j = 0; j < PM_PIX; j += 4)
-                    *reinterpret_cast<float4*>(prob + q0 + j) = make_float4(pv[j], pv[j + 1], pv[j + 2], pv[j + 3]);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < PM_PIX; ++j) {
-                if (j < j0 || j >= j1) continue;
-                const int sh8 = 8 * (j & 3);
-                pred[q0 + j] = (unsigned char)(wp[j >> 2] >> sh8);
-                conf[q0 + j] = (unsigned char)(wc[j >> 2] >> sh8);
-                band[q0 + j] = (unsigned char)(wb[j >> 2] >> sh8);
-                if (prob) prob[q0 + j] = pv[j];
-            }
-        }
+        ISWM_MAP_STORE(q0, j0, j1, pred, conf, band, prob);
     }
-
-    // workgroup reduction in a fixed order: wave shuffles, then wave 0 over the four wave results
-    __shared__ PredictPartial red[PM_BLOCK / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sum += __shfl_down(sum, off, 64);
-        mn = fminf(mn, __shfl_down(mn, off, 64));
-        mx = fmaxf(mx, __shfl_down(mx, off, 64));
-        n_low += __shfl_down(n_low, off, 64);
-        n_pred += __shfl_down(n_pred, off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = PredictPartial{sum, mn, mx, n_low, n_pred};
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        PredictPartial r = red[0];
-        for (int w = 1; w < PM_BLOCK / 64; ++w) {
-            r.sum += red[w].sum;
-            r.mn = fminf(r.mn, red[w].mn);
-            r.mx = fmaxf(r.mx, red[w].mx);
-            r.n_low += red[w].n_low;
-            r.n_pred += red[w].n_pred;
-        }
-        partials[(size_t)n * gridDim.x + blockIdx.x] = r;
-    }
+    ISWM_MAP_BLOCK_SUM(partials, (size_t)n * gridDim.x + blockIdx.x)
 }
 
 // stats[n] = {min p, max p, sum p, count(p < thr), count(pred)}: one wave per image; lane l takes the partials
@@ -626,14 +562,9 @@ static bool scene_plan_ok(const iswm_scene_plan& p) {
            p.ramp <= 1024 && (int64_t)p.nty * p.ntx <= 0x7fffffff;
 }
 
-// workgroups per image: about one chunk per thread, at most ~2048 workgroups in all
-static int predict_blocks_per_image(int N, int H, int W) {
-    const int64_t chunks = ((int64_t)H * W + PM_PIX - 1) / PM_PIX + 1;
-    int64_t b = (chunks + PM_BLOCK - 1) / PM_BLOCK;
-    const int64_t cap = N >= 2048 ? 1 : 2048 / N;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
+int launch_predict_stats(const PredictPartial* partials, int blocks, int N, double* stats, hipStream_t stream) {
+    hipLaunchKernelGGL(k_predict_stats, dim3(N), dim3(64), 0, stream, partials, blocks, stats);
+    return check_launch("predict_stats");
 }
 
 }  // namespace iswm
@@ -686,8 +617,7 @@ extern "C" int iswm_predict_maps(const float* yl, int N, int Hi, int Wi, int ldx
 #undef ISWM_PM
     int rc = check_launch("predict_maps");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_predict_stats, dim3(N), dim3(64), 0, (hipStream_t)stream, part, blocks, stats);
-    return check_launch("predict_stats");
+    return launch_predict_stats(part, blocks, N, stats, (hipStream_t)stream);
 }
 
 extern "C" int iswm_scene_plan_make(int H, int W, int tile, int overlap, iswm_scene_plan* out) {
@@ -761,8 +691,7 @@ extern "C" int iswm_scene_maps(const float* yl, const iswm_scene_plan* plan, int
 #undef ISWM_SM
     int rc = check_launch("scene_maps");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_predict_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, part, blocks, stats);
-    return check_launch("predict_stats");
+    return launch_predict_stats(part, blocks, 1, stats, (hipStream_t)stream);
 }
 
 extern "C" int iswm_predict_view_normalize(const unsigned char* img, int N, int H, int W, int Hv, int Wv, int flip,
@@ -831,6 +760,5 @@ extern "C" int iswm_predict_views_maps(const iswm_predict_view* views, int nview
 #undef ISWM_VM
     int rc = check_launch("predict_views_maps");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_predict_stats, dim3(N), dim3(64), 0, (hipStream_t)stream, part, blocks, stats);
-    return check_launch("predict_stats");
+    return launch_predict_stats(part, blocks, N, stats, (hipStream_t)stream);
 }

@@ -1689,6 +1689,77 @@ def predict_maps(yl, num_classes, fg, H, W, thr, min_prob, max_prob, want_prob=F
     return PredictMaps((pred, conf, band, prob, stats, packed))
 
 
+def prob_maps(prob, thr, min_prob, max_prob):
+    """fp32 CUDA probability [N, H, W] -> PredictMaps with predict_maps' rules, layout and order of summation (prob is the input
+    itself): fed the prob of a predict_maps call it gives that call's packed bytes (include/iswm_hip_cr.h).  Enqueues only."""
+    if not (torch.is_tensor(prob) and prob.dim() == 3 and prob.is_cuda and prob.dtype == torch.float32):
+        raise ValueError("the maps of a probability expect an fp32 CUDA tensor [N,H,W] (there is no CPU fallback)")
+    n, H, W = prob.shape
+    nbytes = _lib.load().iswm_prob_maps_workspace(n, H, W)
+    if nbytes < 0:
+        raise ValueError("the maps of a probability do not take the shape %s" % (tuple(prob.shape),))
+    prob = prob.contiguous()
+    dev = prob.device
+    lay = predict_maps_layout(n, H, W)
+    packed = torch.empty(lay["end"], dtype=torch.uint8, device=dev)
+    stats = packed[:40 * n].view(torch.float64).view(n, 5)
+    pred, conf, band = (packed[lay[k]:lay[k] + n * H * W].view(n, H, W) for k in ("pred", "conf", "band"))
+    lo, hi = band_bounds(min_prob, max_prob)
+    ws = torch.empty(max(1, nbytes), dtype=torch.uint8, device=dev)
+    call("iswm_prob_maps", _p(prob), n, H, W, float(thr), lo, hi, _p(pred), _p(conf), _p(band), _p(stats), _p(ws), nbytes,
+         _stream())
+    return PredictMaps((pred, conf, band, prob, stats, packed))
+
+
+CRF_MAX_RADIUS, CRF_MAX_STEP, CRF_MAX_ITERS, CRF_MAX_SIDE = 7, 4, 20, 8192
+
+
+def crf_check(iters, radius, step, w_bilateral, w_spatial, theta_alpha, theta_beta, theta_gamma):
+    """the parameter ranges of crf_refine (include/iswm_hip_cr.h); ValueError with the offending name"""
+    for name, v, hi in (("iters", iters, CRF_MAX_ITERS), ("radius", radius, CRF_MAX_RADIUS), ("step", step, CRF_MAX_STEP)):
+        if isinstance(v, bool) or int(v) != v or not (0 if name == "iters" else 1) <= v <= hi:
+            raise ValueError("%s is a whole number in [%d, %d] (got %r)" % (name, 0 if name == "iters" else 1, hi, v))
+    for name, v in (("w_bilateral", w_bilateral), ("w_spatial", w_spatial)):
+        if not (math.isfinite(v) and v >= 0):
+            raise ValueError("%s must be finite and not negative (got %r)" % (name, v))
+    for name, v in (("theta_alpha", theta_alpha), ("theta_beta", theta_beta), ("theta_gamma", theta_gamma)):
+        if not (math.isfinite(v) and v > 0):
+            raise ValueError("%s must be finite and positive (got %r)" % (name, v))
+
+
+def crf_refine(prob, img_u8, iters, radius=5, step=2, w_bilateral=10.0, w_spatial=3.0, theta_alpha=80.0, theta_beta=13.0,
+               theta_gamma=3.0):
+    """Local dense-CRF refinement of the foreground probability prob (fp32 CUDA [N,H,W]) on the frames img_u8 (uint8 CUDA
+    [N,H,W,3], RGB): `iters` mean-field updates over the (2 radius + 1)^2 window dilated by `step` (include/iswm_hip_cr.h, DESIGN.md
+    section 25) -> fp32 [N,H,W].  iters == 0 returns prob itself.  The defaults are ConvCRF's published values, unvalidated on this
+    project's data.  The workspace comes from torch's allocator; one launch per iteration, nothing is read back."""
+    crf_check(iters, radius, step, w_bilateral, w_spatial, theta_alpha, theta_beta, theta_gamma)
+    if not (torch.is_tensor(prob) and prob.dim() == 3 and prob.dtype == torch.float32):
+        raise ValueError("the refinement expects an fp32 probability [N,H,W]")
+    if not (torch.is_tensor(img_u8) and img_u8.dim() == 4 and img_u8.dtype == torch.uint8 and
+            tuple(img_u8.shape) == tuple(prob.shape) + (3,)):
+        raise ValueError("the refinement expects uint8 frames [N,H,W,3] for a probability %s (got %s %s)" %
+                         (tuple(prob.shape), tuple(img_u8.shape) if torch.is_tensor(img_u8) else type(img_u8).__name__,
+                          getattr(img_u8, "dtype", None)))
+    if not (prob.is_cuda and img_u8.is_cuda) or prob.device != img_u8.device:
+        raise ValueError("the refinement expects the probability and the frames on one CUDA device (got %s and %s; there is no "
+                         "CPU fallback)" % (prob.device, img_u8.device))
+    n, h, w = prob.shape
+    if n * h * w == 0 or h > CRF_MAX_SIDE or w > CRF_MAX_SIDE:
+        raise ValueError("the refinement takes planes of 1 to %d pixels a side (got %s)" % (CRF_MAX_SIDE, tuple(prob.shape)))
+    if iters == 0:
+        return prob
+    nbytes = _lib.load().iswm_crf_refine_workspace(n, h, w)
+    if nbytes < 0:
+        raise ValueError("the refinement does not take the shape %s" % (tuple(prob.shape),))
+    prob, img_u8 = prob.contiguous(), img_u8.contiguous()
+    work = torch.empty((nbytes // 4,), dtype=torch.float32, device=prob.device)
+    out = torch.empty_like(prob)
+    call("iswm_crf_refine", _p(prob), _p(img_u8), n, h, w, int(radius), int(step), int(iters), float(w_bilateral),
+         float(w_spatial), float(theta_alpha), float(theta_beta), float(theta_gamma), _p(out), _p(work), nbytes, _stream())
+    return out
+
+
 VAL_PANELS = ("original", "target_rgb", "pred_rgb", "overlay", "error", "pred", "conf")     # the packed order
 
 

@@ -2,7 +2,7 @@
 
     python -m iswm_amd.predict --input <dir> --ckpt <checkpoint> --save_val_results_to <out> \\
         [--save_confidence] [--save_binary] [--batch_size B] [--workers W] [--tile_size T [--tile_overlap O]]
-        [--tta_scales S1,S2,... ] [--tta_flip]
+        [--tta_scales S1,S2,... ] [--tta_flip] [--crf_iters T [--crf_radius R] [--crf_step D] ...]
 
 Every subfolder of ``--input`` is walked (process_images, predict.py:292-368) and each frame gets
 ``<out>/<subfolder>/<name>_predict.png`` (0/255 foreground mask), plus ``_confidence.png`` (uint8(p * 255), p = the
@@ -30,6 +30,13 @@ Same flags and defaults as the reference's get_argparser (predict.py:19-67).  Di
     int(H * s + 0.5) x int(W * s + 0.5)) and, with ``--tta_flip``, its mirror image after each; the maps are cut from
     that mean (TTAPredictor).  1 to 8 distinct scales in [0.25, 4.0].  With the defaults the
     whole-frame path runs unchanged.  Not combined with ``--tile_size``: TTA over windows is not built;
+  * new ``--crf_iters T`` (default 0: off) with ``--crf_radius`` (5), ``--crf_step`` (2), ``--crf_bilateral_weight`` (10),
+    ``--crf_spatial_weight`` (3), ``--crf_theta_alpha`` (80), ``--crf_theta_beta`` (13) and ``--crf_theta_gamma`` (3): T mean-field
+    iterations of a locally connected dense CRF pull the foreground probability onto the edges of the frame itself before the
+    maps are cut from it (ops.crf_refine, ops.prob_maps); the printed statistics are those of the refined
+    probability.  It follows every path -- whole frames, ``--tile_size`` (the whole scene is refined, not its windows) and
+    test-time augmentation -- and INT8 checkpoints.  The defaults are ConvCRF's published values and are unvalidated on
+    internal-wave frames.  A ``--crf_*`` flag without ``--crf_iters`` >= 1 is an error; with 0 nothing changes;
   * ``--binary_threshold`` is accepted and unused, as in the reference (predict.py:223);
   * ``--enable_wave_processing`` is refused: its synthetic "broken area" generator is random and draws with
     OpenCV, which is not a dependency here.  Its flags still parse;
@@ -121,7 +128,55 @@ def get_argparser():
                         help="test-time augmentation: add the horizontally mirrored view of every scale")
     parser.add_argument("--use_ema", action='store_true',
                         help="predict with the checkpoint's EMA weights (a checkpoint of train --ema_decay)")
+    parser.add_argument("--crf_iters", type=int, default=0, metavar="T",
+                        help="refine the foreground probability with T mean-field iterations of a locally connected dense CRF "
+                             "on the frame (0: off; at most 20)")
+    parser.add_argument("--crf_radius", type=int, default=None, metavar="R",
+                        help="CRF window radius in steps, 1 to 7 (default: 5; needs --crf_iters)")
+    parser.add_argument("--crf_step", type=int, default=None, metavar="D",
+                        help="CRF window dilation in pixels, 1 to 4 (default: 2; needs --crf_iters)")
+    parser.add_argument("--crf_bilateral_weight", type=float, default=None,
+                        help="weight of the colour-and-position message (default: 10; needs --crf_iters)")
+    parser.add_argument("--crf_spatial_weight", type=float, default=None,
+                        help="weight of the position-only message (default: 3; needs --crf_iters)")
+    parser.add_argument("--crf_theta_alpha", type=float, default=None,
+                        help="position scale of the bilateral kernel in pixels (default: 80; needs --crf_iters)")
+    parser.add_argument("--crf_theta_beta", type=float, default=None,
+                        help="colour scale of the bilateral kernel in grey levels (default: 13; needs --crf_iters)")
+    parser.add_argument("--crf_theta_gamma", type=float, default=None,
+                        help="position scale of the spatial kernel in pixels (default: 3; needs --crf_iters)")
     return parser
+
+
+CRF_FLAGS = (("crf_radius", "radius", 5), ("crf_step", "step", 2), ("crf_bilateral_weight", "w_bilateral", 10.0),
+             ("crf_spatial_weight", "w_spatial", 3.0), ("crf_theta_alpha", "theta_alpha", 80.0),
+             ("crf_theta_beta", "theta_beta", 13.0), ("crf_theta_gamma", "theta_gamma", 3.0))
+
+
+def crf_options(parser, opts):
+    """the keyword arguments of ops.crf_refine (iters included), or None when --crf_iters is 0; the flags left out are filled in
+    with their defaults.  A --crf_* flag without --crf_iters >= 1 and values outside ops.crf_check's ranges are argparse errors"""
+    from . import ops
+    given = ["--" + flag for flag, _, _ in CRF_FLAGS if getattr(opts, flag) is not None]
+    if not 0 <= opts.crf_iters <= ops.CRF_MAX_ITERS:
+        parser.error("--crf_iters %d must lie in [0, %d]" % (opts.crf_iters, ops.CRF_MAX_ITERS))
+    if opts.crf_iters == 0 and given:
+        parser.error("%s needs --crf_iters of at least 1" % ", ".join(given))
+    for flag, _, default in CRF_FLAGS:
+        if getattr(opts, flag) is None:
+            setattr(opts, flag, default)
+    crf = dict(((name, getattr(opts, flag)) for flag, name, _ in CRF_FLAGS), iters=opts.crf_iters)
+    try:
+        ops.crf_check(**crf)
+    except ValueError as e:
+        parser.error("--crf_*: %s" % e)
+    return crf if opts.crf_iters > 0 else None
+
+
+def _crf_maps(maps, frames, crf, thr, min_prob, max_prob):
+    """the maps of the probability of `maps` refined on the uint8 frames [N, H, W, 3] already on the device"""
+    from . import ops
+    return ops.prob_maps(ops.crf_refine(maps.prob, frames, **crf), thr, min_prob, max_prob)
 
 
 def tta_options(parser, opts):
@@ -318,13 +373,15 @@ def process_images(input_base_path, output_path, predict_batch, save_confidence,
 
 class DevicePredictor:
     """predict_batch for process_images: upload -> predict_normalize -> forward_lowres -> predict_maps -> one copy of
-    stats + the requested maps into pinned host memory"""
+    stats + the requested maps into pinned host memory.  With `crf` (crf_options) the probability is refined on the uploaded
+    frames and the maps are cut from that: two more calls, the same single copy."""
 
-    def __init__(self, model, device, num_classes, fg, pred_threshold, min_prob, max_prob, want_conf, want_band):
+    def __init__(self, model, device, num_classes, fg, pred_threshold, min_prob, max_prob, want_conf, want_band, crf=None):
         self.model, self.device = model, device
         self.num_classes, self.fg = num_classes, fg
         self.thr, self.min_prob, self.max_prob = pred_threshold, min_prob, max_prob
         self.want_conf, self.want_band = want_conf, want_band
+        self.crf = crf
 
     def __call__(self, batch):
         import torch
@@ -335,7 +392,10 @@ class DevicePredictor:
             img = pin.to(self.device, non_blocking=True)
             x = ops.predict_normalize(img, MEAN, STD)
             yl = self.model.forward_lowres(x)
-            maps = ops.predict_maps(yl, self.num_classes, self.fg, h, w, self.thr, self.min_prob, self.max_prob)
+            maps = ops.predict_maps(yl, self.num_classes, self.fg, h, w, self.thr, self.min_prob, self.max_prob,
+                                    want_prob=self.crf is not None)
+            if self.crf is not None:
+                maps = _crf_maps(maps, img, self.crf, self.thr, self.min_prob, self.max_prob)
             lay = ops.predict_maps_layout(n, h, w)
             end = lay["band"] + n * h * w if self.want_band else lay["conf"] + n * h * w if self.want_conf else \
                 lay["pred"] + n * h * w
@@ -357,10 +417,12 @@ class DevicePredictor:
 class ScenePredictor:
     """predict_batch for process_images over frames larger than the training crops: per frame, one upload, then
     ops.scene_tiles_normalize -> forward_lowres per batch of windows into one logits buffer, ops.scene_maps over all
-    windows, and one copy of stats + the requested maps into pinned host memory.  Nothing synchronises before wait()."""
+    windows, and one copy of stats + the requested maps into pinned host memory.  With `crf` (crf_options) the blended
+    probability is refined on the whole scene before the maps are cut.  Nothing synchronises before wait()."""
 
     def __init__(self, model, device, num_classes, fg, pred_threshold, min_prob, max_prob, want_conf, want_band,
-                 tile_size, tile_overlap, tile_batch=1):
+                 tile_size, tile_overlap, tile_batch=1, crf=None):
+        self.crf = crf
         self.model, self.device = model, device
         self.num_classes, self.fg = num_classes, fg
         self.thr, self.min_prob, self.max_prob = pred_threshold, min_prob, max_prob
@@ -389,7 +451,10 @@ class ScenePredictor:
                     if logits is None:      # sized once the first batch shows the low-resolution shape and pitch
                         logits = torch.empty((plan.ntiles,) + tuple(yl.shape[1:]), dtype=yl.dtype, device=yl.device)
                     logits[k0:k0 + count].copy_(yl)
-                maps = ops.scene_maps(logits, self.num_classes, self.fg, plan, self.thr, self.min_prob, self.max_prob)
+                maps = ops.scene_maps(logits, self.num_classes, self.fg, plan, self.thr, self.min_prob, self.max_prob,
+                                      want_prob=self.crf is not None)
+                if self.crf is not None:
+                    maps = _crf_maps(maps, scene.unsqueeze(0), self.crf, self.thr, self.min_prob, self.max_prob)
                 host[f].copy_(maps.packed[:end], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
@@ -408,10 +473,12 @@ class TTAPredictor:
     """predict_batch for process_images with test-time augmentation: one upload, then per view of ops.tta_views
     ops.predict_view_normalize -> forward_lowres on the whole frame batch with every view's logits kept, one
     ops.predict_views_maps over all of them, and one copy of stats + the requested maps into pinned host memory.
+    With `crf` (crf_options) the mean probability is refined on the frames before the maps are cut.
     Nothing synchronises before wait()."""
 
     def __init__(self, model, device, num_classes, fg, pred_threshold, min_prob, max_prob, want_conf, want_band,
-                 scales, flip):
+                 scales, flip, crf=None):
+        self.crf = crf
         self.model, self.device = model, device
         self.num_classes, self.fg = num_classes, fg
         self.thr, self.min_prob, self.max_prob = pred_threshold, min_prob, max_prob
@@ -429,7 +496,9 @@ class TTAPredictor:
             yls = [self.model.forward_lowres(ops.predict_view_normalize(img, hv, wv, f, MEAN, STD))
                    for hv, wv, f in views]
             maps = ops.predict_views_maps(yls, [f for _, _, f in views], self.num_classes, self.fg, h, w, self.thr,
-                                          self.min_prob, self.max_prob)
+                                          self.min_prob, self.max_prob, want_prob=self.crf is not None)
+            if self.crf is not None:
+                maps = _crf_maps(maps, img, self.crf, self.thr, self.min_prob, self.max_prob)
             lay = ops.predict_maps_layout(n, h, w)
             end = lay["band"] + n * h * w if self.want_band else lay["conf"] + n * h * w if self.want_conf else \
                 lay["pred"] + n * h * w
@@ -479,6 +548,7 @@ def main(argv=None):
     opts = parser.parse_args(argv)
     tile_size, tile_overlap = tile_options(parser, opts)
     tta = tta_options(parser, opts)
+    crf = crf_options(parser, opts)
     if opts.enable_wave_processing:
         get_argparser().error(WAVE_PROCESSING_REFUSED)
     if opts.batch_size < 1 or opts.workers < 1:
@@ -509,15 +579,15 @@ def main(argv=None):
     if tile_size > 0:                            # windows share a device batch; frames go one at a time
         predictor = ScenePredictor(model, device, num_classes, fg, opts.pred_threshold, opts.min_broken_prob,
                                    opts.max_broken_prob, opts.save_confidence, opts.save_binary, tile_size,
-                                   tile_overlap, tile_batch=opts.batch_size)
+                                   tile_overlap, tile_batch=opts.batch_size, crf=crf)
         frames = 1
     elif tta is not None:
         predictor = TTAPredictor(model, device, num_classes, fg, opts.pred_threshold, opts.min_broken_prob,
-                                 opts.max_broken_prob, opts.save_confidence, opts.save_binary, tta[0], tta[1])
+                                 opts.max_broken_prob, opts.save_confidence, opts.save_binary, tta[0], tta[1], crf=crf)
         frames = opts.batch_size
     else:
         predictor = DevicePredictor(model, device, num_classes, fg, opts.pred_threshold, opts.min_broken_prob,
-                                    opts.max_broken_prob, opts.save_confidence, opts.save_binary)
+                                    opts.max_broken_prob, opts.save_confidence, opts.save_binary, crf=crf)
         frames = opts.batch_size
     return process_images(opts.input, opts.save_val_results_to, predictor, opts.save_confidence, opts.save_binary,
                           pred_threshold=opts.pred_threshold, batch_size=frames, workers=opts.workers)
